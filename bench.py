@@ -32,6 +32,12 @@ whose logits do not match the reference arithmetic fails instead of printing a n
 read (smh_model_status).  `cpu_baseline` (rank 0, N = 1, default workload only, before the GPU is touched) times the CPU path
 (numpy rfft + scipy.ndimage.median_filter + the numpy restatement, `python -m oracle.cpu_baseline`) on one core and on all
 usable cores.
+
+`--dump-outputs DIR` writes, after the timed region, what the last timed step computed -- the arrays the caller of the timed
+path receives: `logits` (B*nP, out_dim) for the full path and config3, `featuregram` (B, 240, T) for config2 -- as DIR/<name>.npy
+(float32; `_rank<r>` appended under N > 1).  At most 64 MB in all: a larger output is cut to a fixed, seeded sample of its rows,
+whose indices go to DIR/<name>_rows.npy (float64).  The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -60,6 +66,7 @@ FLOPS_MODEL = 2.0 * (W_PATCH * FEAT * 32 + 24 * W_PATCH * (3 * 32 * 32 + 32 * 32
 # abs 1e-4 SURVEY 8(d') asks of the network alone.  Measured on MI355X: 2.9e-6.
 GOLDEN_LOGIT_TOL = 1e-4
 GOLDEN_LOGIT_TOL_SPLIT_BF16 = 3e-4  # split-bf16 network: measured 5-8e-5 from the f32 kernel
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all ranks' files together
 
 WORKLOADS = {
     # name: (batch, l_harm, l_perc, classes, model dtype, what runs)
@@ -109,7 +116,14 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal: start the ranks, join the process group (SMH_DIST_BACKEND, e.g. gloo on a CPU "
                          "box), run the timing protocol around an empty step and report value = null.  Measures nothing.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write the outputs of the last timed step as DIR/<name>.npy (float32, at most "
+                         "64 MB in all; a larger output is cut to a fixed, seeded sample of rows)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dry-run computes nothing: there are no outputs to dump")
     wl = WORKLOADS[args.workload]
     for k in ("batch", "l_harm", "l_perc", "classes", "model_dtype"):
         if getattr(args, k) is None:
@@ -127,6 +141,29 @@ def dry_run(args, ranks):
                           "ms_per_step": round(1e3 * elapsed / args.steps, 4), "dry_run": True,
                           "backend": ranks.backend}))
     ranks.close()
+
+
+def dump_outputs(outdir, outputs, rank, world):
+    """outputs: {name: device tensor} of the last timed step -> outdir/<name>[_rank<r>].npy; rows beyond this rank's share of
+    DUMP_LIMIT_BYTES are left out, the rows kept (a seeded choice, the same every run) are written next to them."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // (world * len(outputs))
+    suffix = "_rank%d" % rank if world > 1 else ""
+    written = {}
+    for name, t in outputs.items():
+        a = t.detach().float().cpu().numpy()
+        info = {"shape": list(a.shape)}
+        row_bytes = a[0].nbytes if a.ndim and a.shape[0] else 0
+        if a.nbytes > budget and row_bytes:
+            k = max(1, (budget - 4096) // (row_bytes + 8))  # + 8: the float64 row index; 4096: the two .npy headers
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(outdir, name + "_rows" + suffix + ".npy"), rows.astype(np.float64))
+            info["sampled_rows"] = int(k)
+        np.save(os.path.join(outdir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name + suffix] = info
+    return written
 
 
 def load_pmc():
@@ -216,6 +253,9 @@ def main():
     assert ran == world, "%d ranks ran the timed region, expected %d" % (ran, world)
     if hp is not None:
         logits = hp.logits
+    dumped = None
+    if args.dump_outputs:  # before the steady-state steps overwrite the buffers of the last timed step
+        dumped = dump_outputs(args.dump_outputs, {"featuregram": hp.fv} if model is None else {"logits": logits}, rank, world)
     if model is not None:
         model.check_status()  # a kernel that gave up (smh_model_status) fails the bench instead of handing back zeros
         assert torch.isfinite(logits).all(), "non-finite logits"
@@ -375,6 +415,8 @@ def main():
             res["hbm_roofline_pct_median_kernel"] = round(100 * kernels["median"]["frac"], 2)
         if cpu is not None:
             res["cpu_baseline"] = cpu
+        if dumped is not None:
+            res["outputs_dumped"] = {"dir": os.path.abspath(args.dump_outputs), "rank0_files": dumped}
         print(json.dumps(res))
     ranks.close()
 

@@ -63,6 +63,26 @@ def test_bench_other_baseline_configs_print_a_full_line(workload, unit, dominant
         assert "split bf16" in d["dtype"] and d["config"]["l_harm"] == 21
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the logits of the last timed step (the steady-state steps after it do not replace them), checked against
+    the committed oracle logits; config2's featuregram (96 MB at B = 1024) as a seeded sample of clips under 64 MB."""
+    import numpy as np
+    d = _json_line(["bench.py", "--steps", "3", "--warmup", "1", "--batch", "128", "--no-cpu-baseline", "--steady-steps", "2",
+                    "--dump-outputs", str(tmp_path / "full")])
+    assert d["steps"] == 3 and d["outputs_dumped"]["rank0_files"] == {"logits": {"shape": [128, 7]}}
+    logits = np.load(tmp_path / "full" / "logits.npy")
+    assert logits.dtype == np.float32 and logits.shape == (128, 7)
+    g = np.load(os.path.join(ROOT, "tests", "golden", "bench_golden.npz"))
+    assert np.max(np.abs(logits[:int(g["n_clips"])] - g["logits_17x17"][0])) <= 1e-4
+    d = _json_line(["bench.py", "--workload", "config2", "--steps", "2", "--warmup", "1", "--steady-steps", "0",
+                    "--dump-outputs", str(tmp_path / "fe")])
+    info = d["outputs_dumped"]["rank0_files"]["featuregram"]
+    fv, rows = np.load(tmp_path / "fe" / "featuregram.npy"), np.load(tmp_path / "fe" / "featuregram_rows.npy")
+    assert info["shape"][:2] == [1024, 240] and fv.shape == (info["sampled_rows"],) + tuple(info["shape"][1:])
+    assert fv.dtype == np.float32 and rows.dtype == np.float64 and len(rows) == len(fv) and np.isfinite(fv).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "fe").iterdir()) <= 64_000_000
+
+
 def test_bench_train_contract():
     d = _json_line(["tools/bench_train.py", "--steps", "3", "--warmup", "1", "--batch", "48"])
     assert d["unit"] == "clips/s" and d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["gradient_allreduce_bytes"] == 0

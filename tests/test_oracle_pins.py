@@ -1,9 +1,8 @@
 """CPU: pin the oracle against the boundary routines the reference delegates to and against the
 committed golden vectors.  No GPU, no product code."""
 import ctypes
-import importlib
+import hashlib
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -48,23 +47,28 @@ def test_c_oracle_median_and_patches():
         assert np.array_equal(po, ofe.extract_patches(FV, W, shift))
 
 
-def test_patches_vs_compiled_reference_module():
-    ref_dir = os.path.join(ROOT, "oracle", "_ref")
-    if not any(f.startswith("tools") and f.endswith(".so") for f in (os.listdir(ref_dir) if os.path.isdir(ref_dir) else [])):
-        pytest.skip("oracle/_ref not built")
-    sys.path.insert(0, ref_dir)
-    try:
-        tools = importlib.import_module("tools")
-    finally:
-        sys.path.remove(ref_dir)
+def _sha(a):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+@pytest.fixture(scope="module")
+def ref_tools_golden():
+    """Outputs of the reference's compiled tools module on the inputs below (tests/golden/make_ref_tools_golden.py)."""
+    return np.load(os.path.join(ROOT, "tests", "golden", "ref_tools_golden.npz"))
+
+
+def test_patches_vs_compiled_reference_module(ref_tools_golden):
+    g = ref_tools_golden
     rng = np.random.default_rng(5)
     for T in (69, 98, 137, 300):
         FV = rng.standard_normal((9, T)).astype(np.float32)
+        assert np.array_equal(_sha(FV), g["patches_T%d_in_sha" % T]), T
         for W, shift in ((68, 68), (68, 34), (99, 34), (249, 24)):
             FVt = ofe.tile_if_short(FV, W)
-            ref = tools.extract_patches(FVt, FVt.shape, W, shift)
             got = ofe.extract_patches(FVt, W, shift)
-            assert ref.dtype == got.dtype == np.float64 and np.array_equal(ref, got), (T, W, shift)
+            key = "patches_T%d_W%d_s%d" % (T, W, shift)
+            assert got.dtype == np.float64 and got.shape == tuple(g[key + "_shape"]), (T, W, shift)
+            assert np.array_equal(_sha(got), g[key + "_sha"]), (T, W, shift)
 
 
 def test_npatch_table_golden(golden_fe):
@@ -141,22 +145,6 @@ def test_b3mtl_dilated_conv_matches_torch():
         np.testing.assert_allclose(b3_mtl.conv1d_same(x, k, b, d), ref, atol=1e-5)
 
 
-def _ref_tools():
-    ref_dir = os.path.join(ROOT, "oracle", "_ref")
-    if not any(f.startswith("tools") and f.endswith(".so") for f in (os.listdir(ref_dir) if os.path.isdir(ref_dir) else [])):
-        pytest.skip("oracle/_ref not built")
-    sys.path.insert(0, ref_dir)
-    try:
-        tools = importlib.import_module("tools")
-    finally:
-        sys.path.remove(ref_dir)
-    ss = pytest.importorskip("scipy.signal")
-    # modern scipy.signal.medfilt keeps int64 where the 2021 one promoted to float64 (tools.pyx:98 expects
-    # double): rebind the module global, the reference source itself is untouched
-    tools.medfilt = lambda v, k: ss.medfilt(np.asarray(v, float), k)
-    return tools
-
-
 def _silence_case(c):
     from oracle import silence as sil
     from sm_hpss_mtl_amd.synth import gappy_clip
@@ -165,18 +153,21 @@ def _silence_case(c):
 
 
 @pytest.mark.parametrize("case", range(7))
-def test_remove_silence_vs_compiled_reference(case):
+def test_remove_silence_vs_compiled_reference(case, ref_tools_golden):
     from oracle import silence as sil
     from sm_hpss_mtl_amd.synth import SILENCE_CASES
-    tools = _ref_tools()
+    g = ref_tools_golden
     gaps = SILENCE_CASES[case][1]
     x, energy = _silence_case(case)
     assert energy.shape == (1 + len(x) // 160,) and energy.dtype == np.float32
-    ref_out, ref_sm, ref_fm, ref_tot = tools.removeSilence(x, len(x), energy, len(energy), 16000, 25, 10)
+    assert np.array_equal(_sha(np.concatenate([x, energy])), g["silence_c%d_in_sha" % case])
+    ref_len, ref_untouched, ref_n_sm, ref_tot = g["silence_c%d_meta" % case]
+    ref_sm = np.unpackbits(g["silence_c%d_sample_marker" % case])[:ref_n_sm]
     out, sm, fm, tot = sil.remove_silence(x, energy, 16000, 25, 10)
     assert tot == ref_tot
-    assert np.array_equal(fm, ref_fm) and np.array_equal(sm, ref_sm)
-    assert out.dtype == ref_out.dtype and np.array_equal(out, ref_out)
+    assert np.array_equal(fm, g["silence_c%d_frame_marker" % case]) and len(sm) == ref_n_sm and np.array_equal(sm, ref_sm)
+    assert out.dtype == np.dtype(str(g["silence_c%d_out_dtype" % case])) and len(out) == ref_len
+    assert np.array_equal(_sha(out), g["silence_c%d_out_sha" % case]) and int(out is x) == ref_untouched
     if out is not x:  # >= 2 qualifying runs: the reference's tail of ones
         n_keep = int(sm.sum())
         assert n_keep < len(x) and np.all(out[n_keep:] == 1.0)
@@ -187,7 +178,6 @@ def test_remove_silence_vs_compiled_reference(case):
 @pytest.mark.parametrize("case", range(7))
 def test_remove_silence_vs_golden(case):
     """The committed outputs of the compiled reference (tests/golden/make_silence_golden.py)."""
-    import hashlib
     from oracle import silence as sil
     g = np.load(os.path.join(ROOT, "tests", "golden", "silence_golden.npz"))
     x, energy = _silence_case(case)
@@ -221,26 +211,29 @@ def test_oracle_medfilt_vs_scipy(n, k):
     assert np.array_equal(oinf.medfilt(x, k), ss.medfilt(x, k))
 
 
-def test_scale_data_vs_compiled_reference():
+def test_scale_data_vs_compiled_reference(ref_tools_golden):
     from oracle import tools_stats
-    tools = _ref_tools()
+    g = ref_tools_golden
     rng = np.random.default_rng(3)
     for dt in (np.float32, np.float64):
         FV = rng.normal(size=(42, 68)).astype(dt) * 7 - 3
+        name = np.dtype(dt).name
+        assert np.array_equal(_sha(FV), g["scale_%s_in_sha" % name]), name
         mean, std = FV.mean(axis=1), FV.std(axis=1)
-        ref = tools.scale_data(FV, mean, std)
         got = tools_stats.scale_data(FV, mean, std)
-        assert got.dtype == ref.dtype == np.float64 and np.array_equal(got, ref)
+        assert got.dtype == np.float64 and got.shape == tuple(g["scale_%s_shape" % name])
+        assert np.array_equal(_sha(got), g["scale_%s_sha" % name]), name
 
 
 @pytest.mark.parametrize("stat", ["mean", "variance", "skew", "kurtosis"])
 @pytest.mark.parametrize("axis", [0, 1])
-def test_data_statistics_vs_compiled_reference(stat, axis):
+def test_data_statistics_vs_compiled_reference(stat, axis, ref_tools_golden):
     from oracle import tools_stats
-    tools = _ref_tools()
+    g = ref_tools_golden
     rng = np.random.default_rng(11)
     FV = rng.gamma(2.0, size=(5, 21, 34)) - rng.normal(size=(5, 21, 34)) ** 2
-    ref = tools.get_data_statistics(FV, stat_type=stat, axis=axis)
+    assert np.array_equal(_sha(FV), g["stats_in_sha"])
+    ref = g["stats_%s_%d" % (stat, axis)]
     got = tools_stats.get_data_statistics(FV, stat, axis)
     assert got.shape == ref.shape == (5, 34 if axis == 0 else 21)
     np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-13)
