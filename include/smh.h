@@ -237,6 +237,15 @@ typedef struct smh_model_cfg {
 #define SMH_TCN_BLOCK_2_8 1
 
 int smh_model_create(const smh_model_cfg *cfg, smh_model **out);
+/* Head kind of the model.  SMH_HEADS_MTL: the independent heads of MTL_modifications (lib/proposed_architectures.py:25-80) -- what
+ * smh_model_create builds.  SMH_HEADS_CASCADED: get_Lemaire_Cascaded_MTL_model (:175-323): the same trunk, '3C' and Dense(16) layers;
+ * R = Dense(2)(Dropout(relu(BN(Dense16)))); S and M = sigmoid(Dense(1)(BN18(concat[Dropout(relu(BN(Dense16))), R]))).  Heads are
+ * always S, M, R[2] (n_classes widens '3C' only), so out_dim = 4 + n_classes.  Canonical order as for SMH_HEADS_MTL except that S and
+ * M carry, between their moving_variance and out kernel, the concatenation BatchNorm [gamma, beta, moving_mean, moving_variance]
+ * (18 each) and an out kernel of shape (18, 1).  The bf16 forwards and trainer dtype 1 refuse a cascaded model. */
+#define SMH_HEADS_MTL 0
+#define SMH_HEADS_CASCADED 1
+int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_model **out);
 void smh_model_destroy(smh_model *m);
 /* number of float32 parameters in canonical (Keras-layout) order, see DESIGN.md "weight order" */
 size_t smh_model_num_params(const smh_model *m);
@@ -410,7 +419,8 @@ int smh_train_step_f32(smh_trainer *t, const float *d_x, const float *d_y, int N
  * BN moving statistics <- 0.99*old + 0.01*batch; operand buffers re-packed on the device.              */
 int smh_trainer_apply_sgd_f32(smh_trainer *t, float lr, float momentum, float clipnorm, float grad_scale, void *stream);
 /* floats of the data-parallel bucket that starts at smh_trainer_grad_ptr: [gradient (num_params) | BatchNorm batch
- * statistics of the heads]; all-reduce all of it so the moving statistics follow the mean over the ranks. */
+ * statistics of the heads (4 x 32) | cascaded models only: the concatenation BatchNorm's statistics of S and M (2 x 36)];
+ * all-reduce all of it so the moving statistics follow the mean over the ranks. */
 size_t smh_trainer_bucket_floats(const smh_trainer *t);
 /* copy momentum / Adam moments / step counters from `src` to `dst` (same model): growing a trainer keeps its state */
 int smh_trainer_copy_state(smh_trainer *dst, const smh_trainer *src, void *stream);
@@ -427,7 +437,8 @@ int smh_trainer_set_deterministic(smh_trainer *t, int on, void *stream);
  * bf16, three bf16 products per f32 product, f32 accumulators; master weights, gates, losses, heads, the Dense gradients and the
  * optimiser stay f32.  The forward's outputs are within 1e-4 of the f32 forward's; the backward agrees with the f32 backward on the same
  * forward to 2e-4 (relative L2 per tensor); against the float64 oracle the gradients sit where the forward's 1e-5 puts the relu /
- * channel-maximum gates (2-3e-2 of a tensor's norm).  Patches longer than 128 frames keep the f32 backward. */
+ * channel-maximum gates (2-3e-2 of a tensor's norm).  Patches longer than 128 frames keep the f32 backward.
+ * A cascaded model (SMH_HEADS_CASCADED) accepts dtype 0 only. */
 int smh_trainer_set_dtype(smh_trainer *t, int dtype);
 /* General optimiser step.  optimizer 0 = SGD (beta1 = momentum; what smh_trainer_apply_sgd_f32 calls), 1 = Adam,
  * 2 = Nadam as tf.keras 2.x implements it (momentum schedule u_t = beta1 (1 - 0.5 * 0.96^(0.004 t)); the optimiser of the

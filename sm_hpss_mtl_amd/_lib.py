@@ -86,6 +86,7 @@ SIGNATURES = {
     "smh_scale_data_f64": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "smh_data_statistics_f64": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "smh_model_create": (_i, [C.POINTER(ModelCfg), C.POINTER(_vp)]),
+    "smh_model_create_heads": (_i, [C.POINTER(ModelCfg), _i, C.POINTER(_vp)]),
     "smh_model_destroy": (None, [_vp]),
     "smh_model_num_params": (_sz, [_vp]),
     "smh_model_set_weights": (_i, [_vp, _vp, _sz, _vp]),

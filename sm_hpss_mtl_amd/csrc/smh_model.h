@@ -15,6 +15,10 @@ constexpr int kMaxG = 16;      // patches per workgroup <= MFMA N
 constexpr int kPS = 80;        // row stride of the Dense-on-trunk outputs: up to 5 M-tiles (5-class: 69 outputs)
 constexpr float kNormEps = 1e-5f;
 constexpr float kBnEps = 1e-3f;
+constexpr int kCat = kHidden + 2;  // cascaded heads: width of concat[Dropout(16) of S or M, R's two outputs]
+// packed per-head tail of a cascaded S / M head in `hp` and in canonical order: [gamma, beta, moving_mean, moving_var (16 each),
+// cat gamma, cat beta, cat moving_mean, cat moving_var (18 each), out kernel (18, 1), out bias]
+constexpr int kCatTail = 4 * kHidden + 4 * kCat + kCat + 1;
 // Packed per-block weights: 64 A-operand slots per lane (48 dilated-conv + 16 1x1), four slots per lane contiguous
 // ([slot / 4][lane][slot % 4], see load_block_lds), then [b1 32][b2 32]
 constexpr int kBlockFloats = 24 * 2 * 64 + 8 * 2 * 64 + 32 + 32;
@@ -33,6 +37,7 @@ struct TcnArgs {
                          // featuregram of x0_T frames; patch n is the window of T frames starting at min(n * x0_shift, x0_T - T)
     int head_odim[kMaxHeads];
     int head_sigmoid[kMaxHeads];
+    int cascade;  // SMH_HEADS_CASCADED: heads S and M read BN18(concat[their Dropout(16), R's output]) (smh_tcn_heads.h)
 };
 
 // training-mode extras of the forward kernel (all optional)
@@ -62,6 +67,13 @@ struct HeadsArgs {
 // ticket: one zero-initialised device word the kernel's workgroups count themselves on (left at zero again)
 int launch_heads_train(const HeadsArgs &a, const float *pre, const float *y, const float *hp, const float *drop, float *dpre,
                        float *dxh, float *grad, float *bnstat, float *losses, unsigned *ticket, hipStream_t st);
+// The same for the cascaded heads (smh_train_cascade.hip; a.n_heads = 3: S, M, R[2]).  dr: (2, N, 2) scratch for d loss / d r of
+// S and M; bnstat also receives the BN18 batch statistics of S and M at kMaxHeads * 32 + h * 2 * kCat (means, then variances).
+int launch_cascade_heads_train(const HeadsArgs &a, const float *pre, const float *y, const float *hp, const float *drop,
+                               float *dpre, float *dxh, float *dr, float *grad, float *bnstat, float *losses, hipStream_t st);
+// floats of the BatchNorm batch-statistics part of the trainer's bucket
+constexpr int kBnStatFloats = kMaxHeads * 32;
+constexpr int kCatStatFloats = 2 * 2 * kCat;
 
 }  // namespace smh_tcn
 
@@ -69,6 +81,8 @@ struct smh_model {
     smh_model_cfg cfg;
     int n_blocks, n_heads, NH, n_mt, D, out_dim, FQ;
     int head_odim[smh_tcn::kMaxHeads], head_sigmoid[smh_tcn::kMaxHeads];
+    int heads = 0;                      // SMH_HEADS_MTL / SMH_HEADS_CASCADED
+    int head_cat[smh_tcn::kMaxHeads];   // kCat for a head that reads the concatenation (cascaded S, M), else 0
     size_t n_params;
     float *d_flat = nullptr;  // master weights, canonical (Keras-layout) order, n_params floats
     float *d_W0 = nullptr;    // layer-0 A operands + bias0
@@ -89,6 +103,11 @@ struct smh_model {
 };
 
 namespace smh_tcn {
+// floats of head h behind its Dense(16) kernel and bias (canonical order = the packed `hp` block)
+inline size_t head_tail_floats(const smh_model *m, int h) {
+    const int od = m->head_odim[h], cat = m->head_cat[h];
+    return cat ? (size_t)4 * kHidden + 4 * cat + (size_t)cat * od + od : (size_t)4 * kHidden + (size_t)kHidden * od + od;
+}
 // canonical offsets
 struct Offsets {
     size_t w0_k, w0_b;                 // initial conv kernel / bias

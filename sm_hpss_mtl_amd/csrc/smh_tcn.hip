@@ -1069,9 +1069,8 @@ static void pack_host(const smh_model *m, const float *h, std::vector<float> &W0
         for (int i = 0; i < D; ++i)
             for (int c = 0; c < kHidden; ++c) Wh[(size_t)i * NH + ncls + hd * kHidden + c] = kd[(size_t)i * kHidden + c];
         for (int c = 0; c < kHidden; ++c) bhv[ncls + hd * kHidden + c] = bd[c];
-        const int od = m->head_odim[hd];
-        const size_t cnt = 4 * kHidden + (size_t)kHidden * od + od;
-        std::memcpy(php, p, cnt * sizeof(float));  // gamma beta mean var Wout bout are contiguous in canonical order
+        const size_t cnt = head_tail_floats(m, hd);
+        std::memcpy(php, p, cnt * sizeof(float));  // gamma beta mean var [cat BN] Wout bout are contiguous in canonical order
         php += cnt;
         p += cnt;
     }
@@ -1120,7 +1119,7 @@ Offsets offsets(const smh_model *m) {
     o.c3_b = p, p += ncls;
     for (int h = 0; h < m->n_heads; ++h) {
         o.head[h] = p;
-        p += D * kHidden + kHidden + 4 * kHidden + (size_t)kHidden * m->head_odim[h] + m->head_odim[h];
+        p += D * kHidden + kHidden + head_tail_floats(m, h);
     }
     return o;
 }
@@ -1146,6 +1145,7 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     a.D = m->D, a.NH = m->NH, a.n_mt = m->n_mt, a.n_classes = m->cfg.n_classes, a.n_heads = m->n_heads;
     a.out_dim = m->out_dim;
     for (int i = 0; i < kMaxHeads; ++i) a.head_odim[i] = m->head_odim[i], a.head_sigmoid[i] = m->head_sigmoid[i];
+    a.cascade = m->heads == SMH_HEADS_CASCADED;
     // patches per workgroup: up to 272 rows (17 column tiles) of LDS-resident activations, at most one
     // MFMA tile of patches, and never fewer workgroups than CUs when the batch allows it
     int gmax = 272 / T;
@@ -1263,7 +1263,13 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
 }  // namespace smh_tcn
 
 extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
+    return smh_model_create_heads(cfg, SMH_HEADS_MTL, out);
+}
+
+extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_model **out) {
     SMH_REQUIRE(cfg && out, "smh_model_create: null argument");
+    SMH_REQUIRE(heads == SMH_HEADS_MTL || heads == SMH_HEADS_CASCADED, "smh_model_create_heads: heads must be %d (MTL) or %d (cascaded), got %d",
+                SMH_HEADS_MTL, SMH_HEADS_CASCADED, heads);
     SMH_REQUIRE(cfg->nb_filters == C, "B3_MTL kernel is tiled for nb_filters=32 (got %d)", cfg->nb_filters);
     SMH_REQUIRE(cfg->kernel_size == 3, "B3_MTL kernel supports kernel_size=3 (got %d)", cfg->kernel_size);
     SMH_REQUIRE(cfg->n_classes == 3 || cfg->n_classes == 5, "n_classes must be 3 or 5 (got %d)", cfg->n_classes);
@@ -1273,7 +1279,14 @@ extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
     smh_model *m = new smh_model();
     m->cfg = *cfg;
     m->n_blocks = cfg->nb_stacks * cfg->n_dilations;
-    if (cfg->n_classes == 5) {  // 5_class_classification.py:150-215: S, M, N, R(3)
+    m->heads = heads;
+    for (int i = 0; i < kMaxHeads; ++i) m->head_cat[i] = 0;
+    if (heads == SMH_HEADS_CASCADED) {  // proposed_architectures.py:175-323: S, M, R(2) whatever n_classes is
+        m->n_heads = 3;
+        const int od[3] = {1, 1, 2}, sg[3] = {1, 1, 0};
+        for (int i = 0; i < 3; ++i) m->head_odim[i] = od[i], m->head_sigmoid[i] = sg[i];
+        m->head_cat[0] = m->head_cat[1] = kCat;
+    } else if (cfg->n_classes == 5) {  // 5_class_classification.py:150-215: S, M, N, R(3)
         m->n_heads = 4;
         const int od[4] = {1, 1, 1, 3}, sg[4] = {1, 1, 1, 0};
         for (int i = 0; i < 4; ++i) m->head_odim[i] = od[i], m->head_sigmoid[i] = sg[i];
@@ -1294,8 +1307,7 @@ extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
     if (cfg->block_variant == 1)
         n = (size_t)3 * cfg->n_feat * C + C + 3 * C * C + C + (size_t)cfg->n_feat * C + C + (size_t)(m->n_blocks - 1) * 2 * (3 * C * C + C);
     n += (size_t)m->D * cfg->n_classes + cfg->n_classes;
-    for (int i = 0; i < m->n_heads; ++i)
-        n += (size_t)m->D * kHidden + kHidden + 4 * kHidden + (size_t)kHidden * m->head_odim[i] + m->head_odim[i];
+    for (int i = 0; i < m->n_heads; ++i) n += (size_t)m->D * kHidden + kHidden + head_tail_floats(m, i);
     m->n_params = n;
     SMH_REQUIRE(n < (1u << 24), "model too large for the float-encoded gather map");
     m->nW0 = (size_t)m->FQ * 2 * 64 + 32;
@@ -1303,7 +1315,7 @@ extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
     if (cfg->block_variant == 1) m->nW0 = m->nWb = 0;
     m->nWhA = (size_t)m->D * 64 * ((m->NH + 63) / 64) + (size_t)m->n_mt * 16;
     m->nhp = 0;
-    for (int i = 0; i < m->n_heads; ++i) m->nhp += 4 * kHidden + (size_t)kHidden * m->head_odim[i] + m->head_odim[i];
+    for (int i = 0; i < m->n_heads; ++i) m->nhp += head_tail_floats(m, i);
     // gather map = the host packing applied to 1, 2, 3, ... (0 marks padding)
     std::vector<float> iota(n), W0, Wb, WhA, hp;
     for (size_t i = 0; i < n; ++i) iota[i] = (float)(i + 1);

@@ -913,6 +913,8 @@ static int forward_bf16(smh_model *m, const float *d_x, int N, float *d_out, int
     SMH_REQUIRE(!tio || split, "smh_model_forward_bf16: the training forward exists for split operands only");
     SMH_REQUIRE(N >= 0, "smh_model_forward_bf16: N=%d", N);
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_model_forward_bf16: built for block_variant 0 only");
+    SMH_REQUIRE(m->heads == SMH_HEADS_MTL, "smh_model_forward_bf16: the bf16 forward has the B3_MTL heads only, not the cascaded "
+                "heads of this model (use smh_model_forward_f32)");
     SMH_REQUIRE(m->cfg.n_feat <= 256, "smh_model_forward_bf16: n_feat=%d exceeds the 256 features of the bf16 layer-0 tiling",
                 m->cfg.n_feat);
     if (N == 0) return SMH_OK;

@@ -9,6 +9,54 @@
 
 namespace smh_tcn {
 
+// Inference-mode R head of the cascaded model (get_Lemaire_Cascaded_MTL_model): r = Dense(2)(relu(BN(Dense16))) of one patch from
+// its Dense-on-trunk outputs `pp` (+ biases `bh`).  The S and M threads call it as well -- 16 BN / relu and 32 FMAs -- so all three
+// see bit-identical r without a barrier.
+__device__ __forceinline__ void cascaded_r(const TcnArgs &a, const float *pp, const float *bh, const float *hp, float r[2]) {
+    const float *ph = hp + 2 * kCatTail;  // R follows the two cascaded tails
+    const float *gamma = ph, *beta = ph + 16, *mean = ph + 32, *var = ph + 48, *wo = ph + 64, *bo = wo + 2 * kHidden;
+    r[0] = bo[0], r[1] = bo[1];
+#pragma unroll
+    for (int i = 0; i < kHidden; ++i) {
+        const int o = a.n_classes + 2 * kHidden + i;
+        float v = pp[o] + bh[o];
+        v = (v - mean[i]) / sqrtf(var[i] + kBnEps);
+        v = fmaxf(v * gamma[i] + beta[i], 0.f);
+        r[0] = fmaf(v, wo[2 * i], r[0]);
+        r[1] = fmaf(v, wo[2 * i + 1], r[1]);
+    }
+}
+
+// one (patch, head) of the cascaded tail: h = 2 writes R, h = 0 / 1 writes sigmoid(Dense(1)(BN18(concat[relu(BN(Dense16)), r])))
+__device__ __forceinline__ void cascaded_head(const TcnArgs &a, const float *pp, const float *bh, const float *hp, float *orow, int h) {
+    float r[2];
+    cascaded_r(a, pp, bh, hp, r);
+    if (h == 2) {
+        orow[2] = r[0], orow[3] = r[1];
+        return;
+    }
+    const float *ph = hp + h * kCatTail;
+    const float *gamma = ph, *beta = ph + 16, *mean = ph + 32, *var = ph + 48;
+    const float *cg = ph + 64, *cb = cg + kCat, *cm = cb + kCat, *cv = cm + kCat, *wo = cv + kCat;
+    float s = wo[kCat];  // out bias
+#pragma unroll
+    for (int i = 0; i < kCat; ++i) {
+        float z;
+        if (i < kHidden) {
+            const int o = a.n_classes + h * kHidden + i;
+            float v = pp[o] + bh[o];
+            v = (v - mean[i]) / sqrtf(var[i] + kBnEps);
+            z = fmaxf(v * gamma[i] + beta[i], 0.f);
+        } else {
+            z = r[i - kHidden];
+        }
+        z = (z - cm[i]) / sqrtf(cv[i] + kBnEps);  // the concatenation BatchNorm: no relu behind it
+        z = z * cg[i] + cb[i];
+        s = fmaf(z, wo[i], s);
+    }
+    orow[h] = 1.0f / (1.0f + expf(-s));
+}
+
 template <bool TRAIN>
 __device__ __forceinline__ void dense_and_heads(const TcnArgs &a, const float *xin, float *xout, const float *__restrict__ WhA,
                                                 const float *__restrict__ hp, float *__restrict__ out, const TrainIO &tio,
@@ -99,7 +147,9 @@ __device__ __forceinline__ void dense_and_heads(const TcnArgs &a, const float *x
         return;
     }
     const int tid = threadIdx.x;
-    if (tid < g_here * a.n_heads) {
+    if (a.cascade && tid < g_here * a.n_heads) {
+        cascaded_head(a, pre + (tid / a.n_heads) * kPS, bh, hp, out + (size_t)(n0 + tid / a.n_heads) * a.out_dim, tid % a.n_heads);
+    } else if (tid < g_here * a.n_heads) {
         const int p = tid / a.n_heads, h = tid - p * a.n_heads;
         const float *ph = hp;
         int col = 0;

@@ -19,6 +19,7 @@
 
 #include "smh_model.h"
 #include "smh_train_bwd.h"
+#include "smh_wave.h"
 
 using namespace smh_tcn;
 
@@ -33,25 +34,6 @@ constexpr int kBThreads = 1024;
 
 using smh_tcn::HeadsArgs;
 
-// Sum over the 64 lanes, result in every lane, on the VALU's lane-permute paths: four DPP steps inside each row of 16 lanes
-// (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror), then gfx950's v_permlane32_swap / v_permlane16_swap
-// across the rows.  (__shfl_xor is a ds_bpermute per step -- an LDS round trip, six of them in a dependent chain: the
-// heads kernel makes ~350 of these sums per step and spent most of its time in them.)
-__device__ __forceinline__ float wave_sum_f(float v) {
-    auto dpp = [](float x, auto ctrl) {
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xF, 0xF, false));
-    };
-    v += dpp(v, std::integral_constant<int, 0xB1>{});   // quad_perm [1,0,3,2]
-    v += dpp(v, std::integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
-    v += dpp(v, std::integral_constant<int, 0x141>{});  // row_half_mirror
-    v += dpp(v, std::integral_constant<int, 0x140>{});  // row_mirror: every lane holds the sum of its row of 16
-    const unsigned u = __float_as_uint(v);
-    const auto r32 = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    v = __uint_as_float(r32[0]) + __uint_as_float(r32[1]);
-    const unsigned u2 = __float_as_uint(v);
-    const auto r16 = __builtin_amdgcn_permlane16_swap(u2, u2, false, false);
-    return __uint_as_float(r16[0]) + __uint_as_float(r16[1]);
-}
 // sum over the wave, added to THIS wave's own accumulator row (all lanes must call it; idle lanes pass 0): a plain
 // read-add-write by lane 0 -- no other wave touches the row, so no float atomic (ds_add_f32 is slow and orders nothing);
 // the rows are added up in wave order afterwards, which also makes the sums reproducible
@@ -1245,7 +1227,7 @@ struct smh_trainer {
     smh_model *m;
     int max_batch, nseg;
     float *d_acts = nullptr, *d_pre = nullptr, *d_dpre = nullptr, *d_dxh = nullptr;
-    // ONE bucket [gradient (n_params) | BatchNorm batch statistics (kMaxHeads * 32)]: what data-parallel training all-reduces
+    // ONE bucket [gradient (n_params) | BatchNorm batch statistics (bn_floats)]: what data-parallel training all-reduces
     float *d_grad = nullptr, *d_bnstat = nullptr;
     float *d_vel = nullptr, *d_s2 = nullptr;  // optimiser state: momentum / first moment, second moment
     unsigned long long *d_gq = nullptr;       // deterministic mode: fixed-point gradient accumulators (n_params), else nullptr
@@ -1254,6 +1236,8 @@ struct smh_trainer {
     float *d_gt = nullptr;       // (max_batch, T, 32): d loss / d (TCN output), dtrunk_kernel's product for the f32 backward
     void *d_bwd_pack = nullptr;  // the blocks' kernels as split bf16 A operands of the backward pass (smh_train_bf16.hip), dtype 1 only
     size_t bwd_pack_cap = 0;
+    float *d_dr = nullptr;        // cascaded heads: d loss / d r of S and M, (2, max_batch, 2)
+    size_t bn_floats = 0;         // BatchNorm statistics behind the gradient: kBnStatFloats (+ kCatStatFloats for cascaded heads)
     double *d_l2part = nullptr;   // l2_penalty_kernel: kL2Chunks partial sums per head, then its arrival ticket
     Segment *d_segs = nullptr;
     int dtype = 0;             // smh_trainer_set_dtype: 0 = exact-f32 matrix products, 1 = split-bf16 operands (f32 accumulators, f32 master weights)
@@ -1266,6 +1250,7 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_trainer_create: training is built for block_variant 0 (keras-tcn 2.3.x) only");
     smh_trainer *t = new smh_trainer();
     t->m = m, t->max_batch = max_batch;
+    t->bn_floats = kBnStatFloats + (m->heads == SMH_HEADS_CASCADED ? kCatStatFloats : 0);
     const Offsets off = offsets(m);
     std::vector<Segment> segs;
     int group = 0;
@@ -1297,7 +1282,16 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
         add(p, kHidden, 0, 0), p += kHidden;                 // beta
         add(p, kHidden, 2, h * 32), p += kHidden;            // moving_mean
         add(p, kHidden, 3, h * 32 + 16), p += kHidden;       // moving_variance
-        add(p, (size_t)kHidden * m->head_odim[h], 0, 0), p += (size_t)kHidden * m->head_odim[h];
+        const int cat = m->head_cat[h];
+        if (cat) {  // cascaded S / M: the concatenation BatchNorm
+            const int aux = kBnStatFloats + h * 2 * cat;
+            add(p, cat, 0, 0), p += cat;                     // gamma
+            add(p, cat, 0, 0), p += cat;                     // beta
+            add(p, cat, 2, aux), p += cat;                   // moving_mean
+            add(p, cat, 3, aux + cat), p += cat;             // moving_variance
+        }
+        const size_t hin = cat ? cat : kHidden;
+        add(p, hin * m->head_odim[h], 0, 0), p += hin * m->head_odim[h];
         add(p, m->head_odim[h], 0, 0);
     }
     t->nseg = (int)segs.size();
@@ -1307,7 +1301,8 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_dpre, (size_t)max_batch * kPS * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_dxh, ((size_t)max_batch * kPS + 4) * sizeof(float));  // + the heads kernel's ticket
     if (e == hipSuccess) e = hipMemset(t->d_dxh + (size_t)max_batch * kPS, 0, 4 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&t->d_grad, (m->n_params + kMaxHeads * 32) * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&t->d_grad, (m->n_params + t->bn_floats) * sizeof(float));
+    if (e == hipSuccess && m->heads == SMH_HEADS_CASCADED) e = hipMalloc((void **)&t->d_dr, (size_t)4 * max_batch * sizeof(float));
     if (e == hipSuccess) t->d_bnstat = t->d_grad + m->n_params;
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_vel, m->n_params * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_s2, m->n_params * sizeof(float));
@@ -1320,7 +1315,7 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
     if (e == hipSuccess) e = hipMemcpy(t->d_segs, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(t->d_vel, 0, m->n_params * sizeof(float));
     if (e == hipSuccess) e = hipMemset(t->d_s2, 0, m->n_params * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(t->d_grad, 0, (m->n_params + kMaxHeads * 32) * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(t->d_grad, 0, (m->n_params + t->bn_floats) * sizeof(float));
     if (e != hipSuccess) {
         smh_trainer_destroy(t);
         return smh::set_error(SMH_E_HIP, "smh_trainer_create: device allocation failed: %s", hipGetErrorString(e));
@@ -1338,6 +1333,7 @@ extern "C" void smh_trainer_destroy(smh_trainer *t) {
     (void)hipFree(t->d_gq);
     (void)hipFree(t->d_bwd_pack);
     (void)hipFree(t->d_gt);
+    (void)hipFree(t->d_dr);
     delete t;
 }
 
@@ -1368,6 +1364,8 @@ extern "C" int smh_trainer_set_deterministic(smh_trainer *t, int on, void *strea
 extern "C" int smh_trainer_set_dtype(smh_trainer *t, int dtype) {
     SMH_REQUIRE(t, "smh_trainer_set_dtype: null trainer");
     SMH_REQUIRE(dtype == 0 || dtype == 1, "smh_trainer_set_dtype: dtype must be 0 (f32) or 1 (split bf16 operands)");
+    SMH_REQUIRE(dtype == 0 || t->m->heads == SMH_HEADS_MTL,
+                "smh_trainer_set_dtype: the split-bf16 training step has the B3_MTL heads only; a cascaded model trains in f32 (dtype 0)");
     t->dtype = dtype;
     return SMH_OK;
 }
@@ -1401,12 +1399,16 @@ extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float 
     ha.goff_c3b = off.c3_b;
     ha.ext_losses = 1;
     size_t hpo = 0;
-    for (int i = 0; i < m->n_heads; ++i) {  // d_hp: per head [gamma, beta, mean, var, out kernel, out bias], packed
+    for (int i = 0; i < m->n_heads; ++i) {  // d_hp: per head [gamma, beta, mean, var, (cat BN,) out kernel, out bias], packed
         ha.hp_off[i] = hpo;
-        hpo += 4 * kHidden + (size_t)kHidden * m->head_odim[i] + m->head_odim[i];
+        hpo += head_tail_floats(m, i);
     }
-    rc = launch_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bnstat, d_losses,
-                            reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
+    if (m->heads == SMH_HEADS_CASCADED)
+        rc = launch_cascade_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_dr, t->d_grad,
+                                        t->d_bnstat, d_losses, st);
+    else
+        rc = launch_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bnstat, d_losses,
+                                reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
     if (rc) return rc;
     BwdArgs ba;
     ba.gq = t->d_gq;  // nullptr unless smh_trainer_set_deterministic(t, 1)
@@ -1481,7 +1483,7 @@ extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float 
     return rc ? rc : det_finalize(t, st);
 }
 
-extern "C" size_t smh_trainer_bucket_floats(const smh_trainer *t) { return t ? t->m->n_params + kMaxHeads * 32 : 0; }
+extern "C" size_t smh_trainer_bucket_floats(const smh_trainer *t) { return t ? t->m->n_params + t->bn_floats : 0; }
 
 extern "C" int smh_trainer_copy_state(smh_trainer *dst, const smh_trainer *src, void *stream) {
     SMH_REQUIRE(dst && src && dst->m == src->m, "smh_trainer_copy_state: both trainers must belong to the same model");

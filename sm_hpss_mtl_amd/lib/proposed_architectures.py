@@ -1,4 +1,5 @@
-"""Counterpart of lib/proposed_architectures.py for the hot path: `get_Lemaire_MTL_model` (B3_MTL).
+"""Counterpart of lib/proposed_architectures.py for the hot path: `get_Lemaire_MTL_model` (B3_MTL) and
+`get_Lemaire_Cascaded_MTL_model` (the same TCN with cascaded heads).
 
 Same signature and return value as the reference (proposed_architectures.py:85-91,170): a model object
 with the Keras-style surface the drivers use, and the initial learning rate 0.002.  The 5-class variant
@@ -8,7 +9,7 @@ Papakostas / Jang, row a13) are inference models (`sm_hpss_mtl_amd.cnn_models.Cn
 from __future__ import annotations
 
 from ..cnn_models import CnnMTL
-from ..model import B3MTL
+from ..model import B3MTL, CascadedMTL
 
 
 def get_Lemaire_MTL_model(TR_STEPS, N_MELS=120, n_classes=3, patch_size=68, loss_weights=None, seed=None, tcn_block="2.3"):
@@ -16,6 +17,16 @@ def get_Lemaire_MTL_model(TR_STEPS, N_MELS=120, n_classes=3, patch_size=68, loss
     the reference's positional call at :144 binds under) or "2.8" (two-convolution block, inference only)."""
     model = B3MTL(n_feat=N_MELS, patch_size=patch_size, n_classes=n_classes, TR_STEPS=TR_STEPS,
                   loss_weights=loss_weights, seed=seed, tcn_block=tcn_block)
+    return model, model.initial_learning_rate
+
+
+def get_Lemaire_Cascaded_MTL_model(TR_STEPS, N_MELS=120, n_classes=3, patch_size=68, seed=None, tcn_block="2.3"):
+    """proposed_architectures.py:238-323 -> (model, 0.002): heads of cascade_MTL_modifications (:175-234) -- S and M read a
+    BatchNorm of concat[their Dropout(16), R's output] -- compiled with bce / bce / mse / cce, no loss_weights, l2(0.01) on the
+    Dense(16) kernels, SGD(momentum 0.9, clipnorm 1) on ExponentialDecay(0.002, 3 * TR_STEPS, 0.1).  tcn_block as for
+    get_Lemaire_MTL_model ("2.8": inference only)."""
+    model = CascadedMTL(n_feat=N_MELS, patch_size=patch_size, n_classes=n_classes, TR_STEPS=TR_STEPS, seed=seed,
+                        tcn_block=tcn_block)
     return model, model.initial_learning_rate
 
 

@@ -8,6 +8,8 @@ Weights are kept on the host as float32 numpy arrays in CANONICAL order (Keras a
   3C kernel (T*32, n_classes), bias
   per head (S, M, [N,] R): dense kernel (T*32,16), bias, BN gamma, beta, moving_mean, moving_variance,
                            out kernel (16, odim), out bias
+  (CascadedMTL: heads S, M, R; S and M carry cat_bn gamma, beta, moving_mean, moving_variance (18 each) between their
+   moving_variance and an out kernel of shape (18, 1))
 and uploaded (re-packed into MFMA operand order by libsmh) whenever they change.
 """
 from __future__ import annotations
@@ -24,17 +26,24 @@ from .persistence import ModelSurfaceMixin
 from .training import TrainingMixin
 
 
-def head_spec(n_classes: int):
+HEADS_MTL, HEADS_CASCADED = 0, 1  # include/smh.h: SMH_HEADS_MTL / SMH_HEADS_CASCADED
+CAT = 18  # cascaded heads: width of concat[Dropout(16) of S or M, R's two outputs]
+
+
+def head_spec(n_classes: int, heads: int = HEADS_MTL):
     """(name, out_dim, activation) of the auxiliary heads in Keras output order
-    (proposed_architectures.py:25-80,154; 5_class_classification.py:150-215,286)."""
-    if n_classes == 5:
+    (proposed_architectures.py:25-80,154; 5_class_classification.py:150-215,286).  The cascaded model
+    (cascade_MTL_modifications, :175-234) has S, M, R[2] whatever n_classes is."""
+    if n_classes == 5 and heads == HEADS_MTL:
         return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("N", 1, "sigmoid"), ("R", 3, "linear")]
     return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("R", 2, "linear")]
 
 
-def weight_spec(n_feat, patch_size, n_classes, nb_filters=32, kernel_size=3, nb_stacks=3, n_dil=8, block_variant=0):
+def weight_spec(n_feat, patch_size, n_classes, nb_filters=32, kernel_size=3, nb_stacks=3, n_dil=8, block_variant=0,
+                heads=HEADS_MTL):
     """Ordered (name, shape, fan_in, fan_out|None) in canonical order; fan_out None -> not glorot.
-    block_variant 0: the keras-tcn 2.3.x block; 1: the two-convolution block of keras-tcn >= 2.8 (include/smh.h)."""
+    block_variant 0: the keras-tcn 2.3.x block; 1: the two-convolution block of keras-tcn >= 2.8 (include/smh.h).
+    heads HEADS_CASCADED: S and M carry the concatenation BatchNorm 'cat_bn' (18) and an out kernel (18, 1)."""
     Cf, D = nb_filters, patch_size * nb_filters
     spec = []
     if block_variant == 0:
@@ -54,16 +63,21 @@ def weight_spec(n_feat, patch_size, n_classes, nb_filters=32, kernel_size=3, nb_
                     spec += [(p + "/matching/kernel", (1, cin, Cf), cin, Cf), (p + "/matching/bias", (Cf,), 0, None)]
                 cin = Cf
     spec += [("3C/kernel", (D, n_classes), D, n_classes), ("3C/bias", (n_classes,), 0, None)]
-    for name, odim, _ in head_spec(n_classes):
+    for name, odim, _ in head_spec(n_classes, heads):
         spec += [(name + "/dense/kernel", (D, 16), D, 16), (name + "/dense/bias", (16,), 0, None),
                  (name + "/bn/gamma", (16,), 1, None), (name + "/bn/beta", (16,), 0, None),
-                 (name + "/bn/moving_mean", (16,), 0, None), (name + "/bn/moving_variance", (16,), 1, None),
-                 (name + "/out/kernel", (16, odim), 16, odim), (name + "/out/bias", (odim,), 0, None)]
+                 (name + "/bn/moving_mean", (16,), 0, None), (name + "/bn/moving_variance", (16,), 1, None)]
+        hin = 16
+        if heads == HEADS_CASCADED and name != "R":
+            hin = CAT
+            spec += [(name + "/cat_bn/gamma", (CAT,), 1, None), (name + "/cat_bn/beta", (CAT,), 0, None),
+                     (name + "/cat_bn/moving_mean", (CAT,), 0, None), (name + "/cat_bn/moving_variance", (CAT,), 1, None)]
+        spec += [(name + "/out/kernel", (hin, odim), hin, odim), (name + "/out/bias", (odim,), 0, None)]
     return spec
 
 
 def initial_weights(n_feat=240, patch_size=68, n_classes=3, seed=None, nb_filters=32, kernel_size=3, nb_stacks=3,
-                    n_dilations=8, block_variant=0):
+                    n_dilations=8, block_variant=0, heads=HEADS_MTL):
     """(dropout_rate, OrderedDict name -> float32 array) of a freshly built model: Keras defaults (glorot_uniform
     kernels, zero biases, BatchNormalization gamma = moving_variance = 1) and the build-time draw of the spatial
     dropout rate (proposed_architectures.py:136).  Host-only (numpy): `B3MTL.__init__` and the generator of
@@ -72,7 +86,7 @@ def initial_weights(n_feat=240, patch_size=68, n_classes=3, seed=None, nb_filter
     dropout_rate = float(rng.uniform(0.05, 0.5))
     weights = OrderedDict()
     for name, shape, fan_in, fan_out in weight_spec(n_feat, patch_size, n_classes, nb_filters, kernel_size, nb_stacks,
-                                                    n_dilations, block_variant):
+                                                    n_dilations, block_variant, heads):
         if fan_out is not None:
             lim = np.sqrt(6.0 / (fan_in + fan_out))
             weights[name] = rng.uniform(-lim, lim, size=shape).astype(np.float32)
@@ -83,6 +97,9 @@ def initial_weights(n_feat=240, patch_size=68, n_classes=3, seed=None, nb_filter
 
 class B3MTL(TrainingMixin, ModelSurfaceMixin):
     """`model` object of get_Lemaire_MTL_model.  Inference runs entirely in libsmh (HIP)."""
+
+    HEADS = HEADS_MTL
+    CLASS_NAME = "B3_MTL"
 
     def __init__(self, n_feat=240, patch_size=68, n_classes=3, TR_STEPS=1, loss_weights=None, seed=None,
                  nb_filters=32, kernel_size=3, nb_stacks=3, n_dilations=8, tcn_block="2.3"):
@@ -98,16 +115,19 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
         self.TR_STEPS, self.loss_weights = TR_STEPS, loss_weights
         # proposed_architectures.py:136 draws the (training-only) spatial dropout rate at build time
         self.dropout_rate, self.weights = initial_weights(self.n_feat, self.patch_size, self.n_classes, seed, nb_filters,
-                                                          kernel_size, nb_stacks, n_dilations, self.block_variant)
+                                                          kernel_size, nb_stacks, n_dilations, self.block_variant, self.HEADS)
         self.initial_learning_rate = 0.002
         cfg = _lib.ModelCfg(self.n_feat, self.patch_size, self.n_classes, nb_filters, kernel_size, nb_stacks, n_dilations,
                             self.block_variant)
         h = C.c_void_p()
-        _lib.check(self.lib.smh_model_create(C.byref(cfg), C.byref(h)), "smh_model_create")
+        if self.HEADS == HEADS_MTL:
+            _lib.check(self.lib.smh_model_create(C.byref(cfg), C.byref(h)), "smh_model_create")
+        else:
+            _lib.check(self.lib.smh_model_create_heads(C.byref(cfg), self.HEADS, C.byref(h)), "smh_model_create_heads")
         self._h = h
         self.out_dim = self.lib.smh_model_out_dim(self._h)
         self._spec = weight_spec(self.n_feat, self.patch_size, self.n_classes, nb_filters, kernel_size, nb_stacks, n_dilations,
-                                 self.block_variant)
+                                 self.block_variant, self.HEADS)
         assert self.count_params() == self.lib.smh_model_num_params(self._h)
         self._dirty = True          # host copy newer than the device master
         self._device_newer = False  # device master newer than the host copy (after optimiser steps)
@@ -126,7 +146,7 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
     # ---- Keras-style surface -----------------------------------------------------------------
     @property
     def output_names(self):
-        return [n for n, _, _ in head_spec(self.n_classes)] + ["3C"]
+        return [n for n, _, _ in head_spec(self.n_classes, self.HEADS)] + ["3C"]
 
     @property
     def metrics_names(self):
@@ -186,14 +206,15 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
         self.set_weights_dict(load_weights_file(path, arch_json=arch_json))
 
     def to_json(self):
-        return json.dumps({"class_name": "B3_MTL", "config": {
+        return json.dumps({"class_name": self.CLASS_NAME, "config": {
             "n_feat": self.n_feat, "patch_size": self.patch_size, "n_classes": self.n_classes,
             "nb_filters": self.nb_filters, "kernel_size": self.kernel_size, "nb_stacks": self.nb_stacks,
             "n_dilations": self.n_dilations, "dropout_rate": self.dropout_rate, "outputs": self.output_names,
             "tcn_block": self.tcn_block}})
 
     def summary(self, print_fn=print):
-        print_fn("Model: B3_MTL (Lemaire et al. TCN + MTL heads), input (None, %d, %d)" % (self.patch_size, self.n_feat))
+        print_fn("Model: %s (Lemaire et al. TCN + %s heads), input (None, %d, %d)"
+                 % (self.CLASS_NAME, "cascaded MTL" if self.HEADS == HEADS_CASCADED else "MTL", self.patch_size, self.n_feat))
         for name, shape, _, _ in self._spec:
             print_fn("  %-40s %-18s %d" % (name, str(tuple(shape)), int(np.prod(shape))))
         print_fn("Total params: %d" % self.count_params())
@@ -303,7 +324,7 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
     def split_outputs(self, out):
         """(N, out_dim) -> list in Keras output order [S, M, (N,) R, 3C]."""
         res, col = [], 0
-        for _, odim, _ in head_spec(self.n_classes):
+        for _, odim, _ in head_spec(self.n_classes, self.HEADS):
             res.append(out[:, col:col + odim])
             col += odim
         res.append(out[:, col:col + self.n_classes])
@@ -325,3 +346,14 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
         that its outputs are not results (include/smh.h: smh_model_status).  `forward_device` / `forward_from_x0` only enqueue
         work; callers that keep results on the device call this before trusting them (`predict` and bench.py do)."""
         _lib.check(self.lib.smh_model_status(self._h, _lib.current_stream()), "smh_model_status")
+
+
+class CascadedMTL(B3MTL):
+    """`model` object of get_Lemaire_Cascaded_MTL_model (lib/proposed_architectures.py:175-323): the B3_MTL trunk, '3C' and
+    Dense(16) layers, with cascaded heads -- R = Dense(2)(Dropout(relu(BN(Dense16)))), S and M =
+    sigmoid(Dense(1)(BN(concat[Dropout(relu(BN(Dense16))), R]))).  Outputs [S, M, R, 3C] like B3_MTL; n_classes widens '3C'
+    only.  The same surface as B3MTL (predict / compile / fit / evaluate / persistence); the bf16 paths (forward dtype "bf16",
+    train_dtype "bf16") and the single-head sub-model are B3_MTL only."""
+
+    HEADS = HEADS_CASCADED
+    CLASS_NAME = "B3_MTL_Cascaded"

@@ -71,8 +71,13 @@ def keras_layers_to_canonical(layers, arch=None):
     pair feeds which head is read off the architecture JSON (inbound_nodes: out Dense <- Dropout <- Activation <-
     BatchNormalization <- Dense(16) <- Flatten).  Without the JSON the heads' hidden layers are assigned in creation order
     (S, M, [N,] R -- the order MTL_modifications builds them in); the dead first 'x_mu' / 'x_smr' blocks (:55-58, :68-71)
-    are not part of the saved graph."""
-    convs, dense16, bns, named = [], [], [], {}
+    are not part of the saved graph.
+
+    The cascaded model (get_Lemaire_Cascaded_MTL_model, :175-323) is recognised by its 18-wide BatchNormalization layers: S and
+    M are traced as out Dense <- BatchNormalization(18) ('cat_bn') <- Concatenate <- [Dropout <- ... <- Dense(16), R].  Without
+    the JSON its layers are taken in the creation order of cascade_MTL_modifications: Dense(16) R, S, M; BatchNormalization R,
+    S, S's concatenation, M, M's concatenation."""
+    convs, dense16, bns, cat_bns, named = [], [], [], [], {}
     for lname, ws in layers.items():
         arrs = list(ws.values())
         if not arrs:
@@ -85,6 +90,8 @@ def keras_layers_to_canonical(layers, arch=None):
             dense16.append((lname, arrs))
         elif len(arrs) == 4 and all(a.shape == (16,) for a in arrs):
             bns.append((lname, arrs))
+        elif len(arrs) == 4 and all(a.shape == (18,) for a in arrs):
+            cat_bns.append((lname, arrs))
         else:
             raise ValueError("keras weight file: layer %r with shapes %s does not belong to a B3_MTL graph" % (lname, [a.shape for a in arrs]))
     if "3C" not in named or len(convs) < 3 or (len(convs) - 1) % 2:
@@ -104,6 +111,10 @@ def keras_layers_to_canonical(layers, arch=None):
         out[p + "/conv/kernel"], out[p + "/conv/bias"], out[p + "/conv1x1/kernel"], out[p + "/conv1x1/bias"] = k1, b1, k2, b2
     out["3C/kernel"], out["3C/bias"] = named["3C"]
     heads = [h for h in ("S", "M", "N", "R") if h in named]
+    cascaded = bool(cat_bns)
+    if cascaded and (heads != ["S", "M", "R"] or len(cat_bns) != 2):
+        raise ValueError("keras weight file: %d 18-wide BatchNormalization layers and heads %s: not the cascaded MTL graph"
+                         % (len(cat_bns), heads))
     if len(dense16) != len(heads) or len(bns) != len(heads):
         raise ValueError("keras weight file: %d heads but %d Dense(16) / %d BatchNormalization layers" % (len(heads), len(dense16), len(bns)))
     feeder = {}
@@ -120,29 +131,39 @@ def keras_layers_to_canonical(layers, arch=None):
         cls = {L["name"]: L["class_name"] for L in cfg_layers}
         for h in heads:
             cur, found = h, {}
-            for _ in range(8):  # walk up: Dense(out) <- Dropout <- Activation <- BatchNormalization <- Dense(16)
+            for _ in range(10):  # walk up: Dense(out) <- Dropout <- Activation <- BatchNormalization <- Dense(16)
                 ups = inbound.get(cur, [])
+                if cascaded and cls.get(cur) == "Concatenate":  # cascaded S / M: follow the branch that is not R's output
+                    ups = [u for u in ups if u != "R"]
                 if len(ups) != 1:
                     break
                 cur = ups[0]
-                if cls.get(cur) == "BatchNormalization":
+                if cls.get(cur) == "BatchNormalization" and cascaded and h != "R" and "cat_bn" not in found:
+                    found["cat_bn"] = cur
+                elif cls.get(cur) == "BatchNormalization":
                     found["bn"] = cur
                 elif cls.get(cur) == "Dense":
                     found["dense"] = cur
                     break
-            if "bn" not in found or "dense" not in found:
+            if "bn" not in found or "dense" not in found or (cascaded and h != "R" and "cat_bn" not in found):
                 raise ValueError("architecture JSON: cannot trace head %r back to its BatchNormalization / Dense(16)" % h)
-            feeder[h] = (found["dense"], found["bn"])
+            feeder[h] = (found["dense"], found["bn"], found.get("cat_bn"))
+    elif cascaded:  # creation order of cascade_MTL_modifications: R, S, M
+        for i, h in enumerate(("R", "S", "M")):
+            feeder[h] = (dense16[i][0], bns[i][0], None if h == "R" else cat_bns[i - 1][0])
     else:
         for i, h in enumerate(heads):  # creation order
-            feeder[h] = (dense16[i][0], bns[i][0])
-    d16, bnd = dict(dense16), dict(bns)
+            feeder[h] = (dense16[i][0], bns[i][0], None)
+    d16, bnd, catd = dict(dense16), dict(bns), dict(cat_bns)
     for h in heads:
-        dn, bn = feeder[h]
-        if dn not in d16 or bn not in bnd:
+        dn, bn, cbn = feeder[h]
+        if dn not in d16 or bn not in bnd or (cbn is not None and cbn not in catd):
             raise ValueError("architecture JSON names layers %r / %r that the weight file does not hold" % (dn, bn))
         out[h + "/dense/kernel"], out[h + "/dense/bias"] = d16[dn]
         out[h + "/bn/gamma"], out[h + "/bn/beta"], out[h + "/bn/moving_mean"], out[h + "/bn/moving_variance"] = bnd[bn]
+        if cbn is not None:
+            (out[h + "/cat_bn/gamma"], out[h + "/cat_bn/beta"], out[h + "/cat_bn/moving_mean"],
+             out[h + "/cat_bn/moving_variance"]) = catd[cbn]
         out[h + "/out/kernel"], out[h + "/out/bias"] = named[h]
     return out
 
@@ -162,17 +183,19 @@ def model_from_json(text, seed=None):
         n_conv = sum(1 for l in cfg["layers"] if l["class_name"] == "Conv1D")
         if (n_conv - 1) % 16:
             raise ValueError("model_from_json: %d Conv1D layers: not 1 + 2 x (stacks x 8 dilations)" % n_conv)
-        from .model import B3MTL
-        m = B3MTL(n_feat=int(shp[2]), patch_size=int(shp[1]), n_classes=int(L["3C"]["config"]["units"]), seed=seed,
-                  nb_stacks=(n_conv - 1) // 16)
+        from .model import B3MTL, CascadedMTL
+        cls = CascadedMTL if any(l["class_name"] == "Concatenate" for l in cfg["layers"]) else B3MTL
+        m = cls(n_feat=int(shp[2]), patch_size=int(shp[1]), n_classes=int(L["3C"]["config"]["units"]), seed=seed,
+                nb_stacks=(n_conv - 1) // 16)
         rates = [l["config"]["rate"] for l in cfg["layers"] if l["class_name"] == "SpatialDropout1D"]
         if rates:
             m.dropout_rate = float(rates[0])
         return m
-    if name == "B3_MTL":
-        from .model import B3MTL
-        m = B3MTL(n_feat=cfg["n_feat"], patch_size=cfg["patch_size"], n_classes=cfg["n_classes"], seed=seed,
-                  **{k: cfg[k] for k in ("nb_filters", "kernel_size", "nb_stacks", "n_dilations", "tcn_block") if k in cfg})
+    if name in ("B3_MTL", "B3_MTL_Cascaded"):
+        from .model import B3MTL, CascadedMTL
+        cls = CascadedMTL if name == "B3_MTL_Cascaded" else B3MTL
+        m = cls(n_feat=cfg["n_feat"], patch_size=cfg["patch_size"], n_classes=cfg["n_classes"], seed=seed,
+                **{k: cfg[k] for k in ("nb_filters", "kernel_size", "nb_stacks", "n_dilations", "tcn_block") if k in cfg})
         if "dropout_rate" in cfg:  # drawn at build time by the reference (proposed_architectures.py:136): part of the architecture
             m.dropout_rate = float(cfg["dropout_rate"])
         return m
@@ -211,6 +234,9 @@ class HeadModel:
 
     def __init__(self, model, name):
         from . import optimizers as _opt
+        if getattr(model, "HEADS", 0) != 0:
+            raise ValueError("Model(input, get_layer(%r).output): single-output sub-models are built for the B3_MTL heads only; "
+                             "the cascaded heads S / M depend on R" % (name,))
         self.model, self.name = model, name
         self._index = model.output_names.index(name)
         self.output_names = [name]

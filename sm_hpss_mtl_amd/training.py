@@ -184,7 +184,7 @@ class TrainingMixin:
 
     def _head_spec(self):
         from .model import head_spec
-        return head_spec(self.n_classes)
+        return head_spec(self.n_classes, getattr(self, "HEADS", 0))
 
     def _trainer_fn(self, i):
         return getattr(self.lib, self._TRAINER_API[i])
@@ -226,6 +226,8 @@ class TrainingMixin:
             raise ValueError("train_dtype must be 'f32' or 'bf16', got %r" % (dtype,))
         if dtype == "bf16" and self._TRAINER_API[0] != "smh_trainer_create":
             raise ValueError("train_dtype='bf16' exists for the B3_MTL trainer only")
+        if dtype == "bf16" and getattr(self, "HEADS", 0) != 0:
+            raise ValueError("train_dtype='bf16' exists for the B3_MTL heads only; the cascaded model trains in f32")
         self._train_dtype = dtype
         self._apply_train_dtype()
 
