@@ -438,8 +438,11 @@ int smh_trainer_set_deterministic(smh_trainer *t, int on, void *stream);
  * optimiser stay f32.  The forward's outputs are within 1e-4 of the f32 forward's; the backward agrees with the f32 backward on the same
  * forward to 2e-4 (relative L2 per tensor); against the float64 oracle the gradients sit where the forward's 1e-5 puts the relu /
  * channel-maximum gates (2-3e-2 of a tensor's norm).  Patches longer than 128 frames keep the f32 backward.
- * A cascaded model (SMH_HEADS_CASCADED) accepts dtype 0 only. */
+ * A cascaded model (SMH_HEADS_CASCADED) accepts dtype 0 only, and so does a model the split-bf16 forward cannot run (n_feat > 256,
+ * block_variant 1): dtype 1 is refused here, not at the first step. */
 int smh_trainer_set_dtype(smh_trainer *t, int dtype);
+/* The checks of smh_trainer_set_dtype on a model that has no trainer yet: SMH_OK, or SMH_E_INVALID + smh_last_error. */
+int smh_model_check_train_dtype(const smh_model *m, int dtype);
 /* General optimiser step.  optimizer 0 = SGD (beta1 = momentum; what smh_trainer_apply_sgd_f32 calls), 1 = Adam,
  * 2 = Nadam as tf.keras 2.x implements it (momentum schedule u_t = beta1 (1 - 0.5 * 0.96^(0.004 t)); the optimiser of the
  * single-head fine-tuning in DAFx12_Speech_Music_Detection_B3_MTL_v2.py:524-526).  active_mask selects the tensors that

@@ -483,6 +483,8 @@ b3mtl_forward_kernel(TcnArgs a, const float *__restrict__ X, const float *__rest
                 const float *xr = X + ((size_t)n0 * T + Rc) * a.F + (size_t)q * a.FQ;
                 f32x4 c0 = bl, c1 = bh;
                 for (int s = 0; s < a.FQ; ++s) {
+                    // (lanes past the row's last feature load nothing: on gfx950 the load is exec-masked by this test, not a
+                    // load + select -- tests/test_model_shapes_gpu.py keeps NaN behind the last row of the batch)
                     const float xv = (q * a.FQ + s < a.F) ? xr[s] : 0.f;
                     c0 = mfma4(w0s[(s * 2 + 0) * 64 + lane], xv, c0);
                     c1 = mfma4(w0s[(s * 2 + 1) * 64 + lane], xv, c1);
@@ -1174,6 +1176,16 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     *plds = lds_x + (a.wlds ? lds_w + lds_xch : 0);
 }
 
+// whether the forward of `a` with `units` column tiles per workgroup runs the skewed task schedule (else the barrier schedule)
+static bool skew_schedule(const TcnArgs &a, int units) {
+    const bool skew_ok = a.wlds && units <= 32 && units >= 1 && a.n_blocks * units < 2048 && a.T >= 16;  // (T >= 16: issue_ops)
+    // (13 tiles: since the lone last-round tile is shared by two waves the barrier schedule is ahead there -- W = 68 x 768 patches
+    // 130.1 against 131.5 us, W = 99 x 510 131.5 / 134.7; at 17 tiles the skew schedule stays ahead, 149.8 / 157.5)
+    bool skew = skew_ok && units >= 12 && 8 * ((units + 7) / 8) - units >= 3 && units != 13;
+    if (const char *ev = getenv("SMH_TCN_SKEW")) skew = atoi(ev) == 2 ? skew_ok : (skew && atoi(ev) != 0);
+    return skew;
+}
+
 int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
                    hipStream_t st, int from_x0, int x0_shift, int x0_T) {
     TcnArgs a;
@@ -1208,11 +1220,7 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
     // full rounds of the 8 waves: 162 / 154).  SMH_TCN_SKEW=0 / 2: never / whenever it can run (tests, tuning).
     // (the schedule decodes task n into (block, tile) by multiplication, exact for n < 2048: smh_model_create accepts up to
     // nb_stacks x 16 dilations, the reference tunes nb_stacks up to 10 -- beyond the bound the barrier schedule runs)
-    const bool skew_ok = a.wlds && units <= 32 && units >= 1 && a.n_blocks * units < 2048 && a.T >= 16;  // (T >= 16: issue_ops)
-    // (13 tiles: since the lone last-round tile is shared by two waves the barrier schedule is ahead there -- W = 68 x 768 patches
-    // 130.1 against 131.5 us, W = 99 x 510 131.5 / 134.7; at 17 tiles the skew schedule stays ahead, 149.8 / 157.5)
-    bool skew = skew_ok && units >= 12 && 8 * ((units + 7) / 8) - units >= 3 && units != 13;
-    if (const char *ev = getenv("SMH_TCN_SKEW")) skew = atoi(ev) == 2 ? skew_ok : (skew && atoi(ev) != 0);
+    const bool skew = skew_schedule(a, units);
     if (skew && !getenv("SMH_TCN_WAVES")) nwaves = 8;
     if (skew) nwaves = std::min(nwaves, 8);
     // The 16-wave form of the skew schedule (weights in an LDS ring, four waves per SIMD): inference, when its ring fits beside
@@ -1261,6 +1269,17 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
 }
 
 }  // namespace smh_tcn
+
+// tests: 1 when smh_model_forward_f32 of N patches takes the skewed block schedule, 0 when the barrier schedule (under the
+// current SMH_TCN_SKEW), -1 when that forward would be refused
+extern "C" int smh_internal_tcn_schedule(const smh_model *m, int N) {
+    if (!m || N < 1 || m->cfg.block_variant != 0) return -1;
+    TcnArgs a;
+    size_t lds;
+    fill_args(m, N, &a, &lds);
+    if (lds > 156 * 1024) return -1;
+    return smh_tcn::skew_schedule(a, (std::min(a.G, N) * a.T + 15) / 16) ? 1 : 0;
+}
 
 extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
     return smh_model_create_heads(cfg, SMH_HEADS_MTL, out);

@@ -907,48 +907,78 @@ b3mtl_forward_bf16s_kernel(TcnArgs a, PackInfo pi, Offsets off, const float *__r
 
 }  // namespace
 
-static int forward_bf16(smh_model *m, const float *d_x, int N, float *d_out, int split, int from_x0, void *stream,
-                        const TrainIO *tio = nullptr) {
-    SMH_REQUIRE(m && d_x && (d_out || tio), "smh_model_forward_bf16: null argument");
-    SMH_REQUIRE(!tio || split, "smh_model_forward_bf16: the training forward exists for split operands only");
-    SMH_REQUIRE(N >= 0, "smh_model_forward_bf16: N=%d", N);
+// launch geometry of the split-operand kernel (its wave count and LDS) at a batch of N
+struct SplitPlan {
+    bool two;
+    int nwaves;
+    size_t lds;
+};
+
+// the refusals of forward_bf16 that depend on the model alone
+static int model_bf16_ok(const smh_model *m) {
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_model_forward_bf16: built for block_variant 0 only");
     SMH_REQUIRE(m->heads == SMH_HEADS_MTL, "smh_model_forward_bf16: the bf16 forward has the B3_MTL heads only, not the cascaded "
                 "heads of this model (use smh_model_forward_f32)");
     SMH_REQUIRE(m->cfg.n_feat <= 256, "smh_model_forward_bf16: n_feat=%d exceeds the 256 features of the bf16 layer-0 tiling",
                 m->cfg.n_feat);
+    return SMH_OK;
+}
+
+// The refusals of forward_bf16 that depend on the batch size (after model_bf16_ok), and the kernels' launch arguments and LDS
+// plan at N >= 1 patches.
+static int plan_bf16(const smh_model *m, const PackInfo &pi, int N, int split, int from_x0, TcnArgs *pa, size_t *plds,
+                     SplitPlan *sp) {
+    TcnArgs &a = *pa;
+    fill_args(m, N, &a, plds);
+    a.from_x0 = from_x0;
+    SMH_REQUIRE(*plds <= 156 * 1024, "patch_size %d too long for the LDS-resident TCN", a.T);
+    if (!split) return SMH_OK;
+    const int units_s = (std::min(a.G, N) * a.T + 15) / 16;
+    const bool two = units_s <= 24;  // at most two column tiles per wave on up to 12 waves
+    int nwaves_s = two ? std::min(12, std::max(8, (units_s + 1) / 2)) : 8;
+    if (const char *ev = getenv("SMH_BF16_NW")) nwaves_s = two ? std::min(12, std::max((units_s + 1) / 2, atoi(ev))) : 8;  // tuning
+    // residual image + four split images (hi / lo of two buffers, a zero row each)
+    SMH_REQUIRE(a.n_mt <= 5, "smh_model_forward_bf16: more than five M-tiles of Dense-on-trunk outputs");
+    const size_t lds_s = 4 * (size_t)(a.GRP + 1) * kRS * sizeof(__bf16) + 2 * 2 * kSlotOps * 16 + sizeof(float) * (size_t)nwaves_s * a.G * kPS;
+    SMH_REQUIRE((units_s + nwaves_s - 1) / nwaves_s <= (two ? 2 : 4), "smh_model_forward_bf16: too many column tiles per wave");
+    SMH_REQUIRE(lds_s <= 156 * 1024, "patch_size %d too long for the LDS-resident split-bf16 TCN", a.T);
+    SMH_REQUIRE((size_t)pi.steps0 * 2 * 64 * 2 * 16 <= 2 * (size_t)(a.GRP + 1) * kRS * sizeof(__bf16) || from_x0,
+                "smh_model_forward_bf16: n_feat=%d too wide for the layer-0 operand staging", m->cfg.n_feat);
+    *sp = SplitPlan{two, nwaves_s, lds_s};
+    return SMH_OK;
+}
+
+static int forward_bf16(smh_model *m, const float *d_x, int N, float *d_out, int split, int from_x0, void *stream,
+                        const TrainIO *tio = nullptr) {
+    SMH_REQUIRE(m && d_x && (d_out || tio), "smh_model_forward_bf16: null argument");
+    SMH_REQUIRE(!tio || split, "smh_model_forward_bf16: the training forward exists for split operands only");
+    SMH_REQUIRE(N >= 0, "smh_model_forward_bf16: N=%d", N);
+    int rc = model_bf16_ok(m);
+    if (rc) return rc;
     if (N == 0) return SMH_OK;
-    hipStream_t st = (hipStream_t)stream;
     const PackInfo pi = pack_info(m);
+    TcnArgs a;
+    size_t lds;
+    SplitPlan sp{};
+    rc = plan_bf16(m, pi, N, split, from_x0, &a, &lds, &sp);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
     const Offsets off = offsets(m);
     if (!m->d_bf16) SMH_CHECK_HIP(hipMalloc(&m->d_bf16, 2 * pi.total * 16));  // hi operands, then lo operands
     if (m->bf16_version != m->version) {  // weights changed since the operands were built
         hipLaunchKernelGGL(pack_bf16_kernel, dim3((unsigned)((pi.total + 255) / 256)), dim3(256), 0, st, m->d_flat, off, pi,
                            m->cfg.n_feat, m->cfg.patch_size, m->n_blocks, m->cfg.n_classes, m->n_heads, m->NH,
                            (bf16x8 *)m->d_bf16);
-        int rc = smh::launch_status("pack_bf16_kernel");
+        rc = smh::launch_status("pack_bf16_kernel");
         if (rc) return rc;
         m->bf16_version = m->version;
     }
-    TcnArgs a;
-    size_t lds;
-    fill_args(m, N, &a, &lds);
-    a.from_x0 = from_x0;
     if (const char *ev = smh::probe_env("SMH_TCN_BLOCKS")) a.n_blocks = atoi(ev);  // timing probe (outputs invalid): fewer residual blocks
     if (const char *ev = smh::probe_env("SMH_TCN_TUNE")) a.tune = atoi(ev);  // timing probes: 1 = no tile work, 2 = no operand staging
-    SMH_REQUIRE(lds <= 156 * 1024, "patch_size %d too long for the LDS-resident TCN", a.T);
     if (split) {
-        const int units_s = (std::min(a.G, N) * a.T + 15) / 16;
-        const bool two = units_s <= 24;  // at most two column tiles per wave on up to 12 waves
-        int nwaves_s = two ? std::min(12, std::max(8, (units_s + 1) / 2)) : 8;
-        if (const char *ev = getenv("SMH_BF16_NW")) nwaves_s = two ? std::min(12, std::max((units_s + 1) / 2, atoi(ev))) : 8;  // tuning
-        // residual image + four split images (hi / lo of two buffers, a zero row each)
-        SMH_REQUIRE(a.n_mt <= 5, "smh_model_forward_bf16: more than five M-tiles of Dense-on-trunk outputs");
-        const size_t lds_s = 4 * (size_t)(a.GRP + 1) * kRS * sizeof(__bf16) + 2 * 2 * kSlotOps * 16 + sizeof(float) * (size_t)nwaves_s * a.G * kPS;
-        SMH_REQUIRE((units_s + nwaves_s - 1) / nwaves_s <= (two ? 2 : 4), "smh_model_forward_bf16: too many column tiles per wave");
-        SMH_REQUIRE(lds_s <= 156 * 1024, "patch_size %d too long for the LDS-resident split-bf16 TCN", a.T);
-        SMH_REQUIRE((size_t)pi.steps0 * 2 * 64 * 2 * 16 <= 2 * (size_t)(a.GRP + 1) * kRS * sizeof(__bf16) || from_x0,
-                    "smh_model_forward_bf16: n_feat=%d too wide for the layer-0 operand staging", m->cfg.n_feat);
+        const bool two = sp.two;
+        const int nwaves_s = sp.nwaves;
+        const size_t lds_s = sp.lds;
         const TrainIO io = tio ? *tio : TrainIO{nullptr, nullptr, nullptr, nullptr, 0};
 #define SMH_LAUNCH_BF16S(MT, TR)                                                                                                       \
     do {                                                                                                                              \
@@ -975,6 +1005,19 @@ static int forward_bf16(smh_model *m, const float *d_x, int N, float *d_out, int
 }
 
 namespace smh_tcn {
+// SMH_OK when the split-bf16 training forward can run this model, else its refusal: block_variant 1, cascaded heads, n_feat > 256,
+// and the plan of a one-patch batch -- a patch too long for the LDS plan, or layer-0 operand staging too wide (the staging room
+// grows with the patches per workgroup, so one patch is where that refusal bites first).  Batches large enough to put several
+// patches in a workgroup need more LDS for the same patch length; a model refused only there still fails at that step.
+int forward_bf16_supported(const smh_model *m) {
+    int rc = model_bf16_ok(m);
+    if (rc) return rc;
+    TcnArgs a;
+    size_t lds;
+    SplitPlan sp;
+    return plan_bf16(m, pack_info(m), 1, 1, 0, &a, &lds, &sp);
+}
+
 // the training-mode forward on split bf16 operands (smh_train_step_f32 when the trainer's dtype is bf16): same TrainIO as launch_forward
 int launch_forward_bf16_train(smh_model *m, const float *d_x, int N, const TrainIO *tio, hipStream_t st) {
     return forward_bf16(m, d_x, N, nullptr, 1, 0, (void *)st, tio);

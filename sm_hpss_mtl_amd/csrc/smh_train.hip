@@ -1361,11 +1361,19 @@ extern "C" int smh_trainer_set_deterministic(smh_trainer *t, int on, void *strea
     return SMH_OK;
 }
 
+extern "C" int smh_model_check_train_dtype(const smh_model *m, int dtype) {
+    SMH_REQUIRE(m, "smh_model_check_train_dtype: null model");
+    SMH_REQUIRE(dtype == 0 || dtype == 1, "smh_trainer_set_dtype: dtype must be 0 (f32) or 1 (split bf16 operands)");
+    SMH_REQUIRE(dtype == 0 || m->heads == SMH_HEADS_MTL,
+                "smh_trainer_set_dtype: the split-bf16 training step has the B3_MTL heads only; a cascaded model trains in f32 (dtype 0)");
+    // a model the split-bf16 forward refuses would otherwise fail only at its first training step
+    return dtype == 0 ? SMH_OK : forward_bf16_supported(m);
+}
+
 extern "C" int smh_trainer_set_dtype(smh_trainer *t, int dtype) {
     SMH_REQUIRE(t, "smh_trainer_set_dtype: null trainer");
-    SMH_REQUIRE(dtype == 0 || dtype == 1, "smh_trainer_set_dtype: dtype must be 0 (f32) or 1 (split bf16 operands)");
-    SMH_REQUIRE(dtype == 0 || t->m->heads == SMH_HEADS_MTL,
-                "smh_trainer_set_dtype: the split-bf16 training step has the B3_MTL heads only; a cascaded model trains in f32 (dtype 0)");
+    const int rc = smh_model_check_train_dtype(t->m, dtype);
+    if (rc) return rc;
     t->dtype = dtype;
     return SMH_OK;
 }

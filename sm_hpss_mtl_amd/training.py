@@ -228,6 +228,8 @@ class TrainingMixin:
             raise ValueError("train_dtype='bf16' exists for the B3_MTL trainer only")
         if dtype == "bf16" and getattr(self, "HEADS", 0) != 0:
             raise ValueError("train_dtype='bf16' exists for the B3_MTL heads only; the cascaded model trains in f32")
+        if dtype == "bf16":  # the trainer is created at the first step: refuse a model the bf16 forward cannot run now
+            _lib.check(self.lib.smh_model_check_train_dtype(self._h, 1), "train_dtype='bf16'")
         self._train_dtype = dtype
         self._apply_train_dtype()
 
