@@ -456,6 +456,14 @@ int smh_model_check_train_dtype(const smh_model *m, int dtype);
 int smh_trainer_apply_f32(smh_trainer *t, int optimizer, float lr, float beta1, float beta2, float eps, float clipnorm,
                           float grad_scale, unsigned active_mask, void *stream);
 
+/* ---- internal: for tests, not part of the stable interface ---------------------------------------------------------------- */
+/* The feature path smh_frontend_f32 (no taps) and smh_frontend_ragged_f32 take for a clip of T frames in this context, from the
+ * same decision the dispatch uses: 0 the LDS-image kernel for even T, 1 the LDS-image kernel for odd T (or with SMH_FEAT_NOPAIR),
+ * 2 the streaming kernels of the ragged front end (clips beyond the LDS image), 3 the two-kernel path over the whole clip
+ * (launch_hp_feat + launch_std_patch: window pairs without a block-split median kernel, clips too short for the tiled medians or
+ * too long for the streaming kernels' 32-bit offsets).  -1 for a null context or T < 1. */
+int smh_internal_frontend_route(const smh_ctx *ctx, int T);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ namespace {
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 }  // namespace
 
-namespace smh_rag {  // smh_ragged.hip: the streaming kernels that serve clips beyond the LDS image
+namespace smh_rag {  // smh_ragged.hip: the streaming kernels that serve clips beyond the LDS image (feature_route: smh_rag.h)
 size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T);
 int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, int W, int shift, int nP, float *d_fv,
               float *d_patches, void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st);
@@ -132,10 +132,12 @@ extern "C" int smh_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B,
     if (B == 0) return nP;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if (!d_S && !d_harm && !d_perc && !smh_features_blocked_ok(ctx, T, 0)) {
+    const int route = smh_rag::feature_route(ctx, T);
+    if (!d_S && !d_harm && !d_perc && route == 2) {
         // Clips beyond the LDS image (longer than ~1.6 s at 240 rows), no taps: the streaming kernels of the ragged front end, fed the
         // tables of B equal clips -- a file gets the same bits alone, in an equal-length batch and in a ragged one.  The STFT kernel is
-        // the one smh_stft_mag_f32 would pick for this batch.
+        // the one smh_stft_mag_f32 would pick for this batch: the generic one when a clip starts off an 8-byte boundary (odd n_samples
+        // and B > 1), whose S differs in the last bits from the specialised kernel's that a lone aligned clip gets.
         const bool aligned8 = ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0;
         rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, W, shift, nP, d_fv, nP > 0 ? d_patches : nullptr, d_work, work_bytes, aligned8, st);
         if (rc < 0) return rc;
@@ -146,9 +148,11 @@ extern "C" int smh_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B,
     // the harmonic median is written time-major (coalesced stores) unless the caller taps it
     // the harmonic median is written in the layout its consumer reads best unless the caller taps it:
     // 16-frame blocks for the single-kernel feature path, time-major otherwise
-    const int want = d_harm ? 0 : (smh_features_blocked_ok(ctx, T, 0) ? 2 : 1);
+    const int want = d_harm ? 0 : (route <= 1 ? 2 : 1);
     const int tm = smh_median::launch_hpss(S, B, ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc, harm, perc, want, st);
     if (tm < 0) return tm;
+    if (want == 2 && tm != 2)
+        return smh::set_error(SMH_E_INVALID, "smh_frontend_f32: the medians of T=%d wrote harm layout %d, the feature route needs 2", T, tm);
     if (tm == 2) {
         rc = smh_feat::launch_features_clip(ctx, S, harm, perc, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP, d_fv,
                                             nP > 0 ? d_patches : nullptr, nullptr, nullptr, st);

@@ -282,6 +282,17 @@ int launch_hpss(const float *S, int B, int K, int T, int lh, int lp, float *harm
     int rc = smh_hpss_median_f32(nullptr, S, B, K, T, lh, lp, harm, perc, (void *)st);
     return rc ? rc : 0;
 }
+
+// whether launch_hpss(want_tmajor = 2) writes the 16-frame blocked harm image: the pair kernel's folds fit both axes and the
+// block-split kernel covers a tile of the plan (the persistent kernel, tried first, writes the same layout; smh_frontend_f32 refuses
+// a call whose medians came back in another layout than this promised)
+bool blocked_harm_ok(int K, int T, int lh, int lp) {
+    static const bool no_split = getenv("SMH_MEDIAN_NOSPLIT") != nullptr;
+    if (no_split || !(fast_ok(T, lh) && fast_ok(K, lp) && find_pair_kernel(lh, lp))) return false;
+    const SplitEntry *se = find_split_kernel(lh, lp);
+    Plan p, q;
+    return se && make_plan(K, T, lh, lp, &p) == SMH_OK && make_split_roles(K, p.TT, lh, lp, se->threads / 64, &q);
+}
 }  // namespace smh_median
 
 extern "C" int smh_median_time_f32(const smh_ctx *, const float *d_S, int B, int K, int T, int l_harm, float *d_harm,

@@ -30,6 +30,12 @@ struct Item {
     int clip, tile;
 };
 
+// The feature path of a clip of T frames when no taps are asked for, decided once for smh_frontend_f32 and the ragged planner
+// (and reported by smh_internal_frontend_route):
+//   0  the LDS image, even T: features_half_kernel      1  the LDS image, odd T (or SMH_FEAT_NOPAIR): features_clip_kernel
+//   2  the streaming kernels of smh_ragged.hip           3  neither: launch_hp_feat + launch_std_patch on the whole clip
+int feature_route(const smh_ctx *ctx, int T);
+
 }  // namespace smh_rag
 
 namespace smh_stft {
@@ -44,6 +50,8 @@ constexpr int kRagFrames = 20;  // (the equal-length path splits 98 frames into 
 namespace smh_median {
 // frames per median item and the LDS row stride that goes with it (two workgroups per CU); 0 when (lh, lp) has no block-split kernel
 int rag_tile_frames(int K, int lh, int lp, int *stride);
+// whether launch_hpss(want_tmajor = 2) of a (K, T) spectrogram writes the 16-frame blocked harm layout
+bool blocked_harm_ok(int K, int T, int lh, int lp);
 // both HPSS medians of every (clip, frame tile) item; harm in the 16-frame blocked layout
 int launch_rag(const float *d_S, float *d_harm, float *d_perc, int K, int lh, int lp, const smh_rag::Clip *d_clips,
                const smh_rag::Item *d_items, int n_items, hipStream_t st);

@@ -567,7 +567,21 @@ int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, in
     return rc ? rc : 1;
 }
 
+int feature_route(const smh_ctx *ctx, int T) {
+    if (smh_features_blocked_ok(ctx, T, 0)) {
+        if (!smh_median::blocked_harm_ok(ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc)) return 3;
+        return ((T & 1) || getenv("SMH_FEAT_NOPAIR")) ? 1 : 0;
+    }
+    return rag_context_ok(ctx) && rag_clip_ok(ctx, T) ? 2 : 3;
+}
+
 }  // namespace smh_rag
+
+// tests: the feature route (smh_rag::feature_route) of a clip of T frames in this context; -1 for a bad argument
+extern "C" int smh_internal_frontend_route(const smh_ctx *ctx, int T) {
+    if (!ctx || T < 1) return -1;
+    return smh_rag::feature_route(ctx, T);
+}
 
 // ---- the C ABI -------------------------------------------------------------------------------------------------------------
 namespace {
@@ -599,9 +613,9 @@ void classify(const smh_ctx *ctx, const float *d_audio, const long long *off, co
     for (int b = 0; b < B; ++b) {
         if (!rag_clip_ok(ctx, p.T[b])) continue;
         if (need8 && ((reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)off[b] * 4) % 8) != 0) continue;
-        // (even T: one workgroup per clip half; odd T -- or SMH_FEAT_NOPAIR, which makes smh_frontend_f32 choose the same -- one per clip)
-        if (smh_features_blocked_ok(ctx, p.T[b], 0)) cls[b] = ((p.T[b] & 1) || getenv("SMH_FEAT_NOPAIR")) ? 1 : 0;
-        else cls[b] = 2;
+        // (even T: one workgroup per clip half; odd T -- or SMH_FEAT_NOPAIR -- one per clip: the route smh_frontend_f32 takes)
+        const int r = smh_rag::feature_route(ctx, p.T[b]);
+        if (r <= 2) cls[b] = r;
     }
 }
 }  // namespace

@@ -284,7 +284,9 @@ class Frontend:
         """Clips of DIFFERENT lengths in one call (`smh_frontend_ragged_f32`).  clips: list of 1-D float32 arrays / tensors.
         Returns dict(fv=[(2*rows, T_b) tensors], patches=[(nP_b, W, 2*rows) tensors] (views of one buffer each),
         n_patches=[...], T=[...]).  Every clip gets bit for bit what `run` gives it alone or in an equal-length batch:
-        the clips are laid out at 16-byte aligned offsets, so each takes the same kernels as there."""
+        the clips are laid out at 16-byte aligned offsets, so each takes the same kernels as there.  (Not an equal-length
+        batch of an odd number of samples: its clips start off 8-byte boundaries and take the generic STFT kernel, whose S
+        differs from the specialised kernel's in the last bits.)"""
         B = len(clips)
         if B == 0:
             return {"fv": [], "patches": [], "n_patches": [], "T": []}

@@ -47,6 +47,10 @@ def test_ragged_equals_per_clip_and_equal_length_batches_bit_for_bit(fe):
         ref = ofe.featuregram(clips[i], "LogMelHarmPercSpec")
         got = res["fv"][i].cpu().numpy()
         assert np.mean(np.abs(got - ref) <= 1e-3) >= 0.98 and np.max(np.abs(got - ref)) <= 2e-2, (i, np.max(np.abs(got - ref)))
+        # from the clip's own device S (the kernel the ragged call uses): the medians select identical values, every bin within 1e-3 dB
+        S = fe.stft_mag(torch.from_numpy(clips[i]).cuda()[None])
+        ref_s = ofe.featuregram_from_S(S[0].cpu().numpy(), "LogMelHarmPercSpec")
+        assert np.max(np.abs(got - ref_s)) <= 1e-3, (i, float(np.max(np.abs(got - ref_s))))
         # patches from the DEVICE's featuregram: what is under test here is the scaler and the patch grid
         pref = ofe.tcn_input(ofe.feature_patches(got.astype(np.float32), 68, 34))
         assert pref.shape == tuple(res["patches"][i].shape), (i, pref.shape)
@@ -115,8 +119,9 @@ def test_ragged_sub_batches_and_stream_order(fe):
 
 def test_ragged_other_geometries_and_configurations():
     """Patch geometries of the reference's drivers (W 68 / 99 / 249, incl. clips shorter than a patch: tile-if-short inside the streaming
-    kernels) and the other window pair / feature names, each clip against the same clip alone; patches against the oracle's scaler and
-    patch grid on the device's featuregram."""
+    kernels) and the other window pair / feature names, each clip against the same clip alone and its featuregram against the oracle
+    from the clip's own device S (dB: 1e-3 on every bin; HarmPercSpec: 1e-6 max|S|; MelHarmPercSpec: rel 1e-5, abs 1e-6 max|S|);
+    patches against the oracle's scaler and patch grid on the device's featuregram."""
     from sm_hpss_mtl_amd.frontend import Frontend, FrontendConfig
     from sm_hpss_mtl_amd.synth import synth_clips
     lens = [16000, 30000, 33000, 39998, 60000, 9000, 52345]
@@ -125,7 +130,8 @@ def test_ragged_other_geometries_and_configurations():
                        (FrontendConfig(n_mels=0, log_db=False), ((68, 34),)), (FrontendConfig(log_db=False), ((68, 68),)),
                        (FrontendConfig(n_fft=512, n_mels=0), ((68, 68),))):
         fe = Frontend(cfg)
-        for W, shift in geoms:
+        name = ("Log" if cfg.log_db else "") + ("Mel" if cfg.n_mels else "") + "HarmPercSpec"
+        for g, (W, shift) in enumerate(geoms):
             res = fe.run_ragged(clips, W=W, shift=shift)
             torch.cuda.synchronize()
             for i, c in enumerate(clips):
@@ -133,6 +139,16 @@ def test_ragged_other_geometries_and_configurations():
                 assert torch.equal(res["fv"][i], one["fv"][0]), (cfg, W, i)
                 assert res["n_patches"][i] == one["n_patches"] and torch.equal(res["patches"][i], one["patches"]), (cfg, W, i)
                 got = res["fv"][i].cpu().numpy()
+                if g == 0:  # (the featuregram does not depend on the patch geometry)
+                    S = fe.stft_mag(torch.from_numpy(c).cuda()[None])[0].cpu().numpy()
+                    ref_s = ofe.featuregram_from_S(S, name, n_mels=cfg.n_mels, l_harm=cfg.l_harm, l_perc=cfg.l_perc)
+                    smax = float(S.max())
+                    if cfg.log_db:
+                        assert np.max(np.abs(got - ref_s)) <= 1e-3, (cfg, i, float(np.max(np.abs(got - ref_s))))
+                    elif not cfg.n_mels:
+                        assert np.max(np.abs(got - ref_s)) <= 1e-6 * smax, (cfg, i, float(np.max(np.abs(got - ref_s))) / smax)
+                    else:
+                        np.testing.assert_allclose(got, ref_s, rtol=1e-5, atol=1e-6 * smax, err_msg=str((cfg, i)))
                 pref = ofe.tcn_input(ofe.feature_patches(got.astype(np.float32), W, shift))
                 assert pref.shape == tuple(res["patches"][i].shape), (cfg, W, i, pref.shape)
                 if pref.size:
