@@ -245,6 +245,15 @@ int smh_model_create(const smh_model_cfg *cfg, smh_model **out);
  * (18 each) and an out kernel of shape (18, 1).  The bf16 forwards and trainer dtype 1 refuse a cascaded model. */
 #define SMH_HEADS_MTL 0
 #define SMH_HEADS_CASCADED 1
+/* SMH_HEADS_FUSION: get_Lemaire_MTL_intermediate_fusion_model (:327-420): two inputs harm_input / perc_input, each (N, W, n_feat)
+ * with cfg.n_feat the PER-BRANCH width, two independent TCN trunks 'tcn_initial_conv_H' / '_P', x = BatchNorm(concat[Flatten(trunk
+ * H), Flatten(trunk P)]) over D = 2 * W * 32 features (moving statistics, eps 1e-3), then B3_MTL's '3C' and heads on x.  out_dim as
+ * for SMH_HEADS_MTL.  Canonical order: trunk H [initial_conv kernel (1, n_feat, 32), bias, per block conv kernel, bias, conv1x1
+ * kernel, bias], trunk P (the same), the fused BatchNorm [gamma, beta, moving_mean, moving_variance] (D each), '3C' kernel (D,
+ * n_classes), bias, then per head [dense kernel (D, 16), bias, gamma, beta, moving_mean, moving_variance, out kernel, out bias].
+ * Only the two-input entry points below serve it: every single-input forward, smh_train_step_f32, the bf16 forwards, trainer
+ * dtype 1 and block_variant 1 refuse a fusion model. */
+#define SMH_HEADS_FUSION 2
 int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_model **out);
 void smh_model_destroy(smh_model *m);
 /* number of float32 parameters in canonical (Keras-layout) order, see DESIGN.md "weight order" */
@@ -415,11 +424,24 @@ float *smh_trainer_grad_ptr(smh_trainer *t);
  *             that penalty per head (n_heads), binary accuracy (threshold 0.5) of every sigmoid head (n_heads)] */
 int smh_train_step_f32(smh_trainer *t, const float *d_x, const float *d_y, int N, const float *d_drop_tcn,
                        const float *d_drop_heads, const float *h_loss_weights, float *d_losses, void *stream);
+/* The intermediate-fusion model (SMH_HEADS_FUSION).  Inference: d_xH, d_xP (N, W, n_feat) time-major -> d_out (N, out_dim)
+ * [S | M | (N) | R | 3C-softmax]; d_work: smh_fusion_workspace_bytes(m, N) bytes of device scratch (the two trunks' outputs).
+ * Training: as smh_train_step_f32 with two inputs; d_drop_tcn is (2, N, n_blocks, 32) -- the masks of trunk H, then of trunk P
+ * -- or NULL.  The trainer's data-parallel bucket is [gradient (num_params) | BN16 batch statistics of the heads (4 x 32) | the
+ * fused BatchNorm's batch means (D) and population variances (D)].  Every sum of the fusion layers runs in a fixed order (no
+ * atomics): deterministic mode keeps the step bit-reproducible. */
+size_t smh_fusion_workspace_bytes(const smh_model *m, int N);
+int smh_fusion_forward_f32(const smh_model *m, const float *d_xH, const float *d_xP, int N, float *d_out, void *d_work,
+                           size_t work_bytes, void *stream);
+int smh_fusion_train_step_f32(smh_trainer *t, const float *d_xH, const float *d_xP, const float *d_y, int N,
+                              const float *d_drop_tcn, const float *d_drop_heads, const float *h_loss_weights, float *d_losses,
+                              void *stream);
 /* g = grad * grad_scale (+ l2 term); per-tensor clip to `clipnorm` (<= 0: off); v = momentum*v - lr*g; w += v;
  * BN moving statistics <- 0.99*old + 0.01*batch; operand buffers re-packed on the device.              */
 int smh_trainer_apply_sgd_f32(smh_trainer *t, float lr, float momentum, float clipnorm, float grad_scale, void *stream);
 /* floats of the data-parallel bucket that starts at smh_trainer_grad_ptr: [gradient (num_params) | BatchNorm batch
- * statistics of the heads (4 x 32) | cascaded models only: the concatenation BatchNorm's statistics of S and M (2 x 36)];
+ * statistics of the heads (4 x 32) | cascaded models only: the concatenation BatchNorm's statistics of S and M (2 x 36);
+ * fusion models only: the fused BatchNorm's statistics (2 x D)];
  * all-reduce all of it so the moving statistics follow the mean over the ranks. */
 size_t smh_trainer_bucket_floats(const smh_trainer *t);
 /* copy momentum / Adam moments / step counters from `src` to `dst` (same model): growing a trainer keeps its state */

@@ -128,6 +128,9 @@ SIGNATURES = {
     "smh_trainer_set_dtype": (_i, [_vp, _i]),
     "smh_model_check_train_dtype": (_i, [_vp, _i]),
     "smh_trainer_apply_f32": (_i, [_vp, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint, _vp]),
+    "smh_fusion_workspace_bytes": (_sz, [_vp, _i]),
+    "smh_fusion_forward_f32": (_i, [_vp, _fp, _fp, _i, _fp, _vp, _sz, _vp]),
+    "smh_fusion_train_step_f32": (_i, [_vp, _fp, _fp, _fp, _i, _fp, _fp, _vp, _fp, _vp]),
 }
 
 _lib = None

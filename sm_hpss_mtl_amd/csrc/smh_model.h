@@ -38,6 +38,7 @@ struct TcnArgs {
     int head_odim[kMaxHeads];
     int head_sigmoid[kMaxHeads];
     int cascade;  // SMH_HEADS_CASCADED: heads S and M read BN18(concat[their Dropout(16), R's output]) (smh_tcn_heads.h)
+    int trunk_only;  // 1: the forward ends at the trunk (its tap / saved activations); no Dense-on-trunk, no heads (the fusion model's trunks)
 };
 
 // training-mode extras of the forward kernel (all optional)
@@ -81,7 +82,11 @@ struct smh_model {
     smh_model_cfg cfg;
     int n_blocks, n_heads, NH, n_mt, D, out_dim, FQ;
     int head_odim[smh_tcn::kMaxHeads], head_sigmoid[smh_tcn::kMaxHeads];
-    int heads = 0;                      // SMH_HEADS_MTL / SMH_HEADS_CASCADED
+    int heads = 0;                      // SMH_HEADS_MTL / SMH_HEADS_CASCADED / SMH_HEADS_FUSION
+    // SMH_HEADS_FUSION: the two trunks as models of their own (B3_MTL objects whose Dense / heads are never run).  Their master
+    // weights are copies of the fusion model's trunk tensors, refreshed by repack(); their operand buffers are what the trunk
+    // forwards read.  The fusion model itself packs only the Dense layers on the fused features (D = 2 W 32) and the heads.
+    smh_model *trunk[2] = {nullptr, nullptr};
     int head_cat[smh_tcn::kMaxHeads];   // kCat for a head that reads the concatenation (cascaded S, M), else 0
     size_t n_params;
     float *d_flat = nullptr;  // master weights, canonical (Keras-layout) order, n_params floats
@@ -114,15 +119,33 @@ struct Offsets {
     size_t blk0, blk_stride;           // first block; per block: k1 (3*C*C), b1 (C), k2 (C*C), b2 (C)
     size_t c3_k, c3_b;                 // 3C kernel (D x ncls), bias
     size_t head[kMaxHeads];            // per head: dense k (D x 16), dense b, gamma, beta, mean, var, out k, out b
+    size_t trunk_p = 0;                // fusion: canonical offset of trunk P (trunk H starts at 0, as w0_k ...); else 0
+    size_t fbn = 0;                    // fusion: the fused BatchNorm's gamma, beta, moving_mean, moving_variance (D each)
 };
+// floats of one keras-tcn 2.3 trunk in canonical order
+inline size_t trunk_floats(const smh_model_cfg &c) {
+    return (size_t)c.n_feat * C + C + (size_t)c.nb_stacks * c.n_dilations * (3 * C * C + C + C * C + C);
+}
 Offsets offsets(const smh_model *m);
 void fill_args(const smh_model *m, int N, TcnArgs *a, size_t *lds);
 int repack(smh_model *m, hipStream_t st);  // d_flat -> packed operand buffers
 int launch_forward_bf16_train(smh_model *m, const float *d_x, int N, const TrainIO *tio, hipStream_t st);  // smh_tcn_bf16.hip
 bool backward_bf16_supported(int T, int n_dil);  // smh_train_bf16.hip: the patch geometry fits the split-bf16 backward's LDS plan
 int forward_bf16_supported(const smh_model *m);  // smh_tcn_bf16.hip: SMH_OK, or why the split-bf16 training forward refuses m
+// trunk_only = 1: the forward ends at the trunk (d_trunk tap / tio's saved activations); d_out is not written
 int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
-                   hipStream_t st, int from_x0 = 0, int x0_shift = 0, int x0_T = 0);
+                   hipStream_t st, int from_x0 = 0, int x0_shift = 0, int x0_T = 0, int trunk_only = 0);
+// smh_fusion.hip: the layers behind the intermediate-fusion model's two trunks (SMH_HEADS_FUSION).
+// launch_fusion_dense: the Dense layers on the fused features; train = false: xh / xp = the trunk taps (N, W, 32), BN with the moving
+// statistics, out = the heads' outputs (N, out_dim); train = true: xh = xhat (N, D), out = pre (N, kPS) incl. biases.
+int launch_fusion_dense(const smh_model *m, int N, const float *xh, const float *xp, float *out, bool train, hipStream_t st);
+// trainer scratch of the fusion layers (floats) at a batch capacity of max_batch
+size_t fusion_scratch_floats(const smh_model *m, int max_batch);
+// phase 0: batch statistics (-> bnstat: mean D | variance D), xhat, pre (-> pd); phase 1 (pd = dpre): the Dense kernels' and the fused
+// BatchNorm's gradients (stored into `grad`), d loss / d trunk output of both trunks (fusion_gt)
+int launch_fusion_train(const smh_model *m, int N, int max_batch, const float *acts_h, const float *acts_p, float *scratch,
+                        float *bnstat, float *pd, float *grad, int phase, hipStream_t st);
+const float *fusion_gt(const smh_model *m, int max_batch, const float *scratch, int N, int b);
 // smh_model_cfg.block_variant = 1 (smh_tcn_v2.hip): the two-convolution residual block of keras-tcn >= 2.8, inference only
 int launch_forward_v2(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, hipStream_t st);
 }  // namespace smh_tcn

@@ -987,7 +987,7 @@ b3mtl_forward_kernel(TcnArgs a, const float *__restrict__ X, const float *__rest
     if (tracing && blockIdx.x < 256 && threadIdx.x == 0) a.trace[4 * 3000 + 2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
     if (gave_up) {  // a dependency never arrived: the outputs are not results -- say so in the model's error word
         __syncthreads();
-        for (int i = threadIdx.x; i < g_here * a.out_dim; i += blockDim.x) out[(size_t)n0 * a.out_dim + i] = 0.f;
+        for (int i = threadIdx.x; i < (a.trunk_only ? 0 : g_here * a.out_dim); i += blockDim.x) out[(size_t)n0 * a.out_dim + i] = 0.f;
         if (threadIdx.x == 0 && a.status) atomicOr(a.status, 1);
     }
 }
@@ -1013,7 +1013,9 @@ static void pack_host(const smh_model *m, const float *h, std::vector<float> &W0
     W0.assign(m->nW0, 0.f), Wb.assign(m->nWb, 0.f), WhA.assign(m->nWhA, 0.f), hp.assign(m->nhp, 0.f);
     std::vector<float> Wh((size_t)D * NH, 0.f), bhv((size_t)m->n_mt * 16, 0.f);
     const float *p = h;
-    if (m->cfg.block_variant == 1) {  // smh_tcn_v2.hip reads the trunk from the canonical tensor: only the heads are packed
+    if (m->heads == SMH_HEADS_FUSION) {  // the trunks are packed by m->trunk[0 / 1]; the fused BN is read in canonical order
+        p += 2 * trunk_floats(m->cfg) + (size_t)4 * D;
+    } else if (m->cfg.block_variant == 1) {  // smh_tcn_v2.hip reads the trunk from the canonical tensor: only the heads are packed
         p += (size_t)3 * F * C + C + 3 * C * C + C + (size_t)F * C + C + (size_t)(m->n_blocks - 1) * 2 * (3 * C * C + C);
     } else {
     for (int s = 0; s < FQ; ++s)
@@ -1117,6 +1119,10 @@ Offsets offsets(const smh_model *m) {
     o.w0_b = p, p += C;
     o.blk0 = p, o.blk_stride = 3 * C * C + C + C * C + C;
     p += (size_t)m->n_blocks * o.blk_stride;
+    if (m->heads == SMH_HEADS_FUSION) {  // trunk P, then the fused BatchNorm
+        o.trunk_p = p, p += trunk_floats(m->cfg);
+        o.fbn = p, p += 4 * D;
+    }
     o.c3_k = p, p += D * ncls;
     o.c3_b = p, p += ncls;
     for (int h = 0; h < m->n_heads; ++h) {
@@ -1128,6 +1134,14 @@ Offsets offsets(const smh_model *m) {
 
 int repack(smh_model *m, hipStream_t st) {
     m->version++;  // every change of the master weights passes through here
+    if (m->heads == SMH_HEADS_FUSION) {  // the trunks' master copies follow the fusion model's trunk tensors
+        const size_t tf = trunk_floats(m->cfg);
+        for (int b = 0; b < 2; ++b) {
+            SMH_CHECK_HIP(hipMemcpyAsync(m->trunk[b]->d_flat, m->d_flat + b * tf, tf * sizeof(float), hipMemcpyDeviceToDevice, st));
+            const int rc = repack(m->trunk[b], st);
+            if (rc) return rc;
+        }
+    }
     const size_t n = m->nW0 + m->nWb + m->nWhA + m->nhp;
     // the four operand buffers are one allocation: d_W0 is its base
     hipLaunchKernelGGL(repack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->d_flat, m->d_map, m->d_W0, n);
@@ -1140,6 +1154,7 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     a.N = N, a.T = T, a.F = m->cfg.n_feat, a.FQ = m->FQ, a.n_blocks = m->n_blocks, a.n_dil = m->cfg.n_dilations;
     a.vec_ok = (a.F % 4 == 0) && (a.FQ % 4 == 0) && (a.FQ * 4 == a.F);
     a.skip_heads = 0;
+    a.trunk_only = 0;
     a.tune = 0;
     a.trace = nullptr;
     a.from_x0 = 0, a.x0_shift = 0, a.x0_T = 0;
@@ -1187,10 +1202,11 @@ static bool skew_schedule(const TcnArgs &a, int units) {
 }
 
 int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
-                   hipStream_t st, int from_x0, int x0_shift, int x0_T) {
+                   hipStream_t st, int from_x0, int x0_shift, int x0_T, int trunk_only) {
     TcnArgs a;
     size_t lds;
     fill_args(m, N, &a, &lds);
+    a.trunk_only = trunk_only;
     a.from_x0 = from_x0, a.x0_shift = x0_shift, a.x0_T = x0_T;
     // timing probes (outputs invalid; training would read stale activations): only under SMH_ENABLE_PROBES=1, announced on stderr
     if (const char *ev = smh::probe_env("SMH_TCN_BLOCKS")) a.n_blocks = atoi(ev);  // tools/tune_model.py
@@ -1273,7 +1289,7 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
 // tests: 1 when smh_model_forward_f32 of N patches takes the skewed block schedule, 0 when the barrier schedule (under the
 // current SMH_TCN_SKEW), -1 when that forward would be refused
 extern "C" int smh_internal_tcn_schedule(const smh_model *m, int N) {
-    if (!m || N < 1 || m->cfg.block_variant != 0) return -1;
+    if (!m || N < 1 || m->cfg.block_variant != 0 || m->heads == SMH_HEADS_FUSION) return -1;
     TcnArgs a;
     size_t lds;
     fill_args(m, N, &a, &lds);
@@ -1287,8 +1303,11 @@ extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
 
 extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_model **out) {
     SMH_REQUIRE(cfg && out, "smh_model_create: null argument");
-    SMH_REQUIRE(heads == SMH_HEADS_MTL || heads == SMH_HEADS_CASCADED, "smh_model_create_heads: heads must be %d (MTL) or %d (cascaded), got %d",
-                SMH_HEADS_MTL, SMH_HEADS_CASCADED, heads);
+    SMH_REQUIRE(heads == SMH_HEADS_MTL || heads == SMH_HEADS_CASCADED || heads == SMH_HEADS_FUSION,
+                "smh_model_create_heads: heads must be %d (MTL), %d (cascaded) or %d (intermediate fusion), got %d", SMH_HEADS_MTL,
+                SMH_HEADS_CASCADED, SMH_HEADS_FUSION, heads);
+    SMH_REQUIRE(heads != SMH_HEADS_FUSION || cfg->block_variant == 0,
+                "smh_model_create_heads: the intermediate-fusion model is built for block_variant 0 (keras-tcn 2.3.x) only");
     SMH_REQUIRE(cfg->nb_filters == C, "B3_MTL kernel is tiled for nb_filters=32 (got %d)", cfg->nb_filters);
     SMH_REQUIRE(cfg->kernel_size == 3, "B3_MTL kernel supports kernel_size=3 (got %d)", cfg->kernel_size);
     SMH_REQUIRE(cfg->n_classes == 3 || cfg->n_classes == 5, "n_classes must be 3 or 5 (got %d)", cfg->n_classes);
@@ -1314,7 +1333,7 @@ extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_m
         const int od[3] = {1, 1, 2}, sg[3] = {1, 1, 0};
         for (int i = 0; i < 3; ++i) m->head_odim[i] = od[i], m->head_sigmoid[i] = sg[i];
     }
-    m->D = cfg->patch_size * C;
+    m->D = cfg->patch_size * C * (heads == SMH_HEADS_FUSION ? 2 : 1);
     m->NH = cfg->n_classes + kHidden * m->n_heads;
     m->n_mt = (m->NH + 15) / 16;
     m->out_dim = cfg->n_classes;
@@ -1325,13 +1344,14 @@ extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_m
     n += (size_t)m->n_blocks * (3 * C * C + C + C * C + C);
     if (cfg->block_variant == 1)
         n = (size_t)3 * cfg->n_feat * C + C + 3 * C * C + C + (size_t)cfg->n_feat * C + C + (size_t)(m->n_blocks - 1) * 2 * (3 * C * C + C);
+    if (heads == SMH_HEADS_FUSION) n = 2 * trunk_floats(*cfg) + (size_t)4 * m->D;  // two trunks, the fused BatchNorm
     n += (size_t)m->D * cfg->n_classes + cfg->n_classes;
     for (int i = 0; i < m->n_heads; ++i) n += (size_t)m->D * kHidden + kHidden + head_tail_floats(m, i);
     m->n_params = n;
     SMH_REQUIRE(n < (1u << 24), "model too large for the float-encoded gather map");
     m->nW0 = (size_t)m->FQ * 2 * 64 + 32;
     m->nWb = (size_t)m->n_blocks * kBlockFloats;
-    if (cfg->block_variant == 1) m->nW0 = m->nWb = 0;
+    if (cfg->block_variant == 1 || heads == SMH_HEADS_FUSION) m->nW0 = m->nWb = 0;
     m->nWhA = (size_t)m->D * 64 * ((m->NH + 63) / 64) + (size_t)m->n_mt * 16;
     m->nhp = 0;
     for (int i = 0; i < m->n_heads; ++i) m->nhp += head_tail_floats(m, i);
@@ -1358,6 +1378,15 @@ extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_m
     m->d_Wb = m->d_W0 + m->nW0;
     m->d_WhA = m->d_Wb + m->nWb;
     m->d_hp = m->d_WhA + m->nWhA;
+    if (heads == SMH_HEADS_FUSION) {
+        for (int b = 0; b < 2; ++b) {
+            const int rc = smh_model_create_heads(cfg, SMH_HEADS_MTL, &m->trunk[b]);
+            if (rc) {
+                smh_model_destroy(m);
+                return rc;
+            }
+        }
+    }
     *out = m;
     return SMH_OK;
 }
@@ -1369,6 +1398,8 @@ extern "C" void smh_model_destroy(smh_model *m) {
     (void)hipFree(m->d_map);
     (void)hipFree(m->d_bf16);
     (void)hipFree(m->d_status);
+    smh_model_destroy(m->trunk[0]);
+    smh_model_destroy(m->trunk[1]);
     delete m;
 }
 
@@ -1378,6 +1409,14 @@ extern "C" int smh_model_status(smh_model *m, void *stream) {
     int word = 0;
     SMH_CHECK_HIP(hipMemcpyAsync(&word, m->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
     SMH_CHECK_HIP(hipStreamSynchronize(st));
+    for (smh_model *tm : m->trunk) {  // the fusion model's trunks run as models of their own: their words are this model's
+        if (!tm) continue;
+        int tw = 0;
+        SMH_CHECK_HIP(hipMemcpyAsync(&tw, tm->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
+        SMH_CHECK_HIP(hipStreamSynchronize(st));
+        if (tw) SMH_CHECK_HIP(hipMemsetAsync(tm->d_status, 0, sizeof(int), st));
+        word |= tw;
+    }
     if (word == 0) return SMH_OK;
     SMH_CHECK_HIP(hipMemsetAsync(m->d_status, 0, sizeof(int), st));
     return smh::set_error(SMH_E_DEVICE, "B3_MTL forward: device error word 0x%x (bit 0: a wave gave up waiting for a tile flag of the "
@@ -1408,7 +1447,7 @@ extern "C" int smh_model_get_weights(const smh_model *m, float *h, size_t n, voi
 }
 
 extern "C" const float *smh_model_w0_ptr(const smh_model *m) {
-    return (m && m->cfg.block_variant == 0) ? m->d_flat + smh_tcn::offsets(m).w0_k : nullptr;
+    return (m && m->cfg.block_variant == 0 && m->heads != SMH_HEADS_FUSION) ? m->d_flat + smh_tcn::offsets(m).w0_k : nullptr;
 }
 
 // ---- dense file-level inference (DAFx12_Speech_Music_Detection_B3_MTL_v2.py:634-665): every hop-`shift` patch of a
@@ -1454,6 +1493,8 @@ extern "C" int smh_model_forward_dense_f32(const smh_model *m, const float *d_fv
                                            float *d_out, void *stream) {
     SMH_REQUIRE(m && d_fv && d_work && d_out, "smh_model_forward_dense_f32: null argument");
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_model_forward_dense_f32: exists for block_variant 0 only");
+    SMH_REQUIRE(m->heads != SMH_HEADS_FUSION, "smh_model_forward_dense_f32: no dense file-level path for an intermediate-fusion model "
+                "(two inputs): build the patches and call smh_fusion_forward_f32");
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_fv) % 16) == 0 &&
                     (reinterpret_cast<uintptr_t>(d_out) % 4) == 0,
                 "smh_model_forward_dense_f32: d_fv and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries");
@@ -1561,6 +1602,8 @@ extern "C" int smh_model_forward_x0_f32(const smh_model *m, const float *d_x0p, 
                                         void *stream) {
     SMH_REQUIRE(m && d_x0p && d_out, "smh_model_forward_x0_f32: null argument");
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_model_forward_x0_f32: the layer-0 fusion exists for block_variant 0 only");
+    SMH_REQUIRE(m->heads != SMH_HEADS_FUSION, "smh_model_forward_x0_f32: an intermediate-fusion model has two inputs and no fused-x0 "
+                "path; use smh_fusion_forward_f32");
     SMH_REQUIRE(N >= 0, "smh_model_forward_x0_f32: N=%d", N);
     if (N == 0) return SMH_OK;
     return smh_tcn::launch_forward(m, d_x0p, N, d_out, d_trunk, nullptr, (hipStream_t)stream, 1);
@@ -1569,6 +1612,8 @@ extern "C" int smh_model_forward_x0_f32(const smh_model *m, const float *d_x0p, 
 extern "C" int smh_model_forward_f32(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk,
                                      void *stream) {
     SMH_REQUIRE(m && d_x && d_out, "smh_model_forward_f32: null argument");
+    SMH_REQUIRE(m->heads != SMH_HEADS_FUSION, "smh_model_forward_f32: an intermediate-fusion model has two inputs; use "
+                "smh_fusion_forward_f32");
     SMH_REQUIRE(N >= 0, "smh_model_forward_f32: N=%d", N);
     if (N == 0) return SMH_OK;
     if (m->cfg.block_variant == 1) return smh_tcn::launch_forward_v2(m, d_x, N, d_out, d_trunk, (hipStream_t)stream);

@@ -57,10 +57,59 @@ __device__ __forceinline__ void cascaded_head(const TcnArgs &a, const float *pp,
     orow[h] = 1.0f / (1.0f + expf(-s));
 }
 
+// Inference tail of the heads for the g_here patches n0 .. of a workgroup from their Dense-on-features outputs `pre` (LDS, row
+// stride kPS, without bias) and the NH biases `bh`: BN / relu / output Dense / activations, one thread per (patch, head), one per
+// patch for '3C' (threads 128 ..).  Needs g_here * n_heads <= 128 and blockDim.x >= 128 + g_here.  Shared by dense_and_heads and the
+// fusion model's tail (smh_fusion.hip).
+__device__ __forceinline__ void heads_tail(const TcnArgs &a, const float *pre, const float *bh, const float *__restrict__ hp,
+                                           float *__restrict__ out, int n0, int g_here) {
+    const int tid = threadIdx.x;
+    if (a.cascade && tid < g_here * a.n_heads) {
+        cascaded_head(a, pre + (tid / a.n_heads) * kPS, bh, hp, out + (size_t)(n0 + tid / a.n_heads) * a.out_dim, tid % a.n_heads);
+    } else if (tid < g_here * a.n_heads) {
+        const int p = tid / a.n_heads, h = tid - p * a.n_heads;
+        const float *ph = hp;
+        int col = 0;
+        for (int k = 0; k < h; ++k) {
+            ph += 4 * kHidden + kHidden * a.head_odim[k] + a.head_odim[k];
+            col += a.head_odim[k];
+        }
+        const float *gamma = ph, *beta = ph + 16, *mean = ph + 32, *var = ph + 48, *wo = ph + 64;
+        const int od = a.head_odim[h];
+        const float *bo = wo + kHidden * od;
+        float hid[kHidden];
+#pragma unroll
+        for (int i = 0; i < kHidden; ++i) {
+            const int o = a.n_classes + h * kHidden + i;
+            float v = pre[p * kPS + o] + bh[o];
+            v = (v - mean[i]) / sqrtf(var[i] + kBnEps);
+            v = v * gamma[i] + beta[i];
+            hid[i] = fmaxf(v, 0.f);
+        }
+        for (int c = 0; c < od; ++c) {
+            float s = bo[c];
+#pragma unroll
+            for (int i = 0; i < kHidden; ++i) s = fmaf(hid[i], wo[i * od + c], s);
+            if (a.head_sigmoid[h]) s = 1.0f / (1.0f + expf(-s));
+            out[(size_t)(n0 + p) * a.out_dim + col + c] = s;
+        }
+    } else if (tid >= 128 && tid < 128 + g_here) {
+        const int p = tid - 128;
+        float mxl = -INFINITY;
+        for (int c = 0; c < a.n_classes; ++c) mxl = fmaxf(mxl, pre[p * kPS + c] + bh[c]);
+        float den = 0.f;
+        for (int c = 0; c < a.n_classes; ++c) den += expf(pre[p * kPS + c] + bh[c] - mxl);
+        const int col = a.out_dim - a.n_classes;
+        for (int c = 0; c < a.n_classes; ++c)
+            out[(size_t)(n0 + p) * a.out_dim + col + c] = expf(pre[p * kPS + c] + bh[c] - mxl) / den;
+    }
+}
+
 template <bool TRAIN>
 __device__ __forceinline__ void dense_and_heads(const TcnArgs &a, const float *xin, float *xout, const float *__restrict__ WhA,
                                                 const float *__restrict__ hp, float *__restrict__ out, const TrainIO &tio,
                                                 int n0, int g_here) {
+    if (a.trunk_only) return;  // (uniform) the fusion model's trunks: its own tail reads the trunk tap / saved activations
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int T = a.T;
     // ---- Dense layers on the flattened trunk: pre[g][o] = sum_k flat[g][k] * Wh[k][o], k = t*32 + c, o < NH (51 or 69) ----
@@ -146,46 +195,7 @@ __device__ __forceinline__ void dense_and_heads(const TcnArgs &a, const float *x
         }
         return;
     }
-    const int tid = threadIdx.x;
-    if (a.cascade && tid < g_here * a.n_heads) {
-        cascaded_head(a, pre + (tid / a.n_heads) * kPS, bh, hp, out + (size_t)(n0 + tid / a.n_heads) * a.out_dim, tid % a.n_heads);
-    } else if (tid < g_here * a.n_heads) {
-        const int p = tid / a.n_heads, h = tid - p * a.n_heads;
-        const float *ph = hp;
-        int col = 0;
-        for (int k = 0; k < h; ++k) {
-            ph += 4 * kHidden + kHidden * a.head_odim[k] + a.head_odim[k];
-            col += a.head_odim[k];
-        }
-        const float *gamma = ph, *beta = ph + 16, *mean = ph + 32, *var = ph + 48, *wo = ph + 64;
-        const int od = a.head_odim[h];
-        const float *bo = wo + kHidden * od;
-        float hid[kHidden];
-#pragma unroll
-        for (int i = 0; i < kHidden; ++i) {
-            const int o = a.n_classes + h * kHidden + i;
-            float v = pre[p * kPS + o] + bh[o];
-            v = (v - mean[i]) / sqrtf(var[i] + kBnEps);
-            v = v * gamma[i] + beta[i];
-            hid[i] = fmaxf(v, 0.f);
-        }
-        for (int c = 0; c < od; ++c) {
-            float s = bo[c];
-#pragma unroll
-            for (int i = 0; i < kHidden; ++i) s = fmaf(hid[i], wo[i * od + c], s);
-            if (a.head_sigmoid[h]) s = 1.0f / (1.0f + expf(-s));
-            out[(size_t)(n0 + p) * a.out_dim + col + c] = s;
-        }
-    } else if (tid >= 128 && tid < 128 + g_here) {
-        const int p = tid - 128;
-        float mxl = -INFINITY;
-        for (int c = 0; c < a.n_classes; ++c) mxl = fmaxf(mxl, pre[p * kPS + c] + bh[c]);
-        float den = 0.f;
-        for (int c = 0; c < a.n_classes; ++c) den += expf(pre[p * kPS + c] + bh[c] - mxl);
-        const int col = a.out_dim - a.n_classes;
-        for (int c = 0; c < a.n_classes; ++c)
-            out[(size_t)(n0 + p) * a.out_dim + col + c] = expf(pre[p * kPS + c] + bh[c] - mxl) / den;
-    }
+    heads_tail(a, pre, bh, hp, out, n0, g_here);
 }
 
 }  // namespace smh_tcn

@@ -1237,6 +1237,7 @@ struct smh_trainer {
     void *d_bwd_pack = nullptr;  // the blocks' kernels as split bf16 A operands of the backward pass (smh_train_bf16.hip), dtype 1 only
     size_t bwd_pack_cap = 0;
     float *d_dr = nullptr;        // cascaded heads: d loss / d r of S and M, (2, max_batch, 2)
+    float *d_fusion = nullptr;    // fusion model: scratch of the fused layers (fusion_scratch_floats); d_acts / d_upre hold both trunks
     size_t bn_floats = 0;         // BatchNorm statistics behind the gradient: kBnStatFloats (+ kCatStatFloats for cascaded heads)
     double *d_l2part = nullptr;   // l2_penalty_kernel: kL2Chunks partial sums per head, then its arrival ticket
     Segment *d_segs = nullptr;
@@ -1250,7 +1251,8 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_trainer_create: training is built for block_variant 0 (keras-tcn 2.3.x) only");
     smh_trainer *t = new smh_trainer();
     t->m = m, t->max_batch = max_batch;
-    t->bn_floats = kBnStatFloats + (m->heads == SMH_HEADS_CASCADED ? kCatStatFloats : 0);
+    const bool fusion = m->heads == SMH_HEADS_FUSION;
+    t->bn_floats = kBnStatFloats + (m->heads == SMH_HEADS_CASCADED ? kCatStatFloats : 0) + (fusion ? 2 * (size_t)m->D : 0);
     const Offsets off = offsets(m);
     std::vector<Segment> segs;
     int group = 0;
@@ -1261,14 +1263,24 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
             segs.push_back(Segment{(unsigned)(o + co), (unsigned)sz, kind, kind >= 2 ? aux + (int)co : aux, group, p0, pn});
         }
     };
-    add(off.w0_k, (size_t)m->cfg.n_feat * C, 0, 0);
-    add(off.w0_b, C, 0, 0);
-    for (int b = 0; b < m->n_blocks; ++b) {
-        const size_t w = off.blk0 + (size_t)b * off.blk_stride;
-        add(w, 3 * C * C, 0, 0);
-        add(w + 3 * C * C, C, 0, 0);
-        add(w + 3 * C * C + C, C * C, 0, 0);
-        add(w + 3 * C * C + C + C * C, C, 0, 0);
+    for (int tr = 0; tr < (fusion ? 2 : 1); ++tr) {  // the fusion model's trunks H and P (both in the trunk group)
+        const size_t base = tr ? off.trunk_p : 0;
+        add(base + off.w0_k, (size_t)m->cfg.n_feat * C, 0, 0);
+        add(base + off.w0_b, C, 0, 0);
+        for (int b = 0; b < m->n_blocks; ++b) {
+            const size_t w = base + off.blk0 + (size_t)b * off.blk_stride;
+            add(w, 3 * C * C, 0, 0);
+            add(w + 3 * C * C, C, 0, 0);
+            add(w + 3 * C * C + C, C * C, 0, 0);
+            add(w + 3 * C * C + C + C * C, C, 0, 0);
+        }
+    }
+    if (fusion) {  // the fused BatchNorm (trunk group: every output reads it); its batch statistics sit behind the BN16 ones
+        const size_t D = m->D;
+        add(off.fbn, D, 0, 0);
+        add(off.fbn + D, D, 0, 0);
+        add(off.fbn + 2 * D, D, 2, kBnStatFloats);
+        add(off.fbn + 3 * D, D, 3, kBnStatFloats + (int)D);
     }
     group = 1;
     add(off.c3_k, (size_t)m->D * m->cfg.n_classes, 0, 0);
@@ -1295,7 +1307,7 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
         add(p, m->head_odim[h], 0, 0);
     }
     t->nseg = (int)segs.size();
-    const size_t nact = (size_t)max_batch * (m->n_blocks + 1) * m->cfg.patch_size * C;
+    const size_t nact = (size_t)max_batch * (m->n_blocks + 1) * m->cfg.patch_size * C * (fusion ? 2 : 1);
     hipError_t e = hipMalloc((void **)&t->d_acts, nact * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_pre, (size_t)max_batch * kPS * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_dpre, (size_t)max_batch * kPS * sizeof(float));
@@ -1308,7 +1320,9 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_s2, m->n_params * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_sumsq, segs.size() * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_scratch_out, (size_t)max_batch * m->out_dim * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&t->d_upre, (size_t)max_batch * m->n_blocks * m->cfg.patch_size * C * sizeof(float));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&t->d_upre, (size_t)max_batch * m->n_blocks * m->cfg.patch_size * C * (fusion ? 2 : 1) * sizeof(float));
+    if (e == hipSuccess && fusion) e = hipMalloc((void **)&t->d_fusion, fusion_scratch_floats(m, max_batch) * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_l2part, (kMaxHeads * kL2Chunks + 1) * sizeof(double));
     if (e == hipSuccess) e = hipMemset(t->d_l2part, 0, (kMaxHeads * kL2Chunks + 1) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_segs, segs.size() * sizeof(Segment));
@@ -1334,6 +1348,7 @@ extern "C" void smh_trainer_destroy(smh_trainer *t) {
     (void)hipFree(t->d_bwd_pack);
     (void)hipFree(t->d_gt);
     (void)hipFree(t->d_dr);
+    (void)hipFree(t->d_fusion);
     delete t;
 }
 
@@ -1365,7 +1380,8 @@ extern "C" int smh_model_check_train_dtype(const smh_model *m, int dtype) {
     SMH_REQUIRE(m, "smh_model_check_train_dtype: null model");
     SMH_REQUIRE(dtype == 0 || dtype == 1, "smh_trainer_set_dtype: dtype must be 0 (f32) or 1 (split bf16 operands)");
     SMH_REQUIRE(dtype == 0 || m->heads == SMH_HEADS_MTL,
-                "smh_trainer_set_dtype: the split-bf16 training step has the B3_MTL heads only; a cascaded model trains in f32 (dtype 0)");
+                "smh_trainer_set_dtype: the split-bf16 training step has the B3_MTL heads only; a cascaded or intermediate-fusion model "
+                "trains in f32 (dtype 0)");
     // a model the split-bf16 forward refuses would otherwise fail only at its first training step
     return dtype == 0 ? SMH_OK : forward_bf16_supported(m);
 }
@@ -1382,6 +1398,8 @@ extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float 
                                   const float *d_drop_heads, const float *h_loss_weights, float *d_losses, void *stream) {
     SMH_REQUIRE(t && d_x && d_y && d_losses, "smh_train_step_f32: null argument");
     SMH_REQUIRE(N >= 1 && N <= t->max_batch, "smh_train_step_f32: batch %d outside [1, %d]", N, t->max_batch);
+    SMH_REQUIRE(t->m->heads != SMH_HEADS_FUSION, "smh_train_step_f32: an intermediate-fusion model has two inputs; use "
+                "smh_fusion_train_step_f32");
     smh_model *m = t->m;
     hipStream_t st = (hipStream_t)stream;
     SMH_CHECK_HIP(hipMemsetAsync(t->d_grad, 0, m->n_params * sizeof(float), st));
@@ -1548,4 +1566,96 @@ extern "C" int smh_trainer_apply_f32(smh_trainer *t, int optimizer, float lr, fl
 extern "C" int smh_trainer_apply_sgd_f32(smh_trainer *t, float lr, float momentum, float clipnorm, float grad_scale,
                                          void *stream) {
     return smh_trainer_apply_f32(t, 0, lr, momentum, 0.f, 0.f, clipnorm, grad_scale, 0xFFFFFFFFu, stream);
+}
+
+// The intermediate-fusion model's training step: the two trunks' training forwards (the B3_MTL forward kernel, trunk only), the
+// fused BatchNorm's batch statistics and the Dense layers on the fused features (smh_fusion.hip), B3_MTL's heads-training kernel with
+// D = 2 W 32, the Dense kernels' and the fused BatchNorm's gradients, then the MFMA trunk backward once per trunk, fed with d loss /
+// d (trunk output), each writing its own offsets of the flat gradient.
+extern "C" int smh_fusion_train_step_f32(smh_trainer *t, const float *d_xH, const float *d_xP, const float *d_y, int N,
+                                         const float *d_drop_tcn, const float *d_drop_heads, const float *h_loss_weights,
+                                         float *d_losses, void *stream) {
+    SMH_REQUIRE(t && d_xH && d_xP && d_y && d_losses, "smh_fusion_train_step_f32: null argument");
+    SMH_REQUIRE(t->m->heads == SMH_HEADS_FUSION, "smh_fusion_train_step_f32: the model is not an intermediate-fusion model");
+    SMH_REQUIRE(N >= 1 && N <= t->max_batch, "smh_fusion_train_step_f32: batch %d outside [1, %d]", N, t->max_batch);
+    SMH_REQUIRE(t->dtype == 0, "smh_fusion_train_step_f32: the intermediate-fusion model trains in f32 (dtype 0) only");
+    smh_model *m = t->m;
+    hipStream_t st = (hipStream_t)stream;
+    const int T = m->cfg.patch_size, half = T * C;
+    const size_t nact = (size_t)t->max_batch * (m->n_blocks + 1) * half, nupre = (size_t)t->max_batch * m->n_blocks * half;
+    const size_t ndrop = (size_t)N * m->n_blocks * C;
+    // the f32 MFMA trunk backward with d loss / d trunk output given (smh_train_step_f32's default path)
+    const int RPm = ((kMG * T + 15) / 16) * 16;
+    const size_t lds_m = sizeof(float) * ((size_t)4 * RPm * SX + 4 * C * kWS + kMG * kPS + C + kZW);
+    const size_t lds_long = sizeof(float) * ((size_t)4 * RPm * SX + kMG * kPS + C + kZW);
+    const bool short_ok = lds_m <= 156 * 1024 && T <= kMfmaMaxT, long_ok = lds_long <= 156 * 1024 && T <= kMfmaLongT;
+    SMH_REQUIRE(short_ok || long_ok, "smh_fusion_train_step_f32: patch_size %d too long for the trunk backward (at most %d frames)", T,
+                kMfmaLongT);
+    SMH_CHECK_HIP(hipMemsetAsync(t->d_grad, 0, m->n_params * sizeof(float), st));
+    const float *x[2] = {d_xH, d_xP};
+    for (int b = 0; b < 2; ++b) {
+        TrainIO tio{t->d_acts + b * nact, d_drop_tcn ? d_drop_tcn + b * ndrop : nullptr, t->d_pre, t->d_upre + b * nupre, 0};
+        const int rc = launch_forward(m->trunk[b], x[b], N, t->d_scratch_out, nullptr, &tio, st, 0, 0, 0, 1);
+        if (rc) return rc;
+    }
+    int rc = launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats, t->d_pre,
+                                 t->d_grad, 0, st);
+    if (rc) return rc;
+    const Offsets off = offsets(m);
+    HeadsArgs ha;
+    ha.N = N, ha.D = m->D, ha.NH = m->NH, ha.n_classes = m->cfg.n_classes, ha.n_heads = m->n_heads, ha.out_dim = m->out_dim;
+    for (int i = 0; i < kMaxHeads; ++i) {
+        ha.head_odim[i] = m->head_odim[i], ha.head_sigmoid[i] = m->head_sigmoid[i];
+        ha.goff_head[i] = off.head[i];
+    }
+    for (int i = 0; i <= kMaxHeads; ++i) ha.lw[i] = 1.0f;
+    if (h_loss_weights)
+        for (int i = 0; i <= m->n_heads; ++i) ha.lw[i] = h_loss_weights[i];
+    ha.goff_c3b = off.c3_b;
+    ha.ext_losses = 1;
+    size_t hpo = 0;
+    for (int i = 0; i < m->n_heads; ++i) {
+        ha.hp_off[i] = hpo;
+        hpo += head_tail_floats(m, i);
+    }
+    rc = launch_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bnstat, d_losses,
+                            reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
+    if (rc) return rc;
+    BwdArgs ba;
+    ba.gq = t->d_gq;
+    ba.split3 = 1;
+    if (const char *ev = getenv("SMH_BWD_SPLIT")) ba.split3 = atoi(ev) != 0;
+    ba.N = N, ba.T = T, ba.F = m->cfg.n_feat, ba.n_blocks = m->n_blocks, ba.n_dil = m->cfg.n_dilations;
+    ba.use_wt = 1;
+    ba.stamps = 0;
+    ba.D = m->D, ba.NH = m->NH, ba.n_classes = m->cfg.n_classes, ba.n_heads = m->n_heads, ba.off = off;
+    hipLaunchKernelGGL(l2_penalty_kernel, dim3(m->n_heads * kL2Chunks), dim3(256), 0, st, ba, m->d_flat, d_losses + m->n_heads + 3,
+                       t->d_l2part, reinterpret_cast<unsigned *>(t->d_l2part + kMaxHeads * kL2Chunks));
+    rc = smh::launch_status("l2_penalty_kernel");
+    if (rc) return rc;
+    rc = launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats, t->d_dpre,
+                             t->d_grad, 1, st);
+    if (rc) return rc;
+    for (int b = 0; b < 2; ++b) {
+        BwdArgs bb = ba;
+        bb.D = half;
+        if (b == 1) bb.off.w0_k += off.trunk_p, bb.off.w0_b += off.trunk_p, bb.off.blk0 += off.trunk_p;
+        const float *gt = fusion_gt(m, t->max_batch, t->d_fusion, N, b);
+        const float *drop = d_drop_tcn ? d_drop_tcn + b * ndrop : nullptr;
+        const dim3 grid((N + kMG - 1) / kMG);
+        if (short_ok) {
+            auto kern = tcn_backward_mfma_kernel<true, kMfmaMaxT>;
+            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
+            hipLaunchKernelGGL(kern, grid, dim3(kMThreads), lds_m, st, bb, x[b], m->d_flat, t->d_acts + b * nact, drop, t->d_dpre,
+                               t->d_grad, RPm, (const float *)(t->d_upre + b * nupre), gt);
+        } else {
+            auto kern = tcn_backward_mfma_kernel<false, kMfmaLongT>;
+            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_long));
+            hipLaunchKernelGGL(kern, grid, dim3(kMThreads), lds_long, st, bb, x[b], m->d_flat, t->d_acts + b * nact, drop, t->d_dpre,
+                               t->d_grad, RPm, (const float *)(t->d_upre + b * nupre), gt);
+        }
+        rc = smh::launch_status("tcn_backward_mfma_kernel");
+        if (rc) return rc;
+    }
+    return det_finalize(t, st);
 }

@@ -21,6 +21,9 @@ FEATS = {
     "HarmPercSpec": (False, False),
     "LogHarmPercSpec": (False, True),
 }
+# One-half feature names (the intermediate-fusion driver, Intermediate_Fusion_Results.py:704-706) -> their '*HarmPercSpec' sibling:
+# get_featuregram computes the same H||P featuregram for them (lib/preprocessing.py:404-444); get_feature_patches keeps one half.
+HALF_FEATS = {h + t: h + "HarmPercSpec" for h in ("Mel", "LogMel", "", "Log") for t in ("HarmSpec", "PercSpec")}
 
 
 @dataclass(frozen=True)
@@ -37,8 +40,9 @@ class FrontendConfig:
     @staticmethod
     def from_params(PARAMS, n_fft, n_mels, featName, fs=16000):
         """Build from the reference's PARAMS dict (Proposed_Work_Results.py:723-807)."""
+        featName = HALF_FEATS.get(featName, featName)
         if featName not in FEATS:
-            raise ValueError("featName %r is not one of the HPSS feature names %s" % (featName, sorted(FEATS)))
+            raise ValueError("featName %r is not one of the HPSS feature names %s" % (featName, sorted(FEATS) + sorted(HALF_FEATS)))
         use_mel, log = FEATS[featName]
         model = PARAMS["Model"]
         return FrontendConfig(

@@ -457,6 +457,43 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
             yield batchData, lab['3C']
 
 
+def harm_perc_sibling(featName):
+    """'LogMelHarmSpec' / 'LogMelPercSpec' -> 'LogMelHarmPercSpec' (likewise Mel / Log / plain): the featuregram get_featuregram
+    computes for a one-half feature name (lib/preprocessing.py:404-444)."""
+    for tail in ("HarmPercSpec", "HarmSpec", "PercSpec"):
+        if featName.endswith(tail):
+            return featName[: -len(tail)] + "HarmPercSpec"
+    raise ValueError("featName %r is not a harmonic / percussive feature name" % (featName,))
+
+
+def fusion_generator(PARAMS, folder, file_list, batchSize, **kwargs):
+    """Two-input batch generator of the intermediate-fusion driver (Intermediate_Fusion_Results.py:100-330): yields
+    ({'harm_input': x_H, 'perc_input': x_P}, labels), x_H / x_P (rows, W, F / 2) time-major -- the harmonic and percussive halves of
+    the patches `generator` builds from the H||P featuregram (PARAMS['featName'][Model] may name either half or the pair: each file's
+    featuregram is computed once, both halves are cut from it, each standardised on its own as get_feature_patches does).  Labels
+    and SMR targets as `generator` (the reference takes them from the H side; here both halves come from the same files).  Noise
+    augmentation: ONE draw N(0, scale) added to both inputs (:290-293).  Other arguments as for `generator`."""
+    model = PARAMS['Model']
+    if 'MTL' not in model:
+        raise ValueError("fusion_generator: the intermediate-fusion model is an MTL model (PARAMS['Model'] = %r)" % (model,))
+    inner = dict(PARAMS)
+    inner['featName'] = dict(PARAMS['featName'])
+    inner['featName'][model] = harm_perc_sibling(PARAMS['featName'][model])
+    inner['data_augmentation_with_noise'] = False
+    rng = np.random
+    for batchData, lab in generator(inner, folder, file_list, batchSize, **kwargs):
+        half = batchData.shape[2] // 2
+        if isinstance(batchData, np.ndarray):
+            xh, xp = np.ascontiguousarray(batchData[:, :, :half]), np.ascontiguousarray(batchData[:, :, half:])
+        else:
+            xh, xp = batchData[:, :, :half].contiguous(), batchData[:, :, half:].contiguous()
+        if PARAMS['data_augmentation_with_noise']:
+            zeros = np.zeros_like(xh) if isinstance(xh, np.ndarray) else xh.new_zeros(xh.shape)
+            noise = batching.noise_augmentation(zeros, rng)  # one scale, one draw, shared by both inputs
+            xh, xp = xh + noise, xp + noise
+        yield {'harm_input': xh, 'perc_input': xp}, lab
+
+
 def test_file_wise_generator(PARAMS, file_name_sp, file_name_mu, target_dB, featuregram_fn=None, patches_fn=None):
     """All patches of ONE test file + their one-hot labels (Proposed_Work_Results.py:459-496).  The patch shift is the
     reference's hard-coded 68, not PARAMS['W_shift'].  Device path: float32 tensor (nP, W, 2F); with the per-file callables

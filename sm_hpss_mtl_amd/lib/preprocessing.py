@@ -172,8 +172,8 @@ def get_featuregram(PARAMS, classname, feature_opDir, fName_path_sp, fName_path_
     cache = feature_cache_path(feature_opDir, classname, fName_path_sp, fName_path_mu, target_dB)
     if os.path.exists(cache):
         return np.load(cache, allow_pickle=False)
-    if featName not in _fe.FEATS:
-        raise ValueError("featName %r: only the HPSS features %s are on the built path" % (featName, sorted(_fe.FEATS)))
+    if featName not in _fe.FEATS and featName not in _fe.HALF_FEATS:
+        raise ValueError("featName %r: only the HPSS features %s are on the built path" % (featName, sorted(_fe.FEATS) + sorted(_fe.HALF_FEATS)))
     if classname == 'speech_music':
         Xin_sp, fs = load_and_preprocess_signal(fName_path_sp, PARAMS['Tw'], PARAMS['Ts'])
         Xin_mu, fs = load_and_preprocess_signal(fName_path_mu, PARAMS['Tw'], PARAMS['Ts'])

@@ -1,5 +1,6 @@
 """Counterpart of lib/proposed_architectures.py for the hot path: `get_Lemaire_MTL_model` (B3_MTL) and
-`get_Lemaire_Cascaded_MTL_model` (the same TCN with cascaded heads).
+`get_Lemaire_Cascaded_MTL_model` (the same TCN with cascaded heads) and `get_Lemaire_MTL_intermediate_fusion_model` (two TCN
+trunks, one per half of the H||P featuregram, fused by a BatchNorm of their concatenation).
 
 Same signature and return value as the reference (proposed_architectures.py:85-91,170): a model object
 with the Keras-style surface the drivers use, and the initial learning rate 0.002.  The 5-class variant
@@ -9,7 +10,7 @@ Papakostas / Jang, row a13) are inference models (`sm_hpss_mtl_amd.cnn_models.Cn
 from __future__ import annotations
 
 from ..cnn_models import CnnMTL
-from ..model import B3MTL, CascadedMTL
+from ..model import B3MTL, CascadedMTL, FusionMTL
 
 
 def get_Lemaire_MTL_model(TR_STEPS, N_MELS=120, n_classes=3, patch_size=68, loss_weights=None, seed=None, tcn_block="2.3"):
@@ -27,6 +28,15 @@ def get_Lemaire_Cascaded_MTL_model(TR_STEPS, N_MELS=120, n_classes=3, patch_size
     get_Lemaire_MTL_model ("2.8": inference only)."""
     model = CascadedMTL(n_feat=N_MELS, patch_size=patch_size, n_classes=n_classes, TR_STEPS=TR_STEPS, seed=seed,
                         tcn_block=tcn_block)
+    return model, model.initial_learning_rate
+
+
+def get_Lemaire_MTL_intermediate_fusion_model(TR_STEPS, N_MELS=120, n_classes=3, patch_size=68, seed=None):
+    """proposed_architectures.py:327-420 -> (model, 0.002): inputs 'harm_input' / 'perc_input' (patch_size, N_MELS) each, two
+    independent TCN trunks ('tcn_initial_conv_H' / '_P', one build-time dropout rate), BatchNormalization of the concatenated
+    flattened trunks ('intermediate_fusion_lyr'), then B3_MTL's '3C' and MTL heads; compiled like B3_MTL (bce / bce / mse / cce,
+    l2(0.01) on the Dense(16) kernels, SGD(momentum 0.9, clipnorm 1) on ExponentialDecay(0.002, 3 * TR_STEPS, 0.1))."""
+    model = FusionMTL(n_feat=N_MELS, patch_size=patch_size, n_classes=n_classes, TR_STEPS=TR_STEPS, seed=seed)
     return model, model.initial_learning_rate
 
 

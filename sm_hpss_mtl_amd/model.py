@@ -10,6 +10,8 @@ Weights are kept on the host as float32 numpy arrays in CANONICAL order (Keras a
                            out kernel (16, odim), out bias
   (CascadedMTL: heads S, M, R; S and M carry cat_bn gamma, beta, moving_mean, moving_variance (18 each) between their
    moving_variance and an out kernel of shape (18, 1))
+  (FusionMTL: two trunks 'tcn_H/...' and 'tcn_P/...' in place of 'tcn/...', then the fused BatchNorm 'fusion_bn' gamma, beta,
+   moving_mean, moving_variance (2*T*32 each); '3C' and the heads read the 2*T*32 fused features)
 and uploaded (re-packed into MFMA operand order by libsmh) whenever they change.
 """
 from __future__ import annotations
@@ -26,7 +28,7 @@ from .persistence import ModelSurfaceMixin
 from .training import TrainingMixin
 
 
-HEADS_MTL, HEADS_CASCADED = 0, 1  # include/smh.h: SMH_HEADS_MTL / SMH_HEADS_CASCADED
+HEADS_MTL, HEADS_CASCADED, HEADS_FUSION = 0, 1, 2  # include/smh.h: SMH_HEADS_MTL / SMH_HEADS_CASCADED / SMH_HEADS_FUSION
 CAT = 18  # cascaded heads: width of concat[Dropout(16) of S or M, R's two outputs]
 
 
@@ -34,7 +36,7 @@ def head_spec(n_classes: int, heads: int = HEADS_MTL):
     """(name, out_dim, activation) of the auxiliary heads in Keras output order
     (proposed_architectures.py:25-80,154; 5_class_classification.py:150-215,286).  The cascaded model
     (cascade_MTL_modifications, :175-234) has S, M, R[2] whatever n_classes is."""
-    if n_classes == 5 and heads == HEADS_MTL:
+    if n_classes == 5 and heads != HEADS_CASCADED:  # (the intermediate-fusion model has MTL_modifications' heads)
         return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("N", 1, "sigmoid"), ("R", 3, "linear")]
     return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("R", 2, "linear")]
 
@@ -43,8 +45,25 @@ def weight_spec(n_feat, patch_size, n_classes, nb_filters=32, kernel_size=3, nb_
                 heads=HEADS_MTL):
     """Ordered (name, shape, fan_in, fan_out|None) in canonical order; fan_out None -> not glorot.
     block_variant 0: the keras-tcn 2.3.x block; 1: the two-convolution block of keras-tcn >= 2.8 (include/smh.h).
-    heads HEADS_CASCADED: S and M carry the concatenation BatchNorm 'cat_bn' (18) and an out kernel (18, 1)."""
+    heads HEADS_CASCADED: S and M carry the concatenation BatchNorm 'cat_bn' (18) and an out kernel (18, 1).
+    heads HEADS_FUSION: two trunks 'tcn_H' / 'tcn_P' (n_feat = the per-branch width), the fused BatchNorm 'fusion_bn' over
+    D = 2 * patch_size * nb_filters features, then '3C' and the MTL heads on D inputs."""
     Cf, D = nb_filters, patch_size * nb_filters
+    if heads == HEADS_FUSION:
+        if block_variant != 0:
+            raise ValueError("the intermediate-fusion model is built for the keras-tcn 2.3.x block only")
+        spec = []
+        for t in ("tcn_H", "tcn_P"):
+            spec += [(t + n[3:], shp, fi, fo) for n, shp, fi, fo in
+                     weight_spec(n_feat, patch_size, n_classes, nb_filters, kernel_size, nb_stacks, n_dil) if n.startswith("tcn/")]
+        D = 2 * D
+        spec += [("fusion_bn/gamma", (D,), 1, None), ("fusion_bn/beta", (D,), 0, None),
+                 ("fusion_bn/moving_mean", (D,), 0, None), ("fusion_bn/moving_variance", (D,), 1, None)]
+        spec += [(n, shp if n != "3C/kernel" and not n.endswith("/dense/kernel") else (D,) + tuple(shp[1:]),
+                  D if (n == "3C/kernel" or n.endswith("/dense/kernel")) else fi, fo)
+                 for n, shp, fi, fo in weight_spec(n_feat, patch_size, n_classes, nb_filters, kernel_size, nb_stacks, n_dil)
+                 if not n.startswith("tcn/")]
+        return spec
     spec = []
     if block_variant == 0:
         spec = [("tcn/initial_conv/kernel", (1, n_feat, Cf), n_feat, Cf), ("tcn/initial_conv/bias", (Cf,), 0, None)]
@@ -213,8 +232,10 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
             "tcn_block": self.tcn_block}})
 
     def summary(self, print_fn=print):
-        print_fn("Model: %s (Lemaire et al. TCN + %s heads), input (None, %d, %d)"
-                 % (self.CLASS_NAME, "cascaded MTL" if self.HEADS == HEADS_CASCADED else "MTL", self.patch_size, self.n_feat))
+        kind = {HEADS_CASCADED: "cascaded MTL", HEADS_FUSION: "intermediate-fusion MTL"}.get(self.HEADS, "MTL")
+        inputs = "2 x " if self.HEADS == HEADS_FUSION else ""
+        print_fn("Model: %s (Lemaire et al. TCN + %s heads), input %s(None, %d, %d)"
+                 % (self.CLASS_NAME, kind, inputs, self.patch_size, self.n_feat))
         for name, shape, _, _ in self._spec:
             print_fn("  %-40s %-18s %d" % (name, str(tuple(shape)), int(np.prod(shape))))
         print_fn("Total params: %d" % self.count_params())
@@ -357,3 +378,144 @@ class CascadedMTL(B3MTL):
 
     HEADS = HEADS_CASCADED
     CLASS_NAME = "B3_MTL_Cascaded"
+
+
+class FusionMTL(B3MTL):
+    """`model` object of get_Lemaire_MTL_intermediate_fusion_model (lib/proposed_architectures.py:327-420): two inputs
+    'harm_input' / 'perc_input', each (N, W, n_feat) time-major, two independent keras-tcn 2.3 trunks ('tcn_initial_conv_H' /
+    '_P', one build-time spatial dropout rate, independent masks), x = BatchNormalization(concat[Flatten(trunk H), Flatten(trunk
+    P)]), then B3_MTL's '3C' and heads on x.  Outputs [S, M, (N,) R, 3C] like B3_MTL.  `x` is [x_H, x_P] or {'harm_input': x_H,
+    'perc_input': x_P}.  The same surface as B3MTL; the bf16 paths, the fused-x0 and dense file-level forwards, the keras-tcn 2.8
+    block and the single-head sub-model are B3_MTL only."""
+
+    HEADS = HEADS_FUSION
+    CLASS_NAME = "B3_MTL_Intermediate_Fusion"
+    INPUT_NAMES = ("harm_input", "perc_input")
+
+    def __init__(self, n_feat=120, patch_size=68, n_classes=3, TR_STEPS=1, loss_weights=None, seed=None, nb_filters=32,
+                 kernel_size=3, nb_stacks=3, n_dilations=8, tcn_block="2.3"):
+        if str(tcn_block) != "2.3":
+            raise ValueError("the intermediate-fusion model is built for the keras-tcn 2.3.x block (tcn_block='2.3') only")
+        super().__init__(n_feat=n_feat, patch_size=patch_size, n_classes=n_classes, TR_STEPS=TR_STEPS, loss_weights=loss_weights,
+                         seed=seed, nb_filters=nb_filters, kernel_size=kernel_size, nb_stacks=nb_stacks, n_dilations=n_dilations,
+                         tcn_block=tcn_block)
+
+    # ---- the two inputs ----
+    def _pair(self, x):
+        """[x_H, x_P] or {'harm_input': x_H, 'perc_input': x_P} -> two float32 CUDA tensors (N, W, n_feat); anything else raises."""
+        if isinstance(x, dict):
+            if set(x) != set(self.INPUT_NAMES):
+                raise ValueError("the intermediate-fusion model takes the inputs %s, got %s" % (list(self.INPUT_NAMES), sorted(x)))
+            x = [x[k] for k in self.INPUT_NAMES]
+        if not isinstance(x, (list, tuple)) or len(x) != 2:
+            raise TypeError("the intermediate-fusion model takes two inputs: [x_H, x_P] or {'harm_input': x_H, 'perc_input': x_P}")
+        out = []
+        for a in x:
+            if isinstance(a, np.ndarray):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+            if not isinstance(a, torch.Tensor):
+                raise TypeError("inputs must be numpy arrays or torch tensors, got %s" % type(a).__name__)
+            a = a.to(device="cuda", dtype=torch.float32).contiguous()
+            if a.dim() != 3 or a.shape[1] != self.patch_size or a.shape[2] != self.n_feat:
+                raise ValueError("expected each input (N, %d, %d), got %s" % (self.patch_size, self.n_feat, tuple(a.shape)))
+            out.append(a)
+        if out[0].shape[0] != out[1].shape[0]:
+            raise ValueError("harm_input has %d patches, perc_input %d" % (out[0].shape[0], out[1].shape[0]))
+        return out
+
+    def _device_input(self, x):
+        return self._pair(x)
+
+    def forward_device(self, x, out=None, trunk=None, dtype="f32"):
+        """x: [x_H, x_P] (or the dict) -> (N, out_dim) tensor [S|M|(N)|R|3C] on the device (smh_fusion_forward_f32)."""
+        if dtype != "f32":
+            raise ValueError("the intermediate-fusion model has the f32 forward only, got dtype=%r" % (dtype,))
+        if trunk is not None:
+            raise ValueError("the intermediate-fusion model has no trunk tap")
+        xh, xp = self._pair(x)
+        self._sync_weights()
+        N = xh.shape[0]
+        if out is None:
+            out = torch.empty((N, self.out_dim), dtype=torch.float32, device=xh.device)
+        if N == 0:
+            return out
+        nbytes = self.lib.smh_fusion_workspace_bytes(self._h, N)
+        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=xh.device)
+        _lib.check(self.lib.smh_fusion_forward_f32(self._h, C.c_void_p(xh.data_ptr()), C.c_void_p(xp.data_ptr()), N,
+                                                   C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()), nbytes,
+                                                   _lib.current_stream()), "smh_fusion_forward_f32")
+        return out
+
+    def forward_from_x0(self, *args, **kwargs):
+        raise ValueError("the intermediate-fusion model has no fused layer-0 path (two inputs): use forward_device")
+
+    def forward_dense(self, *args, **kwargs):
+        raise ValueError("the intermediate-fusion model has no dense file-level path: build the patches and use forward_device")
+
+    def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
+        """model.predict([x_H, x_P]) -> [S, M, (N,) R, 3C] numpy arrays (Intermediate_Fusion_Results.py)."""
+        out = self.forward_device(x, dtype=dtype)
+        self.check_status()
+        host = out.cpu().numpy()
+        return [np.ascontiguousarray(o) for o in self.split_outputs(host)]
+
+    # ---- training ----
+    def train_on_batch(self, x, y, drop_tcn="auto", drop_heads="auto", apply=True, sync=True, _only=None, _mask=None):
+        """One optimiser step (smh_fusion_train_step_f32).  drop_tcn: "auto", None, or a (2, N, n_blocks, 32) tensor of
+        SpatialDropout1D masks (trunk H, then trunk P); drop_heads as for B3MTL.  Returns [loss, <per-output losses>, 3C_accuracy]."""
+        from .training import HEAD_DROPOUT, TRAIN_ALL, _cur_stream
+        if _only is not None:
+            raise ValueError("single-output sub-models are built for the B3_MTL heads only")
+        xh, xp = self._pair(x)
+        n = xh.shape[0]
+        yt = y if (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() == 2) else self.pack_targets(y)
+        if yt.shape[0] != n:
+            raise ValueError("%d inputs but %d target rows" % (n, yt.shape[0]))
+        self._sync_weights()
+        tr = self._get_trainer(n)
+        n_blocks, n_heads = self.nb_stacks * self.n_dilations, len(self.output_names) - 1
+        if isinstance(drop_tcn, str) or isinstance(drop_heads, str):
+            from .device_rng import dropout_masks
+            n_t, n_h = 2 * n * n_blocks * 32, n * n_heads * 16  # one rate (drawn at build time), independent masks per trunk
+            masks = dropout_masks(n_t, 1.0 - self.dropout_rate, n_h, 1.0 - HEAD_DROPOUT, self._mask_seed, self._mask_calls)
+            self._mask_calls += 1
+            if isinstance(drop_tcn, str):
+                drop_tcn = masks[:n_t].view(2, n, n_blocks, 32)
+            if isinstance(drop_heads, str):
+                drop_heads = masks[n_t:].view(n, n_heads, 16)
+        if drop_tcn is not None and tuple(drop_tcn.shape) != (2, n, n_blocks, 32):
+            raise ValueError("drop_tcn must be (2, %d, %d, 32), got %s" % (n, n_blocks, tuple(drop_tcn.shape)))
+        losses = torch.empty(self._n_losses(), dtype=torch.float32, device="cuda")
+        p = lambda t: None if t is None else C.c_void_p(t.contiguous().data_ptr())  # noqa: E731
+        _lib.check(self.lib.smh_fusion_train_step_f32(tr, p(xh), p(xp), p(yt), n, p(drop_tcn), p(drop_heads),
+                                                      self._loss_weight_array(), p(losses), _cur_stream()),
+                   "smh_fusion_train_step_f32")
+        if apply:
+            self.apply_gradients(TRAIN_ALL if _mask is None else _mask)
+        if not sync:
+            return losses
+        self._check_device_status()
+        return self.losses_to_list(losses)
+
+    def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_data=None,
+            steps_per_epoch=None, validation_steps=None, initial_epoch=0, **kwargs):
+        """fit(generator of ({'harm_input', 'perc_input'} | [x_H, x_P], y), steps_per_epoch=, ...) as for B3MTL, or arrays:
+        x = [x_H, x_P] / the dict, y, batch_size (consecutive slices of the arrays, as B3MTL.fit takes them)."""
+        if y is not None:
+            if isinstance(x, dict):
+                x = [x[k] for k in self.INPUT_NAMES]
+            xh, xp = (np.asarray(a, np.float32) for a in x)
+            yl = y if isinstance(y, (list, tuple)) else ([y] if isinstance(y, np.ndarray) else [y[k] for k in self.output_names])
+            bs = batch_size or 32
+            steps_per_epoch = steps_per_epoch or int(np.ceil(len(xh) / bs))
+
+            def batches():
+                s = 0
+                while True:
+                    a = (s * bs) % len(xh)
+                    yield [xh[a:a + bs], xp[a:a + bs]], [np.asarray(t)[a:a + bs] for t in yl]
+                    s += 1
+            x, y = batches(), None
+        return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, callbacks=callbacks,
+                           validation_data=validation_data, steps_per_epoch=steps_per_epoch, validation_steps=validation_steps,
+                           initial_epoch=initial_epoch, **kwargs)

@@ -77,6 +77,8 @@ def keras_layers_to_canonical(layers, arch=None):
     M are traced as out Dense <- BatchNormalization(18) ('cat_bn') <- Concatenate <- [Dropout <- ... <- Dense(16), R].  Without
     the JSON its layers are taken in the creation order of cascade_MTL_modifications: Dense(16) R, S, M; BatchNormalization R,
     S, S's concatenation, M, M's concatenation."""
+    if "tcn_initial_conv_H" in layers and "tcn_initial_conv_P" in layers:
+        return _fusion_layers_to_canonical(layers, arch)
     convs, dense16, bns, cat_bns, named = [], [], [], [], {}
     for lname, ws in layers.items():
         arrs = list(ws.values())
@@ -168,6 +170,108 @@ def keras_layers_to_canonical(layers, arch=None):
     return out
 
 
+def _tcn_layer_to_canonical(prefix, arrs, out, n_dil=8):
+    """The weights of one keras-tcn 2.3 `TCN` layer in file order -- initial 1x1 conv (kernel, bias), then per residual block the
+    dilated conv and its 1x1 conv -- under the canonical names of trunk `prefix`."""
+    if len(arrs) < 6 or (len(arrs) - 2) % 4 or arrs[0].ndim != 3:
+        raise ValueError("keras weight file: TCN layer %r holds %d arrays: not (initial conv, (dilated conv, 1x1 conv) per block)"
+                         % (prefix, len(arrs)))
+    out[prefix + "/initial_conv/kernel"], out[prefix + "/initial_conv/bias"] = arrs[0], arrs[1]
+    C = arrs[0].shape[2]
+    n_blocks = (len(arrs) - 2) // 4
+    if n_blocks % n_dil:
+        raise ValueError("keras weight file: %d residual blocks is not a multiple of the 8 dilations" % n_blocks)
+    for b in range(n_blocks):
+        k1, b1, k2, b2 = arrs[2 + 4 * b: 6 + 4 * b]
+        if k1.shape[1:] != (C, C) or k2.shape != (1, C, C):
+            raise ValueError("keras weight file: %s block %d has kernels %s / %s" % (prefix, b, k1.shape, k2.shape))
+        p = "%s/s%d_d%d" % (prefix, b // n_dil, 2 ** (b % n_dil))
+        out[p + "/conv/kernel"], out[p + "/conv/bias"], out[p + "/conv1x1/kernel"], out[p + "/conv1x1/bias"] = k1, b1, k2, b2
+
+
+def _fusion_layers_to_canonical(layers, arch=None):
+    """The intermediate-fusion model (get_Lemaire_MTL_intermediate_fusion_model, :327-420) as Keras wrote it: the two TCN layers by
+    their names 'tcn_initial_conv_H' / '_P' (each holding its convolutions in creation order), the fused BatchNormalization
+    behind the Concatenate 'intermediate_fusion_lyr' (from the architecture JSON; without it: the one BatchNormalization of 2 W 32
+    features), the output layers by name, and each head's Dense(16) / BatchNormalization(16) traced up from its output as for
+    B3_MTL (without the JSON: creation order S, M, [N,] R)."""
+    out = OrderedDict()
+    _tcn_layer_to_canonical("tcn_H", list(layers["tcn_initial_conv_H"].values()), out)
+    _tcn_layer_to_canonical("tcn_P", list(layers["tcn_initial_conv_P"].values()), out)
+    named, dense16, bns, wide_bns = {}, [], [], []
+    for lname, ws in layers.items():
+        arrs = list(ws.values())
+        if not arrs or lname in ("tcn_initial_conv_H", "tcn_initial_conv_P"):
+            continue
+        if lname in ("S", "M", "N", "R", "3C"):
+            named[lname] = arrs
+        elif len(arrs) == 2 and arrs[0].ndim == 2 and arrs[0].shape[1] == 16:
+            dense16.append((lname, arrs))
+        elif len(arrs) == 4 and all(a.shape == (16,) for a in arrs):
+            bns.append((lname, arrs))
+        elif len(arrs) == 4 and all(a.ndim == 1 and a.shape == arrs[0].shape for a in arrs):
+            wide_bns.append((lname, arrs))
+        else:
+            raise ValueError("keras weight file: layer %r with shapes %s does not belong to the intermediate-fusion graph"
+                             % (lname, [a.shape for a in arrs]))
+    if "3C" not in named:
+        raise ValueError("keras weight file: no '3C' output layer")
+    D = named["3C"][0].shape[0]
+    cls, inbound = {}, {}
+    if arch is not None:
+        for L in arch["config"]["layers"]:
+            src = []
+            for node in L.get("inbound_nodes", []):
+                for ref in (node if isinstance(node, list) else []):
+                    if isinstance(ref, list) and ref and isinstance(ref[0], str):
+                        src.append(ref[0])
+            inbound[L["name"]], cls[L["name"]] = src, L["class_name"]
+        fused = [n for n, src in inbound.items() if cls.get(n) == "BatchNormalization" and src == ["intermediate_fusion_lyr"]]
+        if len(fused) != 1:
+            raise ValueError("architecture JSON: no single BatchNormalization behind 'intermediate_fusion_lyr'")
+        fbn = dict(wide_bns).get(fused[0])
+        if fbn is None:
+            raise ValueError("architecture JSON names the fused BatchNormalization %r that the weight file does not hold" % fused[0])
+    else:
+        cand = [a for _, a in wide_bns if a[0].shape == (D,)]
+        if len(cand) != 1:
+            raise ValueError("keras weight file: expected one BatchNormalization of %d features (the fused one)" % D)
+        fbn = cand[0]
+    out["fusion_bn/gamma"], out["fusion_bn/beta"], out["fusion_bn/moving_mean"], out["fusion_bn/moving_variance"] = fbn
+    out["3C/kernel"], out["3C/bias"] = named["3C"]
+    heads = [h for h in ("S", "M", "N", "R") if h in named]
+    if len(dense16) != len(heads) or len(bns) != len(heads):
+        raise ValueError("keras weight file: %d heads but %d Dense(16) / %d BatchNormalization layers" % (len(heads), len(dense16), len(bns)))
+    feeder = {}
+    for i, h in enumerate(heads):
+        if arch is None:
+            feeder[h] = (dense16[i][0], bns[i][0])
+            continue
+        cur, found = h, {}
+        for _ in range(10):  # Dense(out) <- Dropout <- Activation <- BatchNormalization <- Dense(16)
+            ups = inbound.get(cur, [])
+            if len(ups) != 1:
+                break
+            cur = ups[0]
+            if cls.get(cur) == "BatchNormalization" and "bn" not in found:
+                found["bn"] = cur
+            elif cls.get(cur) == "Dense":
+                found["dense"] = cur
+                break
+        if "bn" not in found or "dense" not in found:
+            raise ValueError("architecture JSON: cannot trace head %r back to its BatchNormalization / Dense(16)" % h)
+        feeder[h] = (found["dense"], found["bn"])
+    d16, bnd = dict(dense16), dict(bns)
+    for h in heads:
+        dn, bn = feeder[h]
+        if dn not in d16 or bn not in bnd:
+            raise ValueError("architecture JSON names layers %r / %r that the weight file does not hold" % (dn, bn))
+        out[h + "/dense/kernel"], out[h + "/dense/bias"] = d16[dn]
+        out[h + "/bn/gamma"], out[h + "/bn/beta"], out[h + "/bn/moving_mean"], out[h + "/bn/moving_variance"] = bnd[bn]
+        out[h + "/out/kernel"], out[h + "/out/bias"] = named[h]
+    return out
+
+
 def model_from_json(text, seed=None):
     """Inverse of B3MTL.to_json / CnnMTL.to_json (tensorflow.keras.models.model_from_json at the call site)."""
     d = json.loads(text)
@@ -178,6 +282,15 @@ def model_from_json(text, seed=None):
         L = {l["name"]: l for l in cfg["layers"]}
         inp = next(l for l in cfg["layers"] if l["class_name"] == "InputLayer")
         shp = inp["config"].get("batch_input_shape") or inp["config"].get("batch_shape")
+        if "intermediate_fusion_lyr" in L:  # get_Lemaire_MTL_intermediate_fusion_model: two inputs, two TCN layers
+            from .model import FusionMTL
+            if "3C" not in L or len(shp) != 3:
+                raise ValueError("model_from_json: this Keras architecture is not the intermediate-fusion graph")
+            m = FusionMTL(n_feat=int(shp[2]), patch_size=int(shp[1]), n_classes=int(L["3C"]["config"]["units"]), seed=seed)
+            tcn = L.get("tcn_initial_conv_H", {}).get("config", {})
+            if "dropout_rate" in tcn:
+                m.dropout_rate = float(tcn["dropout_rate"])
+            return m
         if "3C" not in L or len(shp) != 3:
             raise ValueError("model_from_json: this Keras architecture is not the B3_MTL graph (TCN input, '3C' output)")
         n_conv = sum(1 for l in cfg["layers"] if l["class_name"] == "Conv1D")
@@ -191,9 +304,9 @@ def model_from_json(text, seed=None):
         if rates:
             m.dropout_rate = float(rates[0])
         return m
-    if name in ("B3_MTL", "B3_MTL_Cascaded"):
-        from .model import B3MTL, CascadedMTL
-        cls = CascadedMTL if name == "B3_MTL_Cascaded" else B3MTL
+    if name in ("B3_MTL", "B3_MTL_Cascaded", "B3_MTL_Intermediate_Fusion"):
+        from .model import B3MTL, CascadedMTL, FusionMTL
+        cls = {"B3_MTL_Cascaded": CascadedMTL, "B3_MTL_Intermediate_Fusion": FusionMTL}.get(name, B3MTL)
         m = cls(n_feat=cfg["n_feat"], patch_size=cfg["patch_size"], n_classes=cfg["n_classes"], seed=seed,
                 **{k: cfg[k] for k in ("nb_filters", "kernel_size", "nb_stacks", "n_dilations", "tcn_block") if k in cfg})
         if "dropout_rate" in cfg:  # drawn at build time by the reference (proposed_architectures.py:136): part of the architecture

@@ -227,7 +227,7 @@ class TrainingMixin:
         if dtype == "bf16" and self._TRAINER_API[0] != "smh_trainer_create":
             raise ValueError("train_dtype='bf16' exists for the B3_MTL trainer only")
         if dtype == "bf16" and getattr(self, "HEADS", 0) != 0:
-            raise ValueError("train_dtype='bf16' exists for the B3_MTL heads only; the cascaded model trains in f32")
+            raise ValueError("train_dtype='bf16' exists for the B3_MTL heads only; the cascaded and intermediate-fusion models train in f32")
         if dtype == "bf16":  # the trainer is created at the first step: refuse a model the bf16 forward cannot run now
             _lib.check(self.lib.smh_model_check_train_dtype(self._h, 1), "train_dtype='bf16'")
         self._train_dtype = dtype
@@ -459,9 +459,7 @@ class TrainingMixin:
         l2 = float(self._l2_penalty())  # the weights do not change while evaluating
 
         def one(bx, by, weight_of):
-            if isinstance(bx, np.ndarray):
-                bx = torch.from_numpy(np.ascontiguousarray(bx, dtype=np.float32))
-            out = self.forward_device(bx.to(device="cuda", dtype=torch.float32))
+            out = self.forward_device(self._device_input(bx))
             tgt = by if (isinstance(by, torch.Tensor) and by.is_cuda and by.dim() == 2) else self.pack_targets(by)
             if tgt.shape[0] != out.shape[0]:
                 raise ValueError("%d inputs but %d target rows" % (out.shape[0], tgt.shape[0]))
@@ -480,6 +478,12 @@ class TrainingMixin:
                 cnt += one(*next(x), weight)
         self.check_status()  # one synchronisation for the whole pass; a device-side give-up raises here
         return sums.cpu().numpy(), cnt  # already in metrics order: [loss, <per-output losses>, 3C_accuracy]
+
+    def _device_input(self, bx):
+        """A batch's input as forward_device takes it (the fusion model: two inputs)."""
+        if isinstance(bx, np.ndarray):
+            bx = torch.from_numpy(np.ascontiguousarray(bx, dtype=np.float32))
+        return bx.to(device="cuda", dtype=torch.float32)
 
     def _check_device_status(self):
         """Raise if a kernel of this model set the device error word (B3_MTL: smh_model_status); models without one: nothing."""
@@ -543,7 +547,8 @@ class TrainingMixin:
                 return
             main = torch.cuda.current_stream()
             main.wait_event(ev)
-            vals = [bx_] + (list(by_.values()) if isinstance(by_, dict) else list(by_) if isinstance(by_, (list, tuple)) else [by_])
+            xs_ = list(bx_.values()) if isinstance(bx_, dict) else list(bx_) if isinstance(bx_, (list, tuple)) else [bx_]
+            vals = xs_ + (list(by_.values()) if isinstance(by_, dict) else list(by_) if isinstance(by_, (list, tuple)) else [by_])
             for t in vals:
                 if isinstance(t, torch.Tensor) and t.is_cuda:
                     t.record_stream(main)
