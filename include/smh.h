@@ -53,7 +53,25 @@ const char *smh_last_error(void);
 int smh_version(void);
 int smh_device_count(void); /* 0 when no HIP device is visible */
 
-int smh_ctx_create(const smh_frontend_cfg *cfg, smh_ctx **out);
+int smh_ctx_create(const smh_frontend_cfg *cfg, smh_ctx **out); /* = smh_ctx_create_ex(cfg, SMH_STFT_F32, out) */
+/* STFT precision of a context.  Everything after the STFT (medians, masks, mel, dB, scaler, patches) reads the same f32 S in
+ * both modes; only how |S| is computed differs.  smh_stft_mag_f32, smh_frontend_f32 (the streaming route included) and
+ * smh_frontend_ragged_f32 dispatch on it.
+ *   SMH_STFT_F32 (default): f32 FFT, |z| on the hardware square root.  |S| is within 1e-5 of max|S| of the reference's; the
+ *                 last bits of small bins differ.  The faster mode.
+ *   SMH_STFT_F64: x[n] = w64[n] * (double)y[t*hop + n] with the f64 periodic Hann window, an f64 FFT with f64 twiddles from
+ *                 exactly reduced angles, Re and Im rounded once to f32 (nearest even), then numpy's complex64 magnitude
+ *                 l = max(|re|, |im|), r = min(..) / l, |z| = l * sqrtf(fmaf(r, r, 1)) (0 when l = 0), in IEEE f32.
+ *                 |S| equals np.abs(librosa.core.stft(y, n_fft, win_length, hop, center=False)) (float64 rfft -> complex64
+ *                 -> np.abs) bit for bit on (practically) every bin: the f64 transform's summation order does not survive
+ *                 the rounding to complex64.  The exception: bins more than ~100 dB below their frame's maximum (near-pure
+ *                 tones).  There the f64 rounding noise of any order but pocketfft's reaches the f32 ulp; such bins are within
+ *                 1e-11 of the frame's maximum.  The f64 window and twiddle tables exist only in such a context; an n_fft
+ *                 whose f64 frame does not fit the kernel's LDS is rejected here (SMH_E_INVALID), never run in f32.
+ * Any other stft_precision: SMH_E_INVALID. */
+#define SMH_STFT_F32 0
+#define SMH_STFT_F64 1
+int smh_ctx_create_ex(const smh_frontend_cfg *cfg, int stft_precision, smh_ctx **out);
 void smh_ctx_destroy(smh_ctx *ctx);
 /* rows of one half (harmonic or percussive) of the featuregram: n_mels, or K = 1+n_fft/2 */
 int smh_ctx_feat_rows(const smh_ctx *ctx);
@@ -71,7 +89,8 @@ int smh_num_patches(int T, int W, int shift);
 int smh_patch_start(int T, int W, int shift, int p);
 
 /* ---- a1: np.abs(librosa.core.stft(y, n_fft, win_length, hop_length, center=False)) ----------
- * lib/preprocessing.py:407,417,429,439.  d_audio (B, n_samples) -> d_S (B, K, T).               */
+ * lib/preprocessing.py:407,417,429,439.  d_audio (B, n_samples) -> d_S (B, K, T).  In the context's STFT precision
+ * (smh_ctx_create_ex): f32, or f64 with a bit-exact |S|.                                                                   */
 int smh_stft_mag_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, float *d_S, void *stream);
 
 /* ---- a2: the two median filters inside librosa.decompose.hpss (preprocessing.py:408,418,...) --

@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMH_LIBSMH_PATH") or os.path.join(HERE, "libsmh.so")
 
 SMH_OK, SMH_E_INVALID, SMH_E_HIP, SMH_E_WORKSPACE, SMH_E_DEVICE = 0, -1, -2, -3, -4
+SMH_STFT_F32, SMH_STFT_F64 = 0, 1  # smh_ctx_create_ex: stft_precision
 
 
 class FrontendCfg(C.Structure):
@@ -36,6 +37,7 @@ SIGNATURES = {
     "smh_version": (_i, []),
     "smh_device_count": (_i, []),
     "smh_ctx_create": (_i, [C.POINTER(FrontendCfg), C.POINTER(_vp)]),
+    "smh_ctx_create_ex": (_i, [C.POINTER(FrontendCfg), _i, C.POINTER(_vp)]),
     "smh_ctx_destroy": (None, [_vp]),
     "smh_ctx_feat_rows": (_i, [_vp]),
     "smh_ctx_mel_basis": (_i, [_vp, _vp]),

@@ -68,6 +68,13 @@ struct smh_ctx {
     float *d_window;   // (n_fft) periodic Hann, centre-padded
     float2 *d_twM;     // (M)   exp(-2 pi i j / M)
     float2 *d_tw2M;    // (M+1) exp(-2 pi i k / (2M))
+    // STFT precision (smh_ctx_create_ex): 0 = f32 kernels of smh_stft.hip, 1 = stft_f64_kernel (smh_stft_f64.hip); the f64 tables
+    // exist only in f64 contexts
+    int stft_f64;
+    int stft64_frames;    // frames per LDS pass of stft_f64_kernel
+    double *d_window64;   // (n_fft) periodic Hann as oracle.frontend.hann_window, zero-padded centred
+    double2 *d_twM64;     // (M)   exp(-2 pi i j / M)
+    double2 *d_tw2M64;    // (M+1) exp(-2 pi i k / (2M))
     // mel filterbank, CSR by filter row
     int n_mels;
     int *d_mel_start;  // (n_mels) first bin with non-zero weight

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "smh_common.h"
+#include "smh_rag.h"
 
 namespace smh {
 
@@ -150,8 +151,62 @@ static hipError_t upload(T **d, const std::vector<T> &h) {
     return hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-extern "C" int smh_ctx_create(const smh_frontend_cfg *cfg, smh_ctx **out) {
+// exp(-2 pi i n / N) in f64 from the exactly reduced angle: n mod N is split into quarter turns and a remainder folded into
+// [0, pi/4], so that the quarter and half turns are exact and e.g. W^n and W^(N-n) are exact conjugates
+static double2 cis_neg(long long n, long long N) {
+    n %= N;
+    if (n < 0) n += N;
+    const long long q = 4 * n / N, r = 4 * n - q * N;  // 2 pi n / N = (pi / 2) (q + r / N)
+    double c, s;
+    if (2 * r <= N) {
+        const double phi = (M_PI / 2) * (double)r / (double)N;
+        c = std::cos(phi), s = std::sin(phi);
+    } else {
+        const double psi = (M_PI / 2) * (double)(N - r) / (double)N;
+        c = std::sin(psi), s = std::cos(psi);
+    }
+    double cq, sq;  // rotate (c, s) by q quarter turns
+    switch (q) {
+        case 0: cq = c, sq = s; break;
+        case 1: cq = -s, sq = c; break;
+        case 2: cq = -c, sq = -s; break;
+        default: cq = s, sq = -c; break;
+    }
+    return make_double2(cq, -sq);
+}
+
+// the f64 tables of a stft_precision 1 context (smh_stft_f64.hip)
+static int build_f64_tables(smh_ctx *c) {
+    const int n_fft = c->cfg.n_fft, wl = c->cfg.win_length;
+    c->stft64_frames = smh_stft::f64_frames(c->M);
+    if (c->stft64_frames < 1)
+        return smh::set_error(SMH_E_INVALID, "stft_precision f64: n_fft=%d does not fit the f64 STFT's LDS (%zu bytes for one frame)",
+                              n_fft, smh_stft::f64_lds_bytes(c->M, 1));
+    // oracle.frontend.hann_window = scipy get_window('hann', wl, fftbins=True): 0.5 + 0.5 cos(linspace(-pi, pi, wl + 1))[:-1],
+    // zero-padded to n_fft with (n_fft - wl) // 2 in front
+    std::vector<double> win(n_fft, 0.0);
+    const int lpad = (n_fft - wl) / 2;
+    const double step = (M_PI - (-M_PI)) / (double)wl;
+    for (int n = 0; n < wl; ++n) {
+        const double fac = (double)n * step;
+        win[lpad + n] = 0.5 + 0.5 * std::cos(fac + (-M_PI));
+    }
+    std::vector<double2> twM(c->M), tw2M(c->M + 1);
+    for (int j = 0; j < c->M; ++j) twM[j] = cis_neg(j, c->M);
+    for (int k = 0; k <= c->M; ++k) tw2M[k] = cis_neg(k, 2ll * c->M);
+    hipError_t e = upload(&c->d_window64, win);
+    if (e == hipSuccess) e = upload(&c->d_twM64, twM);
+    if (e == hipSuccess) e = upload(&c->d_tw2M64, tw2M);
+    if (e != hipSuccess) return smh::set_error(SMH_E_HIP, "smh_ctx_create_ex: f64 table upload failed: %s", hipGetErrorString(e));
+    return SMH_OK;
+}
+
+extern "C" int smh_ctx_create(const smh_frontend_cfg *cfg, smh_ctx **out) { return smh_ctx_create_ex(cfg, SMH_STFT_F32, out); }
+
+extern "C" int smh_ctx_create_ex(const smh_frontend_cfg *cfg, int stft_precision, smh_ctx **out) {
     SMH_REQUIRE(cfg && out, "smh_ctx_create: null argument");
+    SMH_REQUIRE(stft_precision == SMH_STFT_F32 || stft_precision == SMH_STFT_F64,
+                "stft_precision must be %d (f32) or %d (f64), got %d", SMH_STFT_F32, SMH_STFT_F64, stft_precision);
     SMH_REQUIRE(cfg->n_fft >= 8 && cfg->n_fft % 2 == 0, "n_fft must be even and >= 8 (got %d)", cfg->n_fft);
     SMH_REQUIRE(cfg->win_length >= 1 && cfg->win_length <= cfg->n_fft, "win_length must be in [1, n_fft]");
     SMH_REQUIRE(cfg->hop >= 1, "hop must be >= 1");
@@ -279,6 +334,14 @@ extern "C" int smh_ctx_create(const smh_frontend_cfg *cfg, smh_ctx **out) {
         smh_ctx_destroy(c);
         return smh::set_error(SMH_E_HIP, "smh_ctx_create: table upload failed: %s", hipGetErrorString(e));
     }
+    c->stft_f64 = stft_precision == SMH_STFT_F64 ? 1 : 0;
+    if (c->stft_f64) {
+        const int rc = build_f64_tables(c);
+        if (rc) {
+            smh_ctx_destroy(c);
+            return rc;
+        }
+    }
     *out = c;
     return SMH_OK;
 }
@@ -288,6 +351,9 @@ extern "C" void smh_ctx_destroy(smh_ctx *c) {
     (void)hipFree(c->d_window);
     (void)hipFree(c->d_twM);
     (void)hipFree(c->d_tw2M);
+    (void)hipFree(c->d_window64);
+    (void)hipFree(c->d_twM64);
+    (void)hipFree(c->d_tw2M64);
     (void)hipFree(c->d_feat_plan);
     (void)hipFree(c->d_mel_start);
     (void)hipFree(c->d_mel_count);

@@ -45,6 +45,13 @@ int rag_frames(const smh_ctx *ctx, bool aligned8);
 int launch_rag(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items,
                int n_items, bool aligned8, hipStream_t st);
 constexpr int kRagFrames = 20;  // (the equal-length path splits 98 frames into 5 x 20 as well)
+// the f64 STFT of smh_stft_f64.hip: LDS bytes and frames per pass (0: n_fft too large) of a context, its item size, its launches
+size_t f64_lds_bytes(int M, int tt);
+int f64_frames(int M);
+int rag_frames_f64();
+int launch_rag_f64(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items,
+                   int n_items, hipStream_t st);
+int launch_f64(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, float *d_S, hipStream_t st);
 }  // namespace smh_stft
 
 namespace smh_median {

@@ -559,13 +559,17 @@ constexpr int kRagFramesGeneric = 16;
 }  // namespace
 
 namespace smh_stft {
-int rag_frames(const smh_ctx *ctx, bool aligned8) { return stft400_ok(ctx) && aligned8 ? kRagFrames : kRagFramesGeneric; }
+int rag_frames(const smh_ctx *ctx, bool aligned8) {
+    if (ctx->stft_f64) return rag_frames_f64();
+    return stft400_ok(ctx) && aligned8 ? kRagFrames : kRagFramesGeneric;
+}
 
 // One launch for clips of different lengths (smh_rag.h).  A frame's transform does not depend on the frames it shares a workgroup
 // with, so every clip gets the bits smh_stft_mag_f32 gives it alone.
 int launch_rag(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items,
                int n_items, bool aligned8, hipStream_t st) {
     if (n_items <= 0) return SMH_OK;
+    if (ctx->stft_f64) return launch_rag_f64(ctx, d_audio, d_S, d_clips, d_items, n_items, st);
     const unsigned grid = (unsigned)(8 * (((long long)n_items + 7) / 8));
     if (stft400_ok(ctx) && aligned8) {
         const int F = kRagFrames;
@@ -596,6 +600,7 @@ extern "C" int smh_stft_mag_f32(const smh_ctx *ctx, const float *d_audio, int B,
     const int T = smh_num_frames(n_samples, ctx->cfg.n_fft, ctx->cfg.hop);
     SMH_REQUIRE(T >= 1, "smh_stft_mag_f32: clip of %d samples is shorter than n_fft=%d", n_samples, ctx->cfg.n_fft);
     if (B == 0) return SMH_OK;
+    if (ctx->stft_f64) return smh_stft::launch_f64(ctx, d_audio, B, n_samples, T, d_S, (hipStream_t)stream);
     // n_fft = 400 with 8-byte aligned frames: the specialised 8 x 25 kernel (SMH_STFT_GENERIC=1 forces the generic one)
     // (an odd clip length only matters for where the NEXT clip starts: a single clip keeps the specialised kernel)
     if (stft400_ok(ctx) && ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0) {

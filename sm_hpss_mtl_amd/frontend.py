@@ -24,6 +24,8 @@ FEATS = {
 # One-half feature names (the intermediate-fusion driver, Intermediate_Fusion_Results.py:704-706) -> their '*HarmPercSpec' sibling:
 # get_featuregram computes the same H||P featuregram for them (lib/preprocessing.py:404-444); get_feature_patches keeps one half.
 HALF_FEATS = {h + t: h + "HarmPercSpec" for h in ("Mel", "LogMel", "", "Log") for t in ("HarmSpec", "PercSpec")}
+# FrontendConfig.stft_precision -> the C ABI's stft_precision (include/smh.h: SMH_STFT_F32 / SMH_STFT_F64)
+STFT_PRECISIONS = {"f32": _lib.SMH_STFT_F32, "f64": _lib.SMH_STFT_F64}
 
 
 @dataclass(frozen=True)
@@ -36,6 +38,13 @@ class FrontendConfig:
     l_perc: int = 11
     log_db: bool = True
     mel_sr: float = 22050.0
+    # "f32": the fast STFT (|S| within 1e-5 of max|S| of the reference's); "f64": an f64 transform whose |S| equals
+    # np.abs(librosa.core.stft(...)) bit for bit (include/smh.h: smh_ctx_create_ex).  Everything after the STFT is the same.
+    stft_precision: str = "f32"
+
+    def __post_init__(self):
+        if self.stft_precision not in STFT_PRECISIONS:
+            raise ValueError("stft_precision must be one of %s, got %r" % (sorted(STFT_PRECISIONS), self.stft_precision))
 
     @staticmethod
     def from_params(PARAMS, n_fft, n_mels, featName, fs=16000):
@@ -48,7 +57,7 @@ class FrontendConfig:
         return FrontendConfig(
             n_fft=int(n_fft), win_length=int(PARAMS["Tw"] * fs / 1000), hop=int(PARAMS["Ts"] * fs / 1000),
             n_mels=int(n_mels) if use_mel else 0, l_harm=int(PARAMS["l_harm"][model]),
-            l_perc=int(PARAMS["l_perc"][model]), log_db=log)
+            l_perc=int(PARAMS["l_perc"][model]), log_db=log, stft_precision=PARAMS.get("stft_precision", "f32"))
 
 
 def _ptr(t):
@@ -90,7 +99,7 @@ class Frontend:
         c = _lib.FrontendCfg(cfg.n_fft, cfg.win_length, cfg.hop, cfg.n_mels, cfg.l_harm, cfg.l_perc,
                              1 if cfg.log_db else 0, cfg.mel_sr)
         h = C.c_void_p()
-        _lib.check(self.lib.smh_ctx_create(C.byref(c), C.byref(h)), "smh_ctx_create")
+        _lib.check(self.lib.smh_ctx_create_ex(C.byref(c), STFT_PRECISIONS[cfg.stft_precision], C.byref(h)), "smh_ctx_create_ex")
         self._h = h
         self.K = 1 + cfg.n_fft // 2
         self.rows = self.lib.smh_ctx_feat_rows(self._h)

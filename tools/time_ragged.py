@@ -1,6 +1,7 @@
 """GPU timing of the ragged front end (smh_frontend_ragged_f32: files of DIFFERENT lengths in one call, what the reference's generators
 feed it one file at a time, Proposed_Work_Results.py:92-95, 465-474): B files of 1..MAXS seconds, featuregram + W = 68 / shift 68
-patches.  Reports files/s and seconds of audio per second, against the same amount of audio as equal-length 1 s clips in one batch."""
+patches.  Reports files/s and seconds of audio per second, against the same amount of audio as equal-length 1 s clips in one batch.
+Third argument: the STFT precision, f32 (default) or f64."""
 import os, sys, time
 import ctypes as C
 import numpy as np, torch
@@ -15,7 +16,9 @@ lens = [int(rng.uniform(1.0, MAXS) * 16000) // 2 * 2 for _ in range(B)]
 if os.environ.get("RAG_T_PARITY"):  # tuning: every file an even (0) or odd (1) number of frames
     par = int(os.environ["RAG_T_PARITY"])
     lens = [n if (1 + (n - 400) // 160) % 2 == par else n + 160 for n in lens]
-fe = Frontend(FrontendConfig(l_harm=21, l_perc=11))
+PREC = sys.argv[3] if len(sys.argv) > 3 else "f32"
+fe = Frontend(FrontendConfig(l_harm=21, l_perc=11, stft_precision=PREC))
+print("stft_precision", PREC, flush=True)
 offs, o = [], 0
 for n in lens:
     offs.append(o)
