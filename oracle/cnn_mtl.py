@@ -45,11 +45,21 @@ def _pad_hw(x, kh, kw, sh, sw, padding, value=0.0):
     return np.pad(x, ((0, 0), (t, b), (l, r), (0, 0)), constant_values=value)
 
 
-def conv2d(x, kernel, bias=None, strides=(1, 1), padding="valid"):
-    """x (N, H, W, Cin) float32, kernel (kh, kw, Cin, Cout) -> (N, OH, OW, Cout) float32."""
+def bf16_round(a):
+    """float32 -> the nearest bfloat16 (round to nearest, ties to even), returned as float32 (finite inputs)."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) >> 16 << 16
+    return u.astype(np.uint32).view(np.float32)
+
+
+def conv2d(x, kernel, bias=None, strides=(1, 1), padding="valid", bf16=False):
+    """x (N, H, W, Cin) float32, kernel (kh, kw, Cin, Cout) -> (N, OH, OW, Cout) float32.
+    bf16: both GEMM operands rounded to bfloat16 first (the accumulation stays float64)."""
     kh, kw, cin, cout = kernel.shape
     sh, sw = strides
     xp = _pad_hw(np.asarray(x, np.float32), kh, kw, sh, sw, padding)
+    if bf16:
+        xp, kernel = bf16_round(xp), bf16_round(kernel)
     N, H, W, _ = xp.shape
     oh, ow = (H - kh) // sh + 1, (W - kw) // sw + 1
     y = np.zeros((N, oh, ow, cout), np.float64)
@@ -96,8 +106,11 @@ def relu(x):
     return np.maximum(x, np.float32(0))
 
 
-def dense(x, w, p):
-    return b3_mtl._dense(x, w[p + "/kernel"], w[p + "/bias"])
+def dense(x, w, p, bf16=False):
+    k = w[p + "/kernel"]
+    if bf16:
+        x, k = bf16_round(x), bf16_round(k)
+    return b3_mtl._dense(x, k, w[p + "/bias"])
 
 
 # ---- weight initialisation (seeded stand-ins for the Keras initialisers; values only need to be generic) --------
@@ -157,19 +170,21 @@ def init_doukhan(seed=0, H=240, W=68, n_classes=3, randomize=True):
     return w
 
 
-def forward_doukhan(x, w, n_classes=3, return_features=False):
-    """x (N, 2F, W, 1) -> [S, M, R, 3C]   (proposed_architectures.py:448-492)."""
+def forward_doukhan(x, w, n_classes=3, return_features=False, bf16=False):
+    """x (N, 2F, W, 1) -> [S, M, R, 3C]   (proposed_architectures.py:448-492).
+    bf16=True: what smh_cnn_forward_bf16 computes -- both operands of every Conv2D / Dense GEMM rounded to bfloat16;
+    bias, BatchNorm, pooling and the heads stay float32 (the same holds for the two other networks)."""
     x = np.asarray(x, np.float32)
-    x = relu(batchnorm(conv2d(x, w["conv1/kernel"], w["conv1/bias"]), w, "bn1"))
+    x = relu(batchnorm(conv2d(x, w["conv1/kernel"], w["conv1/bias"], bf16=bf16), w, "bn1"))
     x = maxpool2d(x, (2, 2), (2, 2), "valid")
-    x = relu(batchnorm(conv2d(x, w["conv2/kernel"], w["conv2/bias"]), w, "bn2"))
-    x = relu(batchnorm(conv2d(x, w["conv3/kernel"], w["conv3/bias"]), w, "bn3"))
+    x = relu(batchnorm(conv2d(x, w["conv2/kernel"], w["conv2/bias"], bf16=bf16), w, "bn2"))
+    x = relu(batchnorm(conv2d(x, w["conv3/kernel"], w["conv3/bias"], bf16=bf16), w, "bn3"))
     x = maxpool2d(x, (2, 2), (2, 2), "same")
-    x = relu(batchnorm(conv2d(x, w["conv4/kernel"], w["conv4/bias"]), w, "bn4"))
+    x = relu(batchnorm(conv2d(x, w["conv4/kernel"], w["conv4/bias"], bf16=bf16), w, "bn4"))
     x = maxpool2d(x, (1, 12), (1, 12), "valid")
     x = x.reshape(x.shape[0], -1)
     for i in range(4):
-        x = relu(batchnorm(dense(x, w, f"fc{i + 1}"), w, f"fc{i + 1}_bn"))
+        x = relu(batchnorm(dense(x, w, f"fc{i + 1}", bf16), w, f"fc{i + 1}_bn"))
     outs = b3_mtl.mtl_heads(x, w, n_classes)
     return (outs, x) if return_features else outs
 
@@ -201,18 +216,18 @@ def init_papakostas(seed=0, H=402, W=68, n_classes=3, randomize=True, fc=4096):
     return w
 
 
-def forward_papakostas(x, w, n_classes=3, return_features=False):
-    """x (N, 2K, W, 1) -> [S, M, R, 3C]   (proposed_architectures.py:539-571)."""
+def forward_papakostas(x, w, n_classes=3, return_features=False, bf16=False):
+    """x (N, 2K, W, 1) -> [S, M, R, 3C]   (proposed_architectures.py:539-571).  LRN stays float32 under bf16."""
     x = np.asarray(x, np.float32)
-    x = relu(lrn(conv2d(x, w["conv1/kernel"], w["conv1/bias"], (2, 2), "valid")))
+    x = relu(lrn(conv2d(x, w["conv1/kernel"], w["conv1/bias"], (2, 2), "valid", bf16)))
     x = maxpool2d(x, (3, 3), (2, 2), "same")
-    x = relu(lrn(conv2d(x, w["conv2/kernel"], w["conv2/bias"], (2, 2), "valid")))
+    x = relu(lrn(conv2d(x, w["conv2/kernel"], w["conv2/bias"], (2, 2), "valid", bf16)))
     x = maxpool2d(x, (3, 3), (2, 2), "same")
-    x = relu(conv2d(x, w["conv3/kernel"], w["conv3/bias"], (1, 1), "same"))
+    x = relu(conv2d(x, w["conv3/kernel"], w["conv3/bias"], (1, 1), "same", bf16))
     x = maxpool2d(x, (3, 3), (2, 2), "same")
     x = x.reshape(x.shape[0], -1)
-    x = relu(batchnorm(dense(x, w, "fc1"), w, "fc1_bn"))
-    x = relu(batchnorm(dense(x, w, "fc2"), w, "fc2_bn"))
+    x = relu(batchnorm(dense(x, w, "fc1", bf16), w, "fc1_bn"))
+    x = relu(batchnorm(dense(x, w, "fc2", bf16), w, "fc2_bn"))
     outs = b3_mtl.mtl_heads(x, w, n_classes)
     return (outs, x) if return_features else outs
 
@@ -278,8 +293,9 @@ def mel_scale_layer(x_half, w, name, bins, t_dim=5):
     return np.tanh(np.concatenate(rows, axis=1).astype(np.float64)).astype(np.float32)
 
 
-def forward_jang(x, w, n_classes=3, n_mels=120, n_fft=512, fs=16000, return_features=False):
-    """x (N, 2K, W, 1) with K = n_fft/2 + 1 -> [S, M, R, 3C]   (proposed_architectures.py:695-747)."""
+def forward_jang(x, w, n_classes=3, n_mels=120, n_fft=512, fs=16000, return_features=False, bf16=False):
+    """x (N, 2K, W, 1) with K = n_fft/2 + 1 -> [S, M, R, 3C]   (proposed_architectures.py:695-747).  The mel-scale
+    layer stays float32 under bf16 (smh_cnn.hip runs it on the VALU)."""
     x = np.asarray(x, np.float32)
     K = n_fft // 2 + 1
     _, bins = mel_filter_bins(fs, n_fft, n_mels)
@@ -287,12 +303,12 @@ def forward_jang(x, w, n_classes=3, n_mels=120, n_fft=512, fs=16000, return_feat
                          axis=1)
     x = mel
     for i in range(3):
-        x = conv2d(x, w[f"conv{i + 1}/kernel"], w[f"conv{i + 1}/bias"], (1, 1), "same")
+        x = conv2d(x, w[f"conv{i + 1}/kernel"], w[f"conv{i + 1}/bias"], (1, 1), "same", bf16)
         x = relu(batchnorm(x, w, f"bn{i + 1}"))
         x = maxpool2d(x, (2, 2), (2, 2), "same")
     x = x.reshape(x.shape[0], -1)
-    x = relu(batchnorm(dense(x, w, "fc1"), w, "fc1_bn"))
-    x = relu(batchnorm(dense(x, w, "fc2"), w, "fc2_bn"))
+    x = relu(batchnorm(dense(x, w, "fc1", bf16), w, "fc1_bn"))
+    x = relu(batchnorm(dense(x, w, "fc2", bf16), w, "fc2_bn"))
     outs = b3_mtl.mtl_heads(x, w, n_classes)
     return (outs, (mel, x)) if return_features else outs
 

@@ -1073,6 +1073,7 @@ extern "C" int smh_cnn_train_step_f32(smh_cnn_trainer *t, const float *d_x, cons
             const size_t outf = (size_t)L.K * L.OC;
             a.ksplit = wgrad_split(mt * nt, a.ksteps, outf, t->partial_floats);
             if (const char *e = getenv("SMH_CNN_WSPLIT")) a.ksplit = std::max(1, std::min(atoi(e), a.ksteps));
+            while (a.ksplit > 1 && (size_t)a.ksplit * outf > t->partial_floats) --a.ksplit;  // a forced split too
             a.ksteps_per = (a.ksteps + a.ksplit - 1) / a.ksplit;
             a.ksplit = (a.ksteps + a.ksteps_per - 1) / a.ksteps_per;  // no empty slices
             a.y = gr + m->tensors[L.t_kernel].off, a.partial = t->d_partial;

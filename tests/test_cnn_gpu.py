@@ -133,3 +133,62 @@ def test_bf16_operand_variant(kind, H, W, N, fc):
     assert np.abs(o16b - o32b).max() < 5e-2 and np.abs(o32b - o32).max() > 0
     with pytest.raises(ValueError):
         m.forward_device(x, dtype="fp8")
+
+
+# (kind, H, W, fc, N, n_classes): passes of 64 images -- one full pass, a one-image last pass, two full + a ragged one
+CHUNK_CASES = [(k, H, W, fc, N, nc) for k, H, W, fc in (("Papakostas", 66, 40, 64), ("Jang", 514, 12, 0))
+               for N in (64, 65, 130) for nc in (3, 5)]
+
+
+@pytest.mark.parametrize("kind,H,W,fc,N,n_classes", CHUNK_CASES, ids=["%s-N%d-%dcls" % (c[0], c[4], c[5]) for c in CHUNK_CASES])
+def test_chunked_batches_and_five_class_heads(kind, H, W, fc, N, n_classes):
+    """The ragged last pass has its own split-K plan (tests/test_cnn_plans.py: Jang conv3 splits 3 ways in a full
+    pass, 4 in a one-image pass) and its own offset into the output and feature rows."""
+    _check(kind, H, W, N, n_classes=n_classes, fc=fc)
+
+
+def test_papakostas_reference_fc_width():
+    """fc_width = 4096, the reference's default (proposed_architectures.py:555-566), on a small image."""
+    m = _check("Papakostas", 66, 40, 5, fc=4096)
+    assert m.feat_dim == 4096
+
+
+# (kind, H, W, N, fc, branch); the first four are the cases of test_bf16_operand_variant, the branches are confirmed
+# on the planner's mirror by tests/test_cnn_plans.py
+BF16_CASES = [("Doukhan", 240, 68, 70, 0, "ragged-pass"), ("Doukhan", 40, 68, 3, 0, "split-k"),
+              ("Papakostas", 402, 68, 3, 128, "split-k"), ("Jang", 514, 20, 3, 0, "split-k"),
+              ("Doukhan", 64, 80, 5, 0, "empty-slice:fc1"), ("Doukhan", 240, 68, 3, 0, "empty-slice:conv3"),
+              ("Papakostas", 402, 249, 3, 64, "empty-slice:conv3"), ("Jang", 514, 1, 3, 0, "empty-slice:fc1"),
+              ("Jang", 514, 4, 3, 0, "empty-slice:fc1"), ("Doukhan", 30, 68, 130, 0, "ragged-pass"),
+              ("Papakostas", 66, 40, 130, 64, "ragged-pass"), ("Jang", 514, 12, 70, 0, "ragged-pass")]
+# Measured on an MI355X, worst over BF16_CASES: features 3.79e-3 of their largest entry (Doukhan 240 x 68, N = 70; the
+# others 1.8e-7 .. 2.9e-3), outputs 1.53e-3 (Doukhan 64 x 80).  Rounding by truncation instead of to nearest even moves
+# the oracle's features by 1.5e-2 .. 2.3e-2 and its outputs by 6.6e-3 .. 2.6e-2 (Doukhan 40 x 68, Jang 514 x 20,
+# Papakostas 66 x 40), all inside the 3e-2 / 5e-2 of test_bf16_operand_variant; these bounds reject it.
+BF16_FEAT_TOL = 6e-3  # of the largest feature
+BF16_OUT_TOL = 3e-3   # absolute, on every output
+
+
+@pytest.mark.parametrize("kind,H,W,N,fc,branch", BF16_CASES, ids=["%s-%dx%d-N%d-%s" % (c[:4] + c[5:]) for c in BF16_CASES])
+def test_bf16_forward_vs_bf16_oracle(kind, H, W, N, fc, branch):
+    """smh_cnn_forward_bf16 against the oracle's bf16 mode: the same operands rounded the same way (round to nearest
+    even), accumulated in f64 instead of f32.  What limits the agreement is not the accumulation: an activation whose
+    f32 value differs in the last bit between the device and the oracle and sits on a bf16 rounding boundary rounds to
+    the other neighbour (a 2^-7 relative step in that operand), and the steps cascade: every later layer re-rounds
+    operands that now differ by more.  In the oracle alone, moving bn1's output of Doukhan 40 x 68 by one f32 ulp moves
+    the bf16 features by 2.4e-3 of their maximum, the level measured here -- so the bound cannot be much tighter."""
+    w, fwd = _oracle(kind, H, W, 3, fc or 64)
+    m = _model(kind, H, W, 3, fc_width=fc)
+    m.set_weights_dict(w)
+    x = np.random.default_rng(3).standard_normal((N, H, W)).astype(np.float32)
+    ref, feat_ref = fwd(x[..., None], w, 3, return_features=True, bf16=True)
+    if kind == "Jang":
+        feat_ref = feat_ref[1]
+    feats = torch.empty((N, m.feat_dim), device="cuda")
+    out = m.forward_device(torch.from_numpy(x).cuda(), features=feats, dtype="bf16")
+    got = [o.cpu().numpy() for o in m.split_outputs(out)]
+    f = feats.cpu().numpy()
+    ferr = np.abs(f - feat_ref).max() / max(np.abs(feat_ref).max(), 1e-6)
+    oerr = max(np.abs(g - r).max() for g, r in zip(got, ref))
+    print("%s %dx%d N=%d (%s): bf16 vs bf16 oracle: features %.2e of max, outputs %.2e" % (kind, H, W, N, branch, ferr, oerr))
+    assert ferr <= BF16_FEAT_TOL and oerr <= BF16_OUT_TOL

@@ -55,6 +55,23 @@ def test_lrn_vs_torch():
     assert np.max(np.abs(y - _n(ref))) <= 1e-6
 
 
+def test_bf16_round_matches_torch():
+    """The oracle's bf16 operand rounding against torch's float32 -> bfloat16 conversion (round to nearest even):
+    ties both ways, subnormals, the largest finite bf16 and the values next to it, random values of every scale."""
+    ulp = 2.0 ** -8
+    edge = [1 + ulp / 2, 1 + 1.5 * ulp, -(1 + ulp / 2), 1 + ulp / 2 + 2.0 ** -23, 1 + ulp / 2 - 2.0 ** -23,
+            2.0 ** -130, 2.0 ** -133 * 3, -(2.0 ** -149), 2.0 ** -126 * (1 + ulp / 2), 0.0, -0.0,
+            3.3895313892515355e38, 3.3961775292304e38, 3.39e38, -3.3895313892515355e38, np.finfo(np.float32).max]
+    rng = np.random.default_rng(0)
+    x = np.concatenate([np.array(edge, np.float32),
+                        (rng.standard_normal(20000) * 10.0 ** rng.uniform(-40, 38, 20000)).astype(np.float32),
+                        rng.integers(0, 2 ** 32, 20000, dtype=np.uint64).astype(np.uint32).view(np.float32)])
+    x = x[np.isfinite(x)]
+    ref = torch.from_numpy(x).to(torch.bfloat16).float().numpy()
+    got = oc.bf16_round(x)
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+
+
 def test_published_shapes_and_parameter_counts():
     assert oc.doukhan_shapes(240, 68) == (55, 1, 14080)          # SURVEY a13: flatten 14 080
     w = oc.init_doukhan(H=240, W=68)
