@@ -333,8 +333,10 @@ extern "C" int smh_fusion_forward_f32(const smh_model *m, const float *d_xH, con
     hipStream_t st = (hipStream_t)stream;
     float *tap[2] = {static_cast<float *>(d_work), static_cast<float *>(d_work) + (size_t)N * (m->D / 2)};
     const float *x[2] = {d_xH, d_xP};
+    ForwardOpts fo;
+    fo.trunk_only = 1;
     for (int b = 0; b < 2; ++b) {
-        const int rc = launch_forward(m->trunk[b], x[b], N, d_out, tap[b], nullptr, st, 0, 0, 0, 1);
+        const int rc = launch_forward(m->trunk[b], x[b], N, d_out, tap[b], nullptr, st, fo);
         if (rc) return rc;
     }
     return launch_fusion_dense(m, N, tap[0], tap[1], d_out, false, st);

@@ -132,9 +132,13 @@ int repack(smh_model *m, hipStream_t st);  // d_flat -> packed operand buffers
 int launch_forward_bf16_train(smh_model *m, const float *d_x, int N, const TrainIO *tio, hipStream_t st);  // smh_tcn_bf16.hip
 bool backward_bf16_supported(int T, int n_dil);  // smh_train_bf16.hip: the patch geometry fits the split-bf16 backward's LDS plan
 int forward_bf16_supported(const smh_model *m);  // smh_tcn_bf16.hip: SMH_OK, or why the split-bf16 training forward refuses m
-// trunk_only = 1: the forward ends at the trunk (d_trunk tap / tio's saved activations); d_out is not written
+// what launch_forward reads and where it ends (the TcnArgs members of the same names); the defaults: patches in, heads out
+struct ForwardOpts {
+    int from_x0 = 0, x0_shift = 0, x0_T = 0;
+    int trunk_only = 0;  // 1: the forward ends at the trunk (d_trunk tap / tio's saved activations); d_out is not written
+};
 int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
-                   hipStream_t st, int from_x0 = 0, int x0_shift = 0, int x0_T = 0, int trunk_only = 0);
+                   hipStream_t st, const ForwardOpts &opt = {});
 // smh_fusion.hip: the layers behind the intermediate-fusion model's two trunks (SMH_HEADS_FUSION).
 // launch_fusion_dense: the Dense layers on the fused features; train = false: xh / xp = the trunk taps (N, W, 32), BN with the moving
 // statistics, out = the heads' outputs (N, out_dim); train = true: xh = xhat (N, D), out = pre (N, kPS) incl. biases.

@@ -1202,12 +1202,12 @@ static bool skew_schedule(const TcnArgs &a, int units) {
 }
 
 int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
-                   hipStream_t st, int from_x0, int x0_shift, int x0_T, int trunk_only) {
+                   hipStream_t st, const ForwardOpts &opt) {
     TcnArgs a;
     size_t lds;
     fill_args(m, N, &a, &lds);
-    a.trunk_only = trunk_only;
-    a.from_x0 = from_x0, a.x0_shift = x0_shift, a.x0_T = x0_T;
+    a.trunk_only = opt.trunk_only;
+    a.from_x0 = opt.from_x0, a.x0_shift = opt.x0_shift, a.x0_T = opt.x0_T;
     // timing probes (outputs invalid; training would read stale activations): only under SMH_ENABLE_PROBES=1, announced on stderr
     if (const char *ev = smh::probe_env("SMH_TCN_BLOCKS")) a.n_blocks = atoi(ev);  // tools/tune_model.py
     a.skip_heads = smh::probe_env("SMH_TCN_NOHEADS") ? 1 : 0;
@@ -1511,7 +1511,9 @@ extern "C" int smh_model_forward_dense_f32(const smh_model *m, const float *d_fv
     hipLaunchKernelGGL(l0_frames_kernel, dim3((unsigned)((Tc + 63) / 64), 2), dim3(256), 0, st, d_fv, smh_model_w0_ptr(m), x0, F / 2, Tc);
     int rc = smh::launch_status("l0_frames_kernel");
     if (rc) return rc;
-    rc = smh_tcn::launch_forward(m, x0, nP, d_out, nullptr, nullptr, st, 1, shift, Tc);
+    smh_tcn::ForwardOpts fo;
+    fo.from_x0 = 1, fo.x0_shift = shift, fo.x0_T = Tc;
+    rc = smh_tcn::launch_forward(m, x0, nP, d_out, nullptr, nullptr, st, fo);
     return rc ? rc : nP;
 }
 
@@ -1606,7 +1608,9 @@ extern "C" int smh_model_forward_x0_f32(const smh_model *m, const float *d_x0p, 
                 "path; use smh_fusion_forward_f32");
     SMH_REQUIRE(N >= 0, "smh_model_forward_x0_f32: N=%d", N);
     if (N == 0) return SMH_OK;
-    return smh_tcn::launch_forward(m, d_x0p, N, d_out, d_trunk, nullptr, (hipStream_t)stream, 1);
+    smh_tcn::ForwardOpts fo;
+    fo.from_x0 = 1;
+    return smh_tcn::launch_forward(m, d_x0p, N, d_out, d_trunk, nullptr, (hipStream_t)stream, fo);
 }
 
 extern "C" int smh_model_forward_f32(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk,

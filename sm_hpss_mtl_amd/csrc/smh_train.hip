@@ -614,28 +614,11 @@ tcn_backward_mfma_kernel(BwdArgs a, const float *__restrict__ X, const float *__
     if (tid < kZW) ZW[tid] = 0.f;
     __syncthreads();
     // ---- Dense-on-trunk backward: G = relu'(x) * (dpre @ Wh^T) ------------------------------------------------
-    // gt: the product as dtrunk_kernel computed it for the whole batch (smh_train_bf16.hip) -- here every workgroup read the whole
-    // 444 KB Dense kernel from L2 for its one patch; nullptr (SMH_DTRUNK=0): the loop below
-    if (gt) {
-        for (int i = tid; i < rows * (C / 4); i += nt) {
-            const int R = i >> 3, c4 = (i & 7) * 4;
-            *reinterpret_cast<f32x4 *>(G + (size_t)R * SX + c4) = *reinterpret_cast<const f32x4 *>(gt + ((size_t)n0 * T + R) * C + c4);
-        }
-    }
-    for (int i = tid; i < (gt ? 0 : rows * C); i += nt) {
-        const int R = i / C, c = i - R * C;
-        const int g = R / T, t = R - g * T;
-        const size_t k = (size_t)t * C + c;
-        const float xpre = acts[(((size_t)(n0 + g) * nslot + a.n_blocks) * T + t) * C + c];
-        float acc = 0.f;
-        const float *dp = dps + g * kPS;
-        for (int o = 0; o < a.n_classes; ++o) acc = fmaf(dp[o], flatw[a.off.c3_k + k * a.n_classes + o], acc);
-        for (int h = 0; h < a.n_heads; ++h) {
-            const float *wr = flatw + a.off.head[h] + k * kHidden;
-#pragma unroll
-            for (int jj = 0; jj < kHidden; ++jj) acc = fmaf(dp[a.n_classes + h * kHidden + jj], wr[jj], acc);
-        }
-        G[R * SX + c] = xpre > 0.f ? acc : 0.f;
+    // gt: the product as dtrunk_kernel (smh_train_bf16.hip) or the fusion layers (fusion_gt) computed it for the whole batch -- not
+    // computed here, where every workgroup would read the whole 444 KB Dense kernel from L2 for its one patch
+    for (int i = tid; i < rows * (C / 4); i += nt) {
+        const int R = i >> 3, c4 = (i & 7) * 4;
+        *reinterpret_cast<f32x4 *>(G + (size_t)R * SX + c4) = *reinterpret_cast<const f32x4 *>(gt + ((size_t)n0 * T + R) * C + c4);
     }
 
     unsigned long long tph[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = t_entry;
@@ -1394,25 +1377,29 @@ extern "C" int smh_trainer_set_dtype(smh_trainer *t, int dtype) {
     return SMH_OK;
 }
 
-extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float *d_y, int N, const float *d_drop_tcn,
-                                  const float *d_drop_heads, const float *h_loss_weights, float *d_losses, void *stream) {
-    SMH_REQUIRE(t && d_x && d_y && d_losses, "smh_train_step_f32: null argument");
-    SMH_REQUIRE(N >= 1 && N <= t->max_batch, "smh_train_step_f32: batch %d outside [1, %d]", N, t->max_batch);
-    SMH_REQUIRE(t->m->heads != SMH_HEADS_FUSION, "smh_train_step_f32: an intermediate-fusion model has two inputs; use "
-                "smh_fusion_train_step_f32");
-    smh_model *m = t->m;
-    hipStream_t st = (hipStream_t)stream;
-    SMH_CHECK_HIP(hipMemsetAsync(t->d_grad, 0, m->n_params * sizeof(float), st));
-    // dtype 1: the residual blocks' backward on the bf16 matrix pipe (smh_train_bf16.hip); patch geometries outside its LDS plan, and
-    // SMH_BWD_BF16=0 (A/B and tests), keep the exact-f32 kernel behind the bf16 forward -- which then has to save every block's input
-    const bool bf16_bwd = t->dtype == 1 && !getenv("SMH_TRAIN_VALU") && !(getenv("SMH_BWD_BF16") && atoi(getenv("SMH_BWD_BF16")) == 0) &&
-                          backward_bf16_supported(m->cfg.patch_size, m->cfg.n_dilations);
-    TrainIO tio{t->d_acts, d_drop_tcn, t->d_pre, t->d_upre, bf16_bwd ? 1 : 0};
-    // dtype 1: the training forward on the bf16 matrix pipe (split operands: f32-grade products, smh_tcn_bf16.hip); it saves the
-    // same activations and gates in f32, so the backward pass below is unchanged
-    int rc = t->dtype == 1 ? launch_forward_bf16_train(m, d_x, N, &tio, st) : launch_forward(m, d_x, N, t->d_scratch_out, nullptr, &tio, st);
-    if (rc) return rc;
-    const Offsets off = offsets(m);
+// The implementation switches of the training step (A/B and tests), one getenv each.  Read at the top of every step rather than
+// once in smh_trainer_create: tests flip SMH_BWD_BF16 and SMH_BWD_SPLIT between the steps of one trainer.
+struct StepSwitches {
+    bool valu;      // SMH_TRAIN_VALU set: the scalar backward kernel (tcn_backward_kernel)
+    bool bf16_bwd;  // SMH_BWD_BF16, default on: dtype 1's split-bf16 backward (0: the exact-f32 backward behind the bf16 forward)
+    int split3;     // SMH_BWD_SPLIT, default 1: BwdArgs::split3
+    int stamps;     // SMH_BWD_STAMPS set: BwdArgs::stamps
+    bool dwh_valu;  // SMH_DWH_VALU set: dwh_kernel instead of dwh_mfma_kernel
+};
+
+static StepSwitches read_switches() {
+    StepSwitches s;
+    s.valu = getenv("SMH_TRAIN_VALU") != nullptr;
+    const char *ev = getenv("SMH_BWD_BF16");
+    s.bf16_bwd = !(ev && atoi(ev) == 0);
+    ev = getenv("SMH_BWD_SPLIT");
+    s.split3 = ev ? atoi(ev) != 0 : 1;
+    s.stamps = getenv("SMH_BWD_STAMPS") ? 1 : 0;
+    s.dwh_valu = getenv("SMH_DWH_VALU") != nullptr;
+    return s;
+}
+
+static HeadsArgs heads_args(const smh_model *m, const Offsets &off, int N, const float *h_loss_weights) {
     HeadsArgs ha;
     ha.N = N, ha.D = m->D, ha.NH = m->NH, ha.n_classes = m->cfg.n_classes, ha.n_heads = m->n_heads, ha.out_dim = m->out_dim;
     for (int i = 0; i < kMaxHeads; ++i) {
@@ -1429,6 +1416,91 @@ extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float 
         ha.hp_off[i] = hpo;
         hpo += head_tail_floats(m, i);
     }
+    return ha;
+}
+
+static BwdArgs bwd_args(const smh_trainer *t, const Offsets &off, int N, int split3, int stamps) {
+    const smh_model *m = t->m;
+    BwdArgs ba;
+    ba.gq = t->d_gq;  // nullptr unless smh_trainer_set_deterministic(t, 1)
+    ba.split3 = split3;
+    ba.N = N, ba.T = m->cfg.patch_size, ba.F = m->cfg.n_feat, ba.n_blocks = m->n_blocks, ba.n_dil = m->cfg.n_dilations;
+    ba.use_wt = 1;
+    ba.stamps = stamps;
+    ba.D = m->D, ba.NH = m->NH, ba.n_classes = m->cfg.n_classes, ba.n_heads = m->n_heads, ba.off = off;
+    return ba;
+}
+
+// LDS plan of the f32 MFMA trunk backward at patch length T: the short form parks the block kernels in LDS, the long one reads them
+// from the weight vector
+struct MfmaPlan {
+    int RPm;
+    size_t lds_m, lds_long;
+    bool short_ok, long_ok;
+};
+
+static MfmaPlan mfma_plan(int T) {
+    MfmaPlan p;
+    p.RPm = ((kMG * T + 15) / 16) * 16;
+    p.lds_m = sizeof(float) * ((size_t)4 * p.RPm * SX + 4 * C * kWS + kMG * kPS + C + kZW);
+    p.lds_long = sizeof(float) * ((size_t)4 * p.RPm * SX + kMG * kPS + C + kZW);  // kernels stay in global memory
+    p.short_ok = p.lds_m <= 156 * 1024 && T <= kMfmaMaxT, p.long_ok = p.lds_long <= 156 * 1024 && T <= kMfmaLongT;
+    return p;
+}
+
+// the f32 MFMA backward of one trunk (input x, its saved acts / upre / dropout masks), fed with gt = d loss / d (trunk output);
+// a.off: where that trunk's weights are in the flat weights and gradient
+static int launch_backward_mfma(const smh_trainer *t, const BwdArgs &a, const float *x, const float *acts, const float *drop,
+                                const float *upre, const float *gt, hipStream_t st) {
+    const MfmaPlan p = mfma_plan(a.T);
+    const dim3 grid((a.N + kMG - 1) / kMG);
+    if (p.short_ok) {
+        auto kern = tcn_backward_mfma_kernel<true, kMfmaMaxT>;
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_m));
+        hipLaunchKernelGGL(kern, grid, dim3(kMThreads), p.lds_m, st, a, x, t->m->d_flat, acts, drop, t->d_dpre, t->d_grad, p.RPm,
+                           upre, gt);
+    } else {
+        auto kern = tcn_backward_mfma_kernel<false, kMfmaLongT>;
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_long));
+        hipLaunchKernelGGL(kern, grid, dim3(kMThreads), p.lds_long, st, a, x, t->m->d_flat, acts, drop, t->d_dpre, t->d_grad, p.RPm,
+                           upre, gt);
+    }
+    return smh::launch_status("tcn_backward_mfma_kernel");
+}
+
+// One training step of a TCN model, after the entry point's checks.  x: the trunk inputs, one (B3_MTL, cascaded) or two (intermediate
+// fusion: trunk H, then trunk P; trunk b has its own part b of the saved activations, the gates and the dropout masks).  The fusion
+// model's trunk forwards are the B3_MTL forward kernel, trunk only; its Dense layers and the fused BatchNorm run in smh_fusion.hip,
+// which also hands each trunk backward its d loss / d (trunk output).
+static int train_step(smh_trainer *t, const float *const *x, int nx, const float *d_y, int N, const float *d_drop_tcn,
+                      const float *d_drop_heads, const float *h_loss_weights, float *d_losses, hipStream_t st) {
+    const StepSwitches sw = read_switches();
+    smh_model *m = t->m;
+    const bool fusion = nx == 2;
+    const int half = m->cfg.patch_size * C;
+    const size_t nact = (size_t)t->max_batch * (m->n_blocks + 1) * half, nupre = (size_t)t->max_batch * m->n_blocks * half;
+    const size_t ndrop = (size_t)N * m->n_blocks * C;
+    const auto drop = [&](int b) { return d_drop_tcn ? d_drop_tcn + b * ndrop : nullptr; };
+    SMH_CHECK_HIP(hipMemsetAsync(t->d_grad, 0, m->n_params * sizeof(float), st));
+    // dtype 1: the residual blocks' backward on the bf16 matrix pipe (smh_train_bf16.hip); patch geometries outside its LDS plan, and
+    // SMH_BWD_BF16=0 (A/B and tests), keep the exact-f32 kernel behind the bf16 forward -- which then has to save every block's input
+    const bool bf16_bwd = t->dtype == 1 && !sw.valu && sw.bf16_bwd && backward_bf16_supported(m->cfg.patch_size, m->cfg.n_dilations);
+    ForwardOpts fo;
+    fo.trunk_only = fusion;
+    for (int b = 0; b < nx; ++b) {
+        TrainIO tio{t->d_acts + b * nact, drop(b), t->d_pre, t->d_upre + b * nupre, bf16_bwd ? 1 : 0};
+        // dtype 1: the training forward on the bf16 matrix pipe (split operands: f32-grade products, smh_tcn_bf16.hip); it saves the
+        // same activations and gates in f32, so the backward pass below is unchanged
+        const int rc = t->dtype == 1 ? launch_forward_bf16_train(m, x[b], N, &tio, st)
+                                     : launch_forward(fusion ? m->trunk[b] : m, x[b], N, t->d_scratch_out, nullptr, &tio, st, fo);
+        if (rc) return rc;
+    }
+    int rc = fusion ? launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats,
+                                          t->d_pre, t->d_grad, 0, st)
+                    : SMH_OK;
+    if (rc) return rc;
+    const Offsets off = offsets(m);
+    const HeadsArgs ha = heads_args(m, off, N, h_loss_weights);
     if (m->heads == SMH_HEADS_CASCADED)
         rc = launch_cascade_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_dr, t->d_grad,
                                         t->d_bnstat, d_losses, st);
@@ -1436,77 +1508,70 @@ extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float 
         rc = launch_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bnstat, d_losses,
                                 reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
     if (rc) return rc;
-    BwdArgs ba;
-    ba.gq = t->d_gq;  // nullptr unless smh_trainer_set_deterministic(t, 1)
-    ba.split3 = 1;
-    if (const char *ev = getenv("SMH_BWD_SPLIT")) ba.split3 = atoi(ev) != 0;
-    ba.N = N, ba.T = m->cfg.patch_size, ba.F = m->cfg.n_feat, ba.n_blocks = m->n_blocks, ba.n_dil = m->cfg.n_dilations;
-    ba.use_wt = 1;
-    ba.stamps = getenv("SMH_BWD_STAMPS") ? 1 : 0;
-    ba.D = m->D, ba.NH = m->NH, ba.n_classes = m->cfg.n_classes, ba.n_heads = m->n_heads, ba.off = off;
+    BwdArgs ba = bwd_args(t, off, N, sw.split3, fusion ? 0 : sw.stamps);
     hipLaunchKernelGGL(l2_penalty_kernel, dim3(m->n_heads * kL2Chunks), dim3(256), 0, st, ba, m->d_flat, d_losses + m->n_heads + 3,
                        t->d_l2part, reinterpret_cast<unsigned *>(t->d_l2part + kMaxHeads * kL2Chunks));
     rc = smh::launch_status("l2_penalty_kernel");
     if (rc) return rc;
-    // MFMA backward (default); SMH_TRAIN_VALU=1 keeps the scalar reference kernel
-    const int RPm = ((kMG * ba.T + 15) / 16) * 16;
-    const size_t lds_m = sizeof(float) * ((size_t)4 * RPm * SX + 4 * C * kWS + kMG * kPS + C + kZW);
-    const size_t lds_long = sizeof(float) * ((size_t)4 * RPm * SX + kMG * kPS + C + kZW);  // kernels stay in global memory
-    const bool short_ok = lds_m <= 156 * 1024 && ba.T <= kMfmaMaxT, long_ok = lds_long <= 156 * 1024 && ba.T <= kMfmaLongT;
-    bool bwd_done = false;
-    if (bf16_bwd) {
-        rc = launch_backward_bf16(ba, &t->d_bwd_pack, &t->bwd_pack_cap, d_x, m->d_flat, t->d_acts, d_drop_tcn, t->d_dpre, t->d_grad,
-                                  (const float *)t->d_upre, st);
+    if (fusion) {
+        rc = launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats, t->d_dpre,
+                                 t->d_grad, 1, st);
         if (rc) return rc;
-        bwd_done = true;
     }
-    if (bwd_done || ((short_ok || long_ok) && !getenv("SMH_TRAIN_VALU"))) {
-        const dim3 grid((N + kMG - 1) / kMG);
-        float *d_gt = nullptr;
-        if (!bwd_done && !(getenv("SMH_DTRUNK") && atoi(getenv("SMH_DTRUNK")) == 0)) {  // (SMH_DTRUNK=0: the in-kernel loop, A/B and tests)
-            if (!t->d_gt) SMH_CHECK_HIP(hipMalloc((void **)&t->d_gt, (size_t)t->max_batch * ba.D * sizeof(float)));
-            d_gt = t->d_gt;
-            rc = launch_dtrunk(ba, m->d_flat, t->d_acts, t->d_dpre, d_gt, st);
-            if (rc) return rc;
+    // the trunk backward of each trunk.  The bf16 and the MFMA backward of a one-input model leave the gradient of the Dense layers
+    // on the trunk to dwh_*_kernel; the scalar kernel computes it itself, the fusion model's Dense layers are smh_fusion.hip's.
+    const MfmaPlan plan = mfma_plan(ba.T);
+    bool dwh = false;
+    if (fusion) {
+        for (int b = 0; b < 2 && !rc; ++b) {
+            BwdArgs bb = ba;
+            bb.D = half;
+            if (b == 1) bb.off.w0_k += off.trunk_p, bb.off.w0_b += off.trunk_p, bb.off.blk0 += off.trunk_p;
+            rc = launch_backward_mfma(t, bb, x[b], t->d_acts + b * nact, drop(b), t->d_upre + b * nupre,
+                                      fusion_gt(m, t->max_batch, t->d_fusion, N, b), st);
         }
-        if (bwd_done) {
-        } else if (short_ok) {
-            auto kern = tcn_backward_mfma_kernel<true, kMfmaMaxT>;
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
-            hipLaunchKernelGGL(kern, grid, dim3(kMThreads), lds_m, st, ba, d_x, m->d_flat, t->d_acts, d_drop_tcn, t->d_dpre, t->d_grad,
-                               RPm, (const float *)t->d_upre, (const float *)d_gt);
-        } else {
-            auto kern = tcn_backward_mfma_kernel<false, kMfmaLongT>;
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_long));
-            hipLaunchKernelGGL(kern, grid, dim3(kMThreads), lds_long, st, ba, d_x, m->d_flat, t->d_acts, d_drop_tcn, t->d_dpre,
-                               t->d_grad, RPm, (const float *)t->d_upre, (const float *)d_gt);
+    } else if (bf16_bwd) {
+        rc = launch_backward_bf16(ba, &t->d_bwd_pack, &t->bwd_pack_cap, x[0], m->d_flat, t->d_acts, d_drop_tcn, t->d_dpre, t->d_grad,
+                                  (const float *)t->d_upre, st);
+        dwh = true;
+    } else if ((plan.short_ok || plan.long_ok) && !sw.valu) {  // the MFMA backward (default); SMH_TRAIN_VALU keeps the scalar kernel
+        if (!t->d_gt) SMH_CHECK_HIP(hipMalloc((void **)&t->d_gt, (size_t)t->max_batch * ba.D * sizeof(float)));
+        rc = launch_dtrunk(ba, m->d_flat, t->d_acts, t->d_dpre, t->d_gt, st);
+        if (!rc) rc = launch_backward_mfma(t, ba, x[0], t->d_acts, d_drop_tcn, t->d_upre, t->d_gt, st);
+        dwh = true;
+    } else {
+        const int RP = kBG * ba.T;
+        size_t lds = sizeof(float) * ((size_t)4 * RP * kBS + 2 * (3 * C * C + C * C) + C + 3 * RP + kBG * kPS);
+        if (lds > 156 * 1024) {  // long patches (the reference's W = 249): no room for the transposed kernel copies
+            ba.use_wt = 0;
+            lds -= sizeof(float) * (3 * C * C + C * C);
         }
-        rc = smh::launch_status("tcn_backward_mfma_kernel");
-        if (rc) return rc;
-        if (getenv("SMH_DWH_VALU")) {  // the one-thread-per-element kernel (a second implementation for the tests)
-            hipLaunchKernelGGL(dwh_kernel, dim3((ba.D * kHidden + 255) / 256, (N + kDwhSlice - 1) / kDwhSlice, 1 + ba.n_heads),
-                               dim3(256), 0, st, ba, t->d_acts, t->d_dpre, t->d_grad, kDwhSlice);
-            rc = smh::launch_status("dwh_kernel");
-            return rc ? rc : det_finalize(t, st);
-        }
+        SMH_REQUIRE(lds <= 156 * 1024, "patch_size %d too long for the backward kernel (at most 264 frames)", ba.T);
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)tcn_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(tcn_backward_kernel, dim3((N + kBG - 1) / kBG), dim3(kBThreads), lds, st, ba, x[0], m->d_flat, t->d_acts,
+                           d_drop_tcn, t->d_dpre, t->d_grad);
+        rc = smh::launch_status("tcn_backward_kernel");
+    }
+    if (rc) return rc;
+    if (dwh && sw.dwh_valu) {  // the one-thread-per-element kernel (a second implementation for the tests)
+        hipLaunchKernelGGL(dwh_kernel, dim3((ba.D * kHidden + 255) / 256, (N + kDwhSlice - 1) / kDwhSlice, 1 + ba.n_heads), dim3(256), 0,
+                           st, ba, t->d_acts, t->d_dpre, t->d_grad, kDwhSlice);
+        rc = smh::launch_status("dwh_kernel");
+    } else if (dwh) {
         hipLaunchKernelGGL(dwh_mfma_kernel, dim3((ba.D / 16 + 3) / 4, 1 + ba.n_heads, kDwhSplit), dim3(256), 0, st, ba, t->d_acts,
                            t->d_dpre, t->d_grad);
         rc = smh::launch_status("dwh_mfma_kernel");
-        return rc ? rc : det_finalize(t, st);
     }
-    const int RP = kBG * ba.T;
-    size_t lds = sizeof(float) * ((size_t)4 * RP * kBS + 2 * (3 * C * C + C * C) + C + 3 * RP + kBG * kPS);
-    ba.use_wt = 1;
-    if (lds > 156 * 1024) {  // long patches (the reference's W = 249): no room for the transposed kernel copies
-        ba.use_wt = 0;
-        lds -= sizeof(float) * (3 * C * C + C * C);
-    }
-    SMH_REQUIRE(lds <= 156 * 1024, "patch_size %d too long for the backward kernel (at most 264 frames)", ba.T);
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)tcn_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(tcn_backward_kernel, dim3((N + kBG - 1) / kBG), dim3(kBThreads), lds, st, ba, d_x, m->d_flat,
-                       t->d_acts, d_drop_tcn, t->d_dpre, t->d_grad);
-    rc = smh::launch_status("tcn_backward_kernel");
     return rc ? rc : det_finalize(t, st);
+}
+
+extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float *d_y, int N, const float *d_drop_tcn,
+                                  const float *d_drop_heads, const float *h_loss_weights, float *d_losses, void *stream) {
+    SMH_REQUIRE(t && d_x && d_y && d_losses, "smh_train_step_f32: null argument");
+    SMH_REQUIRE(N >= 1 && N <= t->max_batch, "smh_train_step_f32: batch %d outside [1, %d]", N, t->max_batch);
+    SMH_REQUIRE(t->m->heads != SMH_HEADS_FUSION, "smh_train_step_f32: an intermediate-fusion model has two inputs; use "
+                "smh_fusion_train_step_f32");
+    return train_step(t, &d_x, 1, d_y, N, d_drop_tcn, d_drop_heads, h_loss_weights, d_losses, (hipStream_t)stream);
 }
 
 extern "C" size_t smh_trainer_bucket_floats(const smh_trainer *t) { return t ? t->m->n_params + t->bn_floats : 0; }
@@ -1568,10 +1633,8 @@ extern "C" int smh_trainer_apply_sgd_f32(smh_trainer *t, float lr, float momentu
     return smh_trainer_apply_f32(t, 0, lr, momentum, 0.f, 0.f, clipnorm, grad_scale, 0xFFFFFFFFu, stream);
 }
 
-// The intermediate-fusion model's training step: the two trunks' training forwards (the B3_MTL forward kernel, trunk only), the
-// fused BatchNorm's batch statistics and the Dense layers on the fused features (smh_fusion.hip), B3_MTL's heads-training kernel with
-// D = 2 W 32, the Dense kernels' and the fused BatchNorm's gradients, then the MFMA trunk backward once per trunk, fed with d loss /
-// d (trunk output), each writing its own offsets of the flat gradient.
+// The intermediate-fusion model's training step: the two trunks' training forwards, the fused BatchNorm and the Dense layers on the
+// fused features, B3_MTL's heads-training kernel with D = 2 W 32, then the MFMA trunk backward once per trunk (train_step).
 extern "C" int smh_fusion_train_step_f32(smh_trainer *t, const float *d_xH, const float *d_xP, const float *d_y, int N,
                                          const float *d_drop_tcn, const float *d_drop_heads, const float *h_loss_weights,
                                          float *d_losses, void *stream) {
@@ -1579,83 +1642,10 @@ extern "C" int smh_fusion_train_step_f32(smh_trainer *t, const float *d_xH, cons
     SMH_REQUIRE(t->m->heads == SMH_HEADS_FUSION, "smh_fusion_train_step_f32: the model is not an intermediate-fusion model");
     SMH_REQUIRE(N >= 1 && N <= t->max_batch, "smh_fusion_train_step_f32: batch %d outside [1, %d]", N, t->max_batch);
     SMH_REQUIRE(t->dtype == 0, "smh_fusion_train_step_f32: the intermediate-fusion model trains in f32 (dtype 0) only");
-    smh_model *m = t->m;
-    hipStream_t st = (hipStream_t)stream;
-    const int T = m->cfg.patch_size, half = T * C;
-    const size_t nact = (size_t)t->max_batch * (m->n_blocks + 1) * half, nupre = (size_t)t->max_batch * m->n_blocks * half;
-    const size_t ndrop = (size_t)N * m->n_blocks * C;
-    // the f32 MFMA trunk backward with d loss / d trunk output given (smh_train_step_f32's default path)
-    const int RPm = ((kMG * T + 15) / 16) * 16;
-    const size_t lds_m = sizeof(float) * ((size_t)4 * RPm * SX + 4 * C * kWS + kMG * kPS + C + kZW);
-    const size_t lds_long = sizeof(float) * ((size_t)4 * RPm * SX + kMG * kPS + C + kZW);
-    const bool short_ok = lds_m <= 156 * 1024 && T <= kMfmaMaxT, long_ok = lds_long <= 156 * 1024 && T <= kMfmaLongT;
-    SMH_REQUIRE(short_ok || long_ok, "smh_fusion_train_step_f32: patch_size %d too long for the trunk backward (at most %d frames)", T,
-                kMfmaLongT);
-    SMH_CHECK_HIP(hipMemsetAsync(t->d_grad, 0, m->n_params * sizeof(float), st));
+    const int T = t->m->cfg.patch_size;
+    const MfmaPlan plan = mfma_plan(T);
+    SMH_REQUIRE(plan.short_ok || plan.long_ok, "smh_fusion_train_step_f32: patch_size %d too long for the trunk backward (at most %d frames)",
+                T, kMfmaLongT);
     const float *x[2] = {d_xH, d_xP};
-    for (int b = 0; b < 2; ++b) {
-        TrainIO tio{t->d_acts + b * nact, d_drop_tcn ? d_drop_tcn + b * ndrop : nullptr, t->d_pre, t->d_upre + b * nupre, 0};
-        const int rc = launch_forward(m->trunk[b], x[b], N, t->d_scratch_out, nullptr, &tio, st, 0, 0, 0, 1);
-        if (rc) return rc;
-    }
-    int rc = launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats, t->d_pre,
-                                 t->d_grad, 0, st);
-    if (rc) return rc;
-    const Offsets off = offsets(m);
-    HeadsArgs ha;
-    ha.N = N, ha.D = m->D, ha.NH = m->NH, ha.n_classes = m->cfg.n_classes, ha.n_heads = m->n_heads, ha.out_dim = m->out_dim;
-    for (int i = 0; i < kMaxHeads; ++i) {
-        ha.head_odim[i] = m->head_odim[i], ha.head_sigmoid[i] = m->head_sigmoid[i];
-        ha.goff_head[i] = off.head[i];
-    }
-    for (int i = 0; i <= kMaxHeads; ++i) ha.lw[i] = 1.0f;
-    if (h_loss_weights)
-        for (int i = 0; i <= m->n_heads; ++i) ha.lw[i] = h_loss_weights[i];
-    ha.goff_c3b = off.c3_b;
-    ha.ext_losses = 1;
-    size_t hpo = 0;
-    for (int i = 0; i < m->n_heads; ++i) {
-        ha.hp_off[i] = hpo;
-        hpo += head_tail_floats(m, i);
-    }
-    rc = launch_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bnstat, d_losses,
-                            reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
-    if (rc) return rc;
-    BwdArgs ba;
-    ba.gq = t->d_gq;
-    ba.split3 = 1;
-    if (const char *ev = getenv("SMH_BWD_SPLIT")) ba.split3 = atoi(ev) != 0;
-    ba.N = N, ba.T = T, ba.F = m->cfg.n_feat, ba.n_blocks = m->n_blocks, ba.n_dil = m->cfg.n_dilations;
-    ba.use_wt = 1;
-    ba.stamps = 0;
-    ba.D = m->D, ba.NH = m->NH, ba.n_classes = m->cfg.n_classes, ba.n_heads = m->n_heads, ba.off = off;
-    hipLaunchKernelGGL(l2_penalty_kernel, dim3(m->n_heads * kL2Chunks), dim3(256), 0, st, ba, m->d_flat, d_losses + m->n_heads + 3,
-                       t->d_l2part, reinterpret_cast<unsigned *>(t->d_l2part + kMaxHeads * kL2Chunks));
-    rc = smh::launch_status("l2_penalty_kernel");
-    if (rc) return rc;
-    rc = launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats, t->d_dpre,
-                             t->d_grad, 1, st);
-    if (rc) return rc;
-    for (int b = 0; b < 2; ++b) {
-        BwdArgs bb = ba;
-        bb.D = half;
-        if (b == 1) bb.off.w0_k += off.trunk_p, bb.off.w0_b += off.trunk_p, bb.off.blk0 += off.trunk_p;
-        const float *gt = fusion_gt(m, t->max_batch, t->d_fusion, N, b);
-        const float *drop = d_drop_tcn ? d_drop_tcn + b * ndrop : nullptr;
-        const dim3 grid((N + kMG - 1) / kMG);
-        if (short_ok) {
-            auto kern = tcn_backward_mfma_kernel<true, kMfmaMaxT>;
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
-            hipLaunchKernelGGL(kern, grid, dim3(kMThreads), lds_m, st, bb, x[b], m->d_flat, t->d_acts + b * nact, drop, t->d_dpre,
-                               t->d_grad, RPm, (const float *)(t->d_upre + b * nupre), gt);
-        } else {
-            auto kern = tcn_backward_mfma_kernel<false, kMfmaLongT>;
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_long));
-            hipLaunchKernelGGL(kern, grid, dim3(kMThreads), lds_long, st, bb, x[b], m->d_flat, t->d_acts + b * nact, drop, t->d_dpre,
-                               t->d_grad, RPm, (const float *)(t->d_upre + b * nupre), gt);
-        }
-        rc = smh::launch_status("tcn_backward_mfma_kernel");
-        if (rc) return rc;
-    }
-    return det_finalize(t, st);
+    return train_step(t, x, 2, d_y, N, d_drop_tcn, d_drop_heads, h_loss_weights, d_losses, (hipStream_t)stream);
 }

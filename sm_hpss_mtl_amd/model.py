@@ -249,6 +249,17 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
                        "smh_model_set_weights")
             self._dirty = False
 
+    def _train_inputs(self, x):
+        """A training step's input -> [x] as a contiguous float32 CUDA tensor (N, W, n_feat) (TrainingMixin.train_on_batch)."""
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        x = x.to(device="cuda", dtype=torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[1] != self.patch_size or x.shape[2] != self.n_feat:
+            raise ValueError("expected input (N, %d, %d), got %s" % (self.patch_size, self.n_feat, tuple(x.shape)))
+        if self.block_variant != 0:
+            raise NotImplementedError("training is built for the keras-tcn 2.3.x block (tcn_block='2.3'); the 2.8 block is inference only")
+        return [x]
+
     def forward_device(self, x, out=None, trunk=None, dtype="f32"):
         """x: float32 CUDA tensor (N, W, n_feat) -> (N, out_dim) tensor [S|M|(N)|R|3C] on the device.
         dtype="bf16" selects the mixed-precision kernel (bf16 matrix-core operands, f32 everything else): faster,
@@ -426,6 +437,9 @@ class FusionMTL(B3MTL):
     def _device_input(self, x):
         return self._pair(x)
 
+    def _train_inputs(self, x):
+        return self._pair(x)
+
     def forward_device(self, x, out=None, trunk=None, dtype="f32"):
         """x: [x_H, x_P] (or the dict) -> (N, out_dim) tensor [S|M|(N)|R|3C] on the device (smh_fusion_forward_f32)."""
         if dtype != "f32":
@@ -458,44 +472,6 @@ class FusionMTL(B3MTL):
         self.check_status()
         host = out.cpu().numpy()
         return [np.ascontiguousarray(o) for o in self.split_outputs(host)]
-
-    # ---- training ----
-    def train_on_batch(self, x, y, drop_tcn="auto", drop_heads="auto", apply=True, sync=True, _only=None, _mask=None):
-        """One optimiser step (smh_fusion_train_step_f32).  drop_tcn: "auto", None, or a (2, N, n_blocks, 32) tensor of
-        SpatialDropout1D masks (trunk H, then trunk P); drop_heads as for B3MTL.  Returns [loss, <per-output losses>, 3C_accuracy]."""
-        from .training import HEAD_DROPOUT, TRAIN_ALL, _cur_stream
-        if _only is not None:
-            raise ValueError("single-output sub-models are built for the B3_MTL heads only")
-        xh, xp = self._pair(x)
-        n = xh.shape[0]
-        yt = y if (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() == 2) else self.pack_targets(y)
-        if yt.shape[0] != n:
-            raise ValueError("%d inputs but %d target rows" % (n, yt.shape[0]))
-        self._sync_weights()
-        tr = self._get_trainer(n)
-        n_blocks, n_heads = self.nb_stacks * self.n_dilations, len(self.output_names) - 1
-        if isinstance(drop_tcn, str) or isinstance(drop_heads, str):
-            from .device_rng import dropout_masks
-            n_t, n_h = 2 * n * n_blocks * 32, n * n_heads * 16  # one rate (drawn at build time), independent masks per trunk
-            masks = dropout_masks(n_t, 1.0 - self.dropout_rate, n_h, 1.0 - HEAD_DROPOUT, self._mask_seed, self._mask_calls)
-            self._mask_calls += 1
-            if isinstance(drop_tcn, str):
-                drop_tcn = masks[:n_t].view(2, n, n_blocks, 32)
-            if isinstance(drop_heads, str):
-                drop_heads = masks[n_t:].view(n, n_heads, 16)
-        if drop_tcn is not None and tuple(drop_tcn.shape) != (2, n, n_blocks, 32):
-            raise ValueError("drop_tcn must be (2, %d, %d, 32), got %s" % (n, n_blocks, tuple(drop_tcn.shape)))
-        losses = torch.empty(self._n_losses(), dtype=torch.float32, device="cuda")
-        p = lambda t: None if t is None else C.c_void_p(t.contiguous().data_ptr())  # noqa: E731
-        _lib.check(self.lib.smh_fusion_train_step_f32(tr, p(xh), p(xp), p(yt), n, p(drop_tcn), p(drop_heads),
-                                                      self._loss_weight_array(), p(losses), _cur_stream()),
-                   "smh_fusion_train_step_f32")
-        if apply:
-            self.apply_gradients(TRAIN_ALL if _mask is None else _mask)
-        if not sync:
-            return losses
-        self._check_device_status()
-        return self.losses_to_list(losses)
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_data=None,
             steps_per_epoch=None, validation_steps=None, initial_epoch=0, **kwargs):

@@ -301,36 +301,37 @@ class TrainingMixin:
     def train_on_batch(self, x, y, drop_tcn="auto", drop_heads="auto", apply=True, sync=True, _only=None, _mask=TRAIN_ALL):
         """One optimiser step.  Returns [loss, <per-output losses>, 3C_accuracy] like Keras; with sync=False the raw
         device tensor of the step's losses (no host round trip: feed it to `losses_to_list` later).
-        drop_*: "auto" draws masks with the model's rates, None disables dropout, or pass mask tensors."""
-        if isinstance(x, np.ndarray):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        x = x.to(device="cuda", dtype=torch.float32).contiguous()
-        n = x.shape[0]
-        if x.dim() != 3 or x.shape[1] != self.patch_size or x.shape[2] != self.n_feat:
-            raise ValueError("expected input (N, %d, %d), got %s" % (self.patch_size, self.n_feat, tuple(x.shape)))
-        if getattr(self, "block_variant", 0) != 0:
-            raise NotImplementedError("training is built for the keras-tcn 2.3.x block (tcn_block='2.3'); the 2.8 block is inference only")
+        drop_*: "auto" draws masks with the model's rates, None disables dropout, or pass mask tensors: drop_tcn (N, n_blocks, 32),
+        (2, N, n_blocks, 32) for a model with two trunks (trunk H, then trunk P), drop_heads (N, n_heads, 16)."""
+        xs = self._train_inputs(x)
+        if _only is not None and len(xs) != 1:
+            raise ValueError("single-output sub-models are built for the B3_MTL heads only")
+        n = xs[0].shape[0]
         yt = y if (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() == 2) else self.pack_targets(y)
         if yt.shape[0] != n:
             raise ValueError("%d inputs but %d target rows" % (n, yt.shape[0]))
         self._sync_weights()
         tr = self._get_trainer(n)
         n_blocks, n_heads = self.nb_stacks * self.n_dilations, len(self.output_names) - 1
+        tcn_shape = ((len(xs),) if len(xs) > 1 else ()) + (n, n_blocks, 32)
         if isinstance(drop_tcn, str) or isinstance(drop_heads, str):
             # both masks from ONE launch (csrc/smh_rng.hip; until round 3 a torch Bernoulli draw and a scaling): Philox keyed by this
-            # replica's seed (1234 + RANK: every rank draws its own masks), one stream per step
+            # replica's seed (1234 + RANK: every rank draws its own masks), one stream per step; one rate, independent masks per trunk
             from .device_rng import dropout_masks
-            n_t, n_h = n * n_blocks * 32, n * n_heads * 16
+            n_t, n_h = len(xs) * n * n_blocks * 32, n * n_heads * 16
             masks = dropout_masks(n_t, 1.0 - self.dropout_rate, n_h, 1.0 - HEAD_DROPOUT, self._mask_seed, self._mask_calls)
             self._mask_calls += 1
             if isinstance(drop_tcn, str):
-                drop_tcn = masks[:n_t].view(n, n_blocks, 32)
+                drop_tcn = masks[:n_t].view(tcn_shape)
             if isinstance(drop_heads, str):
                 drop_heads = masks[n_t:].view(n, n_heads, 16)
+        if drop_tcn is not None and tuple(drop_tcn.shape) != tcn_shape:
+            raise ValueError("drop_tcn must be %s, got %s" % (tcn_shape, tuple(drop_tcn.shape)))
         losses = torch.empty(self._n_losses(), dtype=torch.float32, device="cuda")
         p = lambda t: None if t is None else C.c_void_p(t.contiguous().data_ptr())  # noqa: E731
-        _lib.check(self.lib.smh_train_step_f32(tr, p(x), p(yt), n, p(drop_tcn), p(drop_heads), self._loss_weight_array(_only),
-                                               p(losses), _cur_stream()), "smh_train_step_f32")
+        entry = "smh_train_step_f32" if len(xs) == 1 else "smh_fusion_train_step_f32"
+        _lib.check(getattr(self.lib, entry)(tr, *map(p, xs), p(yt), n, p(drop_tcn), p(drop_heads), self._loss_weight_array(_only),
+                                            p(losses), _cur_stream()), entry)
         if apply:
             self.apply_gradients(_mask)
         if not sync:

@@ -585,3 +585,20 @@ def test_backward_kernel_residency():
     f.restype = C.c_int
     f.argtypes = [C.c_int]
     assert f(68) == 2
+
+
+@pytest.mark.parametrize("kind", ["B3_MTL", "fusion"])
+def test_a_mis_shaped_dropout_mask_is_refused(kind):
+    """drop_tcn is (N, n_blocks, 32) per trunk, trunk H before trunk P: a mask of any other shape is refused before the step
+    (one read as the right shape would take the wrong masks, or read past its end)."""
+    from sm_hpss_mtl_amd.model import B3MTL, FusionMTL
+    N, W = 4, 68
+    if kind == "fusion":
+        m, x, shape = FusionMTL(n_feat=120, patch_size=W), [np.zeros((N, W, 120), np.float32)] * 2, (2, N, 24, 32)
+    else:
+        m, x, shape = B3MTL(n_feat=240, patch_size=W), np.zeros((N, W, 240), np.float32), (N, 24, 32)
+    y = torch.zeros((N, m.out_dim), device="cuda")
+    # (N, 48, 32): twice the masks of B3_MTL; for the fusion model as many floats as its masks, in the wrong layout
+    with pytest.raises(ValueError, match="drop_tcn must be"):
+        m.train_on_batch(x, y, drop_tcn=torch.ones((N, 48, 32), device="cuda"), apply=False)
+    m.train_on_batch(x, y, drop_tcn=torch.ones(shape, device="cuda"), apply=False)
