@@ -455,6 +455,30 @@ int smh_fusion_forward_f32(const smh_model *m, const float *d_xH, const float *d
 int smh_fusion_train_step_f32(smh_trainer *t, const float *d_xH, const float *d_xP, const float *d_y, int N,
                               const float *d_drop_tcn, const float *d_drop_heads, const float *h_loss_weights, float *d_losses,
                               void *stream);
+/* The fusion model without materialised input halves.  Its trunks' first layers are per half already (trunk H reads the harmonic
+ * half of the H||P featuregram, trunk P the percussive half), so the per-half layer-0 partials that smh_features_l0_f32 writes are,
+ * with the right kernel, each trunk's COMPLETE first layer:
+ *   smh_fusion_w0_ptr            device pointer to (2 * n_feat, 32) floats: trunk H's initial-conv kernel, then trunk P's -- the d_w0 of
+ *                                smh_features_l0_f32 for this model.  Owned by the model, follows every weight change (set_weights,
+ *                                the trainer's apply).  Null unless SMH_HEADS_FUSION (smh_model_w0_ptr stays null for a fusion model).
+ *   smh_fusion_forward_x0_f32    d_x0p (N, 2, W, 32) as smh_features_l0_f32 wrote it with that kernel -> d_out (N, out_dim), as
+ *                                smh_fusion_forward_f32 on the halves of the same patches to f32 tolerance (layer 0 sums in another
+ *                                order).  d_work: smh_fusion_x0_workspace_bytes(m, N) = N * 2 * W * 32 floats (the trunk taps).
+ *   smh_fusion_forward_dense_f32 dense file-level inference, the fusion model's smh_model_forward_dense_f32: d_fv (2 * n_feat, Tc),
+ *                                the standardised H||P featuregram (H rows, then P rows); layer 0 of both trunks once per FRAME,
+ *                                every hop-`shift` patch of smh_num_patches(Tc, W, shift) a window of it.  Returns the number of
+ *                                patches; d_out (nP, out_dim).  The patches pass the trunks and the tail in chunks of 2048, so
+ *                                d_work = smh_fusion_dense_workspace_bytes(m, Tc, shift) = 4 * (2 * Tc * 32 + min(nP, 2048) * 2 * W * 32)
+ *                                bytes however long the featuregram is.  Needs Tc >= W, shift >= 1, n_feat a multiple of 4.
+ * Both trunks run as ONE grid (a second grid row selects trunk P); SMH_FUSION_TWO_LAUNCH=1 in the environment, read per call, runs
+ * them as two launches instead -- bit-identical, for A/B timing.  That switch also governs smh_fusion_forward_f32.
+ * Stream-ordered, no host synchronisation; d_x0p, d_fv and d_work on 16-byte boundaries; N = 0 / no patch: no launch. */
+const float *smh_fusion_w0_ptr(const smh_model *m);
+size_t smh_fusion_x0_workspace_bytes(const smh_model *m, int N);
+int smh_fusion_forward_x0_f32(smh_model *m, const float *d_x0p, int N, void *d_work, size_t work_bytes, float *d_out, void *stream);
+size_t smh_fusion_dense_workspace_bytes(const smh_model *m, int Tc, int shift);
+int smh_fusion_forward_dense_f32(smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes, float *d_out,
+                                 void *stream);
 /* g = grad * grad_scale (+ l2 term); per-tensor clip to `clipnorm` (<= 0: off); v = momentum*v - lr*g; w += v;
  * BN moving statistics <- 0.99*old + 0.01*batch; operand buffers re-packed on the device.              */
 int smh_trainer_apply_sgd_f32(smh_trainer *t, float lr, float momentum, float clipnorm, float grad_scale, void *stream);

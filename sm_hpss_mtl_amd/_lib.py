@@ -133,6 +133,11 @@ SIGNATURES = {
     "smh_fusion_workspace_bytes": (_sz, [_vp, _i]),
     "smh_fusion_forward_f32": (_i, [_vp, _fp, _fp, _i, _fp, _vp, _sz, _vp]),
     "smh_fusion_train_step_f32": (_i, [_vp, _fp, _fp, _fp, _i, _fp, _fp, _vp, _fp, _vp]),
+    "smh_fusion_w0_ptr": (_vp, [_vp]),
+    "smh_fusion_x0_workspace_bytes": (_sz, [_vp, _i]),
+    "smh_fusion_forward_x0_f32": (_i, [_vp, _fp, _i, _vp, _sz, _fp, _vp]),
+    "smh_fusion_dense_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "smh_fusion_forward_dense_f32": (_i, [_vp, _fp, _i, _i, _vp, _sz, _fp, _vp]),
 }
 
 _lib = None

@@ -315,6 +315,20 @@ const float *fusion_gt(const smh_model *m, int max_batch, const float *scratch, 
     return scratch + 2 * (size_t)max_batch * m->D + (size_t)b * N * (m->D / 2);
 }
 
+int launch_fusion_trunks(const smh_model *m, const float *xh, const float *xp, int N, float *tap_h, float *tap_p, ForwardOpts fo,
+                         hipStream_t st) {
+    fo.trunk_only = 1;
+    const char *ev = getenv("SMH_FUSION_TWO_LAUNCH");
+    if (ev && atoi(ev) != 0) {  // A/B runs and tests: one launch per trunk
+        const int rc = launch_forward(m->trunk[0], xh, N, nullptr, tap_h, nullptr, st, fo);
+        return rc ? rc : launch_forward(m->trunk[1], xp, N, nullptr, tap_p, nullptr, st, fo);
+    }
+    // one grid of (workgroups, 2): at the batch sizes of file-level inference with a hop above 1 and of the reference's own batches
+    // (48 patches) one trunk fills 48 of 256 CUs.  Every workgroup does what it does in a launch of its own: same results
+    fo.pair = m->trunk[1], fo.pair_x = xp, fo.pair_trunk = tap_p;
+    return launch_forward(m->trunk[0], xh, N, nullptr, tap_h, nullptr, st, fo);
+}
+
 }  // namespace smh_tcn
 
 extern "C" size_t smh_fusion_workspace_bytes(const smh_model *m, int N) {
@@ -332,12 +346,86 @@ extern "C" int smh_fusion_forward_f32(const smh_model *m, const float *d_xH, con
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0, "smh_fusion_forward_f32: d_work must start on a 16-byte boundary");
     hipStream_t st = (hipStream_t)stream;
     float *tap[2] = {static_cast<float *>(d_work), static_cast<float *>(d_work) + (size_t)N * (m->D / 2)};
-    const float *x[2] = {d_xH, d_xP};
+    const int rc = launch_fusion_trunks(m, d_xH, d_xP, N, tap[0], tap[1], ForwardOpts{}, st);
+    if (rc) return rc;
+    return launch_fusion_dense(m, N, tap[0], tap[1], d_out, false, st);
+}
+
+// ---- inference from the layer-0 partials: the fused pipeline from audio, and dense file-level inference ----
+// The feature kernel (smh_features_l0_f32) and l0_frames_kernel write per featuregram half its share of a 1x1 convolution with
+// rows [half * rows, + rows) of `w0`.  With w0 = smh_fusion_w0_ptr (trunk H's layer-0 kernel, then trunk P's) half 0 IS trunk H's
+// complete layer 0 and half 1 trunk P's: the trunks read them in the x0_one mode, nothing is added up.
+extern "C" const float *smh_fusion_w0_ptr(const smh_model *m) { return (m && m->heads == SMH_HEADS_FUSION) ? m->d_w0cat : nullptr; }
+
+extern "C" size_t smh_fusion_x0_workspace_bytes(const smh_model *m, int N) { return smh_fusion_workspace_bytes(m, N); }
+
+extern "C" int smh_fusion_forward_x0_f32(smh_model *m, const float *d_x0p, int N, void *d_work, size_t work_bytes, float *d_out,
+                                         void *stream) {
+    SMH_REQUIRE(m && d_x0p && d_out, "smh_fusion_forward_x0_f32: null argument");
+    SMH_REQUIRE(m->heads == SMH_HEADS_FUSION, "smh_fusion_forward_x0_f32: the model is not an intermediate-fusion model; a B3_MTL or "
+                "cascaded model takes smh_model_forward_x0_f32");
+    SMH_REQUIRE(N >= 0, "smh_fusion_forward_x0_f32: N=%d", N);
+    if (N == 0) return SMH_OK;
+    SMH_REQUIRE(d_work, "smh_fusion_forward_x0_f32: null workspace");
+    SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_x0p) % 16) == 0,
+                "smh_fusion_forward_x0_f32: d_x0p and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries");
+    SMH_REQUIRE(work_bytes >= smh_fusion_x0_workspace_bytes(m, N), "smh_fusion_forward_x0_f32: workspace of %zu bytes, %zu needed",
+                work_bytes, smh_fusion_x0_workspace_bytes(m, N));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t half = (size_t)m->D / 2;  // W * 32: one trunk's tap per patch = one half of a patch's partials
+    float *tap[2] = {static_cast<float *>(d_work), static_cast<float *>(d_work) + (size_t)N * half};
     ForwardOpts fo;
-    fo.trunk_only = 1;
-    for (int b = 0; b < 2; ++b) {
-        const int rc = launch_forward(m->trunk[b], x[b], N, d_out, tap[b], nullptr, st, fo);
+    fo.from_x0 = 1, fo.x0_one = 1;
+    const int rc = launch_fusion_trunks(m, d_x0p, d_x0p + half, N, tap[0], tap[1], fo, st);
+    if (rc) return rc;
+    return launch_fusion_dense(m, N, tap[0], tap[1], d_out, false, st);
+}
+
+// Dense file-level inference: the patches go through the trunks and the tail in chunks of kFusionDenseChunk, so the workspace is
+// [x0 (2, Tc, 32) | the two trunk taps of one chunk, (chunk, W, 32) each] whatever the length of the featuregram.
+constexpr int kFusionDenseChunk = 2048;  // (a multiple of 16: every chunk but the last fills whole row tiles of fusion_dense_kernel)
+
+extern "C" size_t smh_fusion_dense_workspace_bytes(const smh_model *m, int Tc, int shift) {
+    if (!m || m->heads != SMH_HEADS_FUSION || Tc < m->cfg.patch_size || shift < 1) return 0;
+    const int nP = smh_num_patches(Tc, m->cfg.patch_size, shift);
+    const size_t chunk = (size_t)std::min(std::max(nP, 0), kFusionDenseChunk);
+    return sizeof(float) * (2 * (size_t)Tc * C + chunk * m->D);
+}
+
+extern "C" int smh_fusion_forward_dense_f32(smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes,
+                                            float *d_out, void *stream) {
+    SMH_REQUIRE(m && d_fv && d_work && d_out, "smh_fusion_forward_dense_f32: null argument");
+    SMH_REQUIRE(m->heads == SMH_HEADS_FUSION, "smh_fusion_forward_dense_f32: the model is not an intermediate-fusion model; a B3_MTL or "
+                "cascaded model takes smh_model_forward_dense_f32");
+    const int W = m->cfg.patch_size, F = m->cfg.n_feat;
+    SMH_REQUIRE(shift >= 1 && Tc >= W, "smh_fusion_forward_dense_f32: needs shift >= 1 and at least patch_size=%d frames (Tc=%d, shift=%d); "
+                "shorter chunks are tiled by get_feature_patches and take smh_fusion_forward_f32", W, Tc, shift);
+    SMH_REQUIRE(F % 4 == 0, "smh_fusion_forward_dense_f32: the per-branch n_feat=%d must be a multiple of 4 (whole k steps per half)", F);
+    SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_fv) % 16) == 0 &&
+                    (reinterpret_cast<uintptr_t>(d_out) % 4) == 0,
+                "smh_fusion_forward_dense_f32: d_fv and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries");
+    SMH_REQUIRE(work_bytes >= smh_fusion_dense_workspace_bytes(m, Tc, shift), "smh_fusion_forward_dense_f32: workspace of %zu bytes, need %zu",
+                work_bytes, smh_fusion_dense_workspace_bytes(m, Tc, shift));
+    const int nP = smh_num_patches(Tc, W, shift);
+    if (nP <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    float *x0 = static_cast<float *>(d_work);
+    int rc = launch_l0_frames(d_fv, m->d_w0cat, x0, F, Tc, st);
+    if (rc) return rc;
+    const size_t half = (size_t)m->D / 2;
+    const int chunk = std::min(nP, kFusionDenseChunk);
+    float *tap[2] = {x0 + 2 * (size_t)Tc * C, x0 + 2 * (size_t)Tc * C + (size_t)chunk * half};
+    for (int p0 = 0; p0 < nP; p0 += chunk) {
+        const int n = std::min(chunk, nP - p0);
+        // patch p0 + i starts at min((p0 + i) shift, Tc - W): the window array advanced by p0 shift frames and shortened by as many
+        // (p0 shift <= Tc - W: patch p0's centre lies inside the featuregram)
+        const size_t adv = (size_t)p0 * shift;
+        ForwardOpts fo;
+        fo.from_x0 = 1, fo.x0_one = 1, fo.x0_shift = shift, fo.x0_T = Tc - (int)adv;
+        rc = launch_fusion_trunks(m, x0 + adv * C, x0 + ((size_t)Tc + adv) * C, n, tap[0], tap[1], fo, st);
+        if (rc) return rc;
+        rc = launch_fusion_dense(m, n, tap[0], tap[1], d_out + (size_t)p0 * m->out_dim, false, st);
         if (rc) return rc;
     }
-    return launch_fusion_dense(m, N, tap[0], tap[1], d_out, false, st);
+    return nP;
 }

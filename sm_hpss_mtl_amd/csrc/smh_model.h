@@ -39,6 +39,14 @@ struct TcnArgs {
     int head_sigmoid[kMaxHeads];
     int cascade;  // SMH_HEADS_CASCADED: heads S and M read BN18(concat[their Dropout(16), R's output]) (smh_tcn_heads.h)
     int trunk_only;  // 1: the forward ends at the trunk (its tap / saved activations); no Dense-on-trunk, no heads (the fusion model's trunks)
+    int x0_one;   // from_x0 with ONE partial per frame and channel: X (advanced by the caller to its half) already holds the complete
+                  // layer-0 product of this trunk and nothing but the bias is added.  The two addressing forms of the two-half mode:
+                  // packed (N, 2, T, 32) read at the full 2 T 32 patch stride, or with x0_shift windows of (x0_T, 32)
+    // A second trunk in the same grid (the fusion model; inference, trunk_only): with pair_Wb != nullptr the grid is (workgroups, 2)
+    // and the workgroups of row 1 read pair_X / pair_W0 / pair_Wb and write pair_trunk instead of the kernel's parameters; apart
+    // from that they do exactly what a launch of their own would
+    const float *pair_X, *pair_W0, *pair_Wb;
+    float *pair_trunk;
 };
 
 // training-mode extras of the forward kernel (all optional)
@@ -94,6 +102,8 @@ struct smh_model {
     float *d_Wb = nullptr;    // per-block packed weights
     float *d_WhA = nullptr;   // Dense-on-trunk weights in A-operand order + biases
     float *d_hp = nullptr;    // per-head BN / out params
+    float *d_w0cat = nullptr; // SMH_HEADS_FUSION: the layer-0 kernels of trunk H, then of trunk P, (2 n_feat, 32) in canonical layout -- the
+                              // `w0` of the feature kernel and of l0_frames_kernel (smh_fusion_w0_ptr); rebuilt by repack()
     int *d_map = nullptr;     // gather map: packed[i] = map[i] ? flat[map[i]-1] : 0 for [W0 | Wb | WhA | hp]
     size_t nW0, nWb, nWhA, nhp;
     // bf16 operand cache of smh_model_forward_bf16 (smh_tcn_bf16.hip): rebuilt when `version` moves
@@ -136,9 +146,17 @@ int forward_bf16_supported(const smh_model *m);  // smh_tcn_bf16.hip: SMH_OK, or
 struct ForwardOpts {
     int from_x0 = 0, x0_shift = 0, x0_T = 0;
     int trunk_only = 0;  // 1: the forward ends at the trunk (d_trunk tap / tio's saved activations); d_out is not written
+    int x0_one = 0;      // from_x0: d_x holds one complete layer-0 partial per frame (TcnArgs::x0_one), already advanced to its half
+    // a second trunk in the same grid (inference, trunk_only): `pair`'s operands, its input and its tap; same geometry as m
+    const smh_model *pair = nullptr;
+    const float *pair_x = nullptr;
+    float *pair_trunk = nullptr;
 };
 int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
                    hipStream_t st, const ForwardOpts &opt = {});
+// l0_frames_kernel (smh_tcn.hip): x0 (2, Tc, 32) = per half the 1x1 convolution of fv's rows [half * rows, + rows) (fv: (2 rows, Tc))
+// with w0's rows of the same range (w0: (2 rows, 32)); rows % 4 == 0
+int launch_l0_frames(const float *fv, const float *w0, float *x0, int rows, int Tc, hipStream_t st);
 // smh_fusion.hip: the layers behind the intermediate-fusion model's two trunks (SMH_HEADS_FUSION).
 // launch_fusion_dense: the Dense layers on the fused features; train = false: xh / xp = the trunk taps (N, W, 32), BN with the moving
 // statistics, out = the heads' outputs (N, out_dim); train = true: xh = xhat (N, D), out = pre (N, kPS) incl. biases.
@@ -150,6 +168,11 @@ size_t fusion_scratch_floats(const smh_model *m, int max_batch);
 int launch_fusion_train(const smh_model *m, int N, int max_batch, const float *acts_h, const float *acts_p, float *scratch,
                         float *bnstat, float *pd, float *grad, int phase, hipStream_t st);
 const float *fusion_gt(const smh_model *m, int max_batch, const float *scratch, int N, int b);
+// both trunks of a fusion model over N patches, ending at their taps (N, W, 32): one grid of (workgroups, 2), or two launches back to
+// back under SMH_FUSION_TWO_LAUNCH=1 (read per call; A/B runs and tests -- the two forms are bit-identical).  fo: the input mode;
+// xh / xp: each trunk's input, in the x0_one mode already advanced to its half
+int launch_fusion_trunks(const smh_model *m, const float *xh, const float *xp, int N, float *tap_h, float *tap_p, ForwardOpts fo,
+                         hipStream_t st);
 // smh_model_cfg.block_variant = 1 (smh_tcn_v2.hip): the two-convolution residual block of keras-tcn >= 2.8, inference only
 int launch_forward_v2(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, hipStream_t st);
 }  // namespace smh_tcn

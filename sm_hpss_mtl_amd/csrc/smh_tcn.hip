@@ -397,6 +397,7 @@ b3mtl_forward_kernel(TcnArgs a, const float *__restrict__ X, const float *__rest
     const int units = (GR + 15) >> 4;
     const int ZR = a.GRP;  // all-zero row behind the GRP activation rows of each buffer (padding taps of the dilated conv)
     float *xa = lds, *xb = lds + (size_t)(a.GRP + 1) * SX;
+    if (a.pair_Wb && blockIdx.y) X = a.pair_X, W0 = a.pair_W0, Wb = a.pair_Wb, trunk = a.pair_trunk;  // (uniform) second trunk of a paired launch
     const bool tracing = TRACE && a.trace != nullptr;
     if (tracing && blockIdx.x < 256 && threadIdx.x == 0) a.trace[4 * 3000 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 
@@ -415,7 +416,31 @@ b3mtl_forward_kernel(TcnArgs a, const float *__restrict__ X, const float *__rest
         const float *bias0 = W0 + (size_t)nW0;
         const f32x4 bl = *reinterpret_cast<const f32x4 *>(bias0 + 4 * q);
         const f32x4 bh = *reinterpret_cast<const f32x4 *>(bias0 + 16 + 4 * q);
-        if (a.from_x0) {
+        if (a.from_x0 && a.x0_one) {
+            // layer 0 of THIS trunk was computed in full by the feature kernel / l0_frames_kernel (the fusion model's trunks): one
+            // partial, add the bias.  X starts at this trunk's half; the packed form keeps the 2 T patch stride of (n, 2, T, 32)
+            constexpr int kX0R = 4;
+            const int n4 = GR * (C / 4);
+            for (int i0 = threadIdx.x; i0 < n4; i0 += kX0R * blockDim.x) {
+                f32x4 pa[kX0R];
+#pragma unroll
+                for (int r = 0; r < kX0R; ++r) {
+                    const int i = min(i0 + r * (int)blockDim.x, n4 - 1);
+                    const int R = i >> 3, c4 = (i & 7) * 4;
+                    const int g = R / T, t = R - g * T;
+                    const size_t first = a.x0_shift ? (size_t)min((n0 + g) * a.x0_shift, a.x0_T - T) : (size_t)(n0 + g) * 2 * T;
+                    pa[r] = *reinterpret_cast<const f32x4 *>(X + ((first + t) * C + c4));
+                }
+#pragma unroll
+                for (int r = 0; r < kX0R; ++r) {
+                    const int i = i0 + r * (int)blockDim.x;
+                    if (i < n4) {
+                        const int R = i >> 3, c4 = (i & 7) * 4;
+                        *reinterpret_cast<f32x4 *>(xa + (size_t)R * SX + c4) = pa[r] + *reinterpret_cast<const f32x4 *>(bias0 + c4);
+                    }
+                }
+            }
+        } else if (a.from_x0) {
             // layer 0 was computed by the feature kernel: sum its two per-half partials, add the bias
             // all loads of a thread in flight before the first sum (up to 4 rounds x 2 partials: one HBM latency, not four)
             constexpr int kX0R = 4;
@@ -1140,6 +1165,9 @@ int repack(smh_model *m, hipStream_t st) {
             SMH_CHECK_HIP(hipMemcpyAsync(m->trunk[b]->d_flat, m->d_flat + b * tf, tf * sizeof(float), hipMemcpyDeviceToDevice, st));
             const int rc = repack(m->trunk[b], st);
             if (rc) return rc;
+            // the layer-0 kernels of both trunks as one (2 n_feat, 32) array (smh_fusion_w0_ptr): each trunk's canonical block starts with it
+            const size_t k0 = (size_t)m->cfg.n_feat * C;
+            SMH_CHECK_HIP(hipMemcpyAsync(m->d_w0cat + b * k0, m->d_flat + b * tf, k0 * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
     }
     const size_t n = m->nW0 + m->nWb + m->nWhA + m->nhp;
@@ -1157,7 +1185,8 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     a.trunk_only = 0;
     a.tune = 0;
     a.trace = nullptr;
-    a.from_x0 = 0, a.x0_shift = 0, a.x0_T = 0;
+    a.from_x0 = 0, a.x0_shift = 0, a.x0_T = 0, a.x0_one = 0;
+    a.pair_X = a.pair_W0 = a.pair_Wb = nullptr, a.pair_trunk = nullptr;
     a.status = m->d_status, a.spin_limit = kSkewSpinLimit;
     a.D = m->D, a.NH = m->NH, a.n_mt = m->n_mt, a.n_classes = m->cfg.n_classes, a.n_heads = m->n_heads;
     a.out_dim = m->out_dim;
@@ -1208,6 +1237,15 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
     fill_args(m, N, &a, &lds);
     a.trunk_only = opt.trunk_only;
     a.from_x0 = opt.from_x0, a.x0_shift = opt.x0_shift, a.x0_T = opt.x0_T;
+    a.x0_one = opt.from_x0 ? opt.x0_one : 0;
+    if (opt.pair) {
+        const smh_model *p = opt.pair;
+        SMH_REQUIRE(!tio && opt.trunk_only && d_trunk && opt.pair_x && opt.pair_trunk, "paired trunk launch: inference to the trunk taps only");
+        SMH_REQUIRE(p->cfg.n_feat == m->cfg.n_feat && p->cfg.patch_size == m->cfg.patch_size && p->n_blocks == m->n_blocks &&
+                        p->cfg.n_dilations == m->cfg.n_dilations && p->nW0 == m->nW0 && p->nWb == m->nWb && p->nW0 > 0,
+                    "paired trunk launch: the two trunks differ in geometry");
+        a.pair_X = opt.pair_x, a.pair_W0 = p->d_W0, a.pair_Wb = p->d_Wb, a.pair_trunk = opt.pair_trunk;
+    }
     // timing probes (outputs invalid; training would read stale activations): only under SMH_ENABLE_PROBES=1, announced on stderr
     if (const char *ev = smh::probe_env("SMH_TCN_BLOCKS")) a.n_blocks = atoi(ev);  // tools/tune_model.py
     a.skip_heads = smh::probe_env("SMH_TCN_NOHEADS") ? 1 : 0;
@@ -1252,7 +1290,7 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
     // two waves of different SIMDs (half_tile_compute).  SMH_TCN_SPLIT=0 switches it off (tests: the two forms agree bit for bit).
     a.split_last = (!skew && prefetch && nwaves == 8 && units >= 2 && (units % 8 == 1 || units % 8 == 5)) ? 1 : 0;
     if (const char *ev = getenv("SMH_TCN_SPLIT")) a.split_last = a.split_last && atoi(ev) != 0;
-    const dim3 grid((N + a.G - 1) / a.G), block(64 * nwaves);
+    const dim3 grid((N + a.G - 1) / a.G, opt.pair ? 2 : 1), block(64 * nwaves);
     TrainIO io{nullptr, nullptr, nullptr, nullptr};
     if (tio) io = *tio;
 #define SMH_LAUNCH_FWD(TR, MD, TC)                                                                                      \
@@ -1371,6 +1409,8 @@ extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_m
     if (e == hipSuccess) e = hipMemset(m->d_flat, 0, n * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&m->d_status, sizeof(int));
     if (e == hipSuccess) e = hipMemset(m->d_status, 0, sizeof(int));
+    if (e == hipSuccess && heads == SMH_HEADS_FUSION) e = hipMalloc((void **)&m->d_w0cat, (size_t)2 * cfg->n_feat * C * sizeof(float));
+    if (e == hipSuccess && heads == SMH_HEADS_FUSION) e = hipMemset(m->d_w0cat, 0, (size_t)2 * cfg->n_feat * C * sizeof(float));
     if (e != hipSuccess) {
         smh_model_destroy(m);
         return smh::set_error(SMH_E_HIP, "smh_model_create: device allocation failed: %s", hipGetErrorString(e));
@@ -1398,6 +1438,7 @@ extern "C" void smh_model_destroy(smh_model *m) {
     (void)hipFree(m->d_map);
     (void)hipFree(m->d_bf16);
     (void)hipFree(m->d_status);
+    (void)hipFree(m->d_w0cat);
     smh_model_destroy(m->trunk[0]);
     smh_model_destroy(m->trunk[1]);
     delete m;
@@ -1485,6 +1526,13 @@ l0_frames_kernel(const float *__restrict__ fv, const float *__restrict__ w0, flo
 }
 }  // namespace
 
+namespace smh_tcn {
+int launch_l0_frames(const float *fv, const float *w0, float *x0, int rows, int Tc, hipStream_t st) {
+    hipLaunchKernelGGL(l0_frames_kernel, dim3((unsigned)((Tc + 63) / 64), 2), dim3(256), 0, st, fv, w0, x0, rows, Tc);
+    return smh::launch_status("l0_frames_kernel");
+}
+}  // namespace smh_tcn
+
 extern "C" size_t smh_model_dense_workspace_bytes(const smh_model *m, int Tc) {
     return (m && Tc > 0) ? sizeof(float) * 2 * (size_t)Tc * 32 : 0;
 }
@@ -1508,8 +1556,7 @@ extern "C" int smh_model_forward_dense_f32(const smh_model *m, const float *d_fv
     if (nP <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     float *x0 = static_cast<float *>(d_work);
-    hipLaunchKernelGGL(l0_frames_kernel, dim3((unsigned)((Tc + 63) / 64), 2), dim3(256), 0, st, d_fv, smh_model_w0_ptr(m), x0, F / 2, Tc);
-    int rc = smh::launch_status("l0_frames_kernel");
+    int rc = smh_tcn::launch_l0_frames(d_fv, smh_model_w0_ptr(m), x0, F / 2, Tc, st);
     if (rc) return rc;
     smh_tcn::ForwardOpts fo;
     fo.from_x0 = 1, fo.x0_shift = shift, fo.x0_T = Tc;

@@ -28,6 +28,19 @@ HALF_FEATS = {h + t: h + "HarmPercSpec" for h in ("Mel", "LogMel", "", "Log") fo
 STFT_PRECISIONS = {"f32": _lib.SMH_STFT_F32, "f64": _lib.SMH_STFT_F64}
 
 
+def _l0_kernel(model):
+    """(device address of the (rows_in, 32) layer-0 kernel the feature kernel multiplies by, rows_in) of a model with a fused
+    layer-0 path: B3MTL / cascaded -- its initial-conv kernel, rows_in = n_feat; FusionMTL -- trunk H's kernel followed by trunk
+    P's, rows_in = 2 * n_feat.  Anything else raises."""
+    from .model import HEADS_FUSION
+    model._sync_weights()
+    fusion = getattr(model, "HEADS", None) == HEADS_FUSION
+    w0 = model.lib.smh_fusion_w0_ptr(model._h) if fusion else model.lib.smh_model_w0_ptr(model._h)
+    if not w0:
+        raise ValueError("the model has no layer-0 kernel the feature kernel could apply (keras-tcn 2.3.x block only)")
+    return w0, (2 if fusion else 1) * model.n_feat
+
+
 @dataclass(frozen=True)
 class FrontendConfig:
     n_fft: int = 400
@@ -229,15 +242,17 @@ class Frontend:
 
     def features_l0(self, S, harm, perc, harm_layout, W, shift, model, out=None, patches=False):
         """`features` fused with the first layer of `model` (B3MTL): returns dict(fv, x0p (B*nP, 2, W, 32)[, patches]).
-        Feed x0p to `model.forward_from_x0`.  Same logits as features -> forward_device within f32 tolerance."""
+        Feed x0p to `model.forward_from_x0`.  Same logits as features -> forward_device within f32 tolerance.
+        A FusionMTL whose 2 * n_feat equals the featuregram's rows works too: half 0 of x0p is then trunk H's first layer,
+        half 1 trunk P's, and x0p goes to `model.forward_from_x0_halves`."""
         S, harm, perc = _f32c(S, "S"), _f32c(harm, "harm"), _f32c(perc, "perc")
         B, K, T = S.shape
         if int(harm_layout) == 2 and harm.numel() < B * self.lib.smh_harm_buffer_floats(K, T):
             raise ValueError("harm_layout 2 needs smh_harm_buffer_floats(K, T) floats per clip")
-        if model.n_feat != 2 * self.rows or model.patch_size != W:
+        w0, rows_in = _l0_kernel(model)
+        if rows_in != 2 * self.rows or model.patch_size != W:
             raise ValueError("model expects (W=%d, n_feat=%d), the front end produces (W=%d, n_feat=%d)"
-                             % (model.patch_size, model.n_feat, W, 2 * self.rows))
-        model._sync_weights()
+                             % (model.patch_size, rows_in, W, 2 * self.rows))
         nP = self.num_patches(T, W, shift)
         dev = S.device
         fv = _out(out, "fv", (B, 2 * self.rows, T), torch.float32, dev)
@@ -250,7 +265,7 @@ class Frontend:
             raise ValueError("out['maxkeys'] must be a contiguous int32 device tensor with at least 2*B = %d entries" % (2 * B))
         got = _lib.check(self.lib.smh_features_l0_f32(
             self._h, _ptr(S), _ptr(harm), _ptr(perc), int(harm_layout), B, T, W, shift, _ptr(fv), _ptr(pt),
-            C.c_void_p(self.lib.smh_model_w0_ptr(model._h)), _ptr(x0p), _ptr(keys), _stream()), "smh_features_l0_f32")
+            C.c_void_p(w0), _ptr(x0p), _ptr(keys), _stream()), "smh_features_l0_f32")
         assert got == nP
         return {"fv": fv, "x0p": x0p, "patches": pt, "n_patches": nP, "maxkeys": keys}
 

@@ -92,7 +92,8 @@ def smooth_labels(Predictions, PtdLabels, win_size, smooth_type="prediction"):
 
 def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000):
     """fv (2R, nFrames) HarmPerc featuregram of one file -> 1-D float32 numpy track of the chosen head's
-    probability, one value per patch, batches concatenated (DAFx12...:612-676)."""
+    probability, one value per patch, batches concatenated (DAFx12...:612-676).  model: B3MTL, cascaded, or FusionMTL (per-branch
+    n_feat = R; the file-wise predict of Intermediate_Fusion_Results.py:441-590)."""
     fe = _frontend()
     d = _dev(fv)
     if d.dim() != 2 or d.shape[0] % 2:
@@ -106,9 +107,12 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
             break
         col += o.shape[1]
     R = d.shape[0] // 2
+    # the intermediate-fusion model reads the two halves as two inputs; its n_feat is the per-branch width
+    fusion = hasattr(model, "forward_from_x0_halves")
+    rows_ok = d.shape[0] == (2 if fusion else 1) * getattr(model, "n_feat", d.shape[0])
     # batches longer than a patch skip the (nP, W, 2R) patch tensor (648 MB per 10 000 frames at W = 68, hop 1) when the model has
     # the entry for it; SMH_DENSE_PATCHES=1 keeps the patch path (A/B, tests)
-    dense = (hasattr(model, "forward_dense") and getattr(model, "block_variant", 1) == 0 and d.shape[0] % 8 == 0
+    dense = (hasattr(model, "forward_dense") and getattr(model, "block_variant", 1) == 0 and d.shape[0] % 8 == 0 and rows_ok
              and getattr(model, "patch_size", None) == W and not os.environ.get("SMH_DENSE_PATCHES"))
     d = fe.standardize_rows(d)  # :612-626, whole file; the scaler works row by row, so the two halves are one call
     T = d.shape[1]
@@ -129,7 +133,7 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
         p = fe.extract_patches(fe.standardize_rows(chunk[R:])[None], W, W_shift, time_major=True)
         if h.shape[0] == 0:
             continue
-        x = torch.cat([h, p], dim=2)
+        x = [h, p] if fusion else torch.cat([h, p], dim=2)  # (the fusion model takes the halves as they are: no copy)
         preds.append(model.forward_device(x)[:, col])
     if not preds:
         return np.zeros((0,), np.float32)

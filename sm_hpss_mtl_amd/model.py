@@ -396,8 +396,10 @@ class FusionMTL(B3MTL):
     'harm_input' / 'perc_input', each (N, W, n_feat) time-major, two independent keras-tcn 2.3 trunks ('tcn_initial_conv_H' /
     '_P', one build-time spatial dropout rate, independent masks), x = BatchNormalization(concat[Flatten(trunk H), Flatten(trunk
     P)]), then B3_MTL's '3C' and heads on x.  Outputs [S, M, (N,) R, 3C] like B3_MTL.  `x` is [x_H, x_P] or {'harm_input': x_H,
-    'perc_input': x_P}.  The same surface as B3MTL; the bf16 paths, the fused-x0 and dense file-level forwards, the keras-tcn 2.8
-    block and the single-head sub-model are B3_MTL only."""
+    'perc_input': x_P}.  The same surface as B3MTL.  Inference without materialised halves: `forward_from_x0_halves` on the per-half
+    layer-0 partials of `Frontend.features_l0(..., model=self)` (what `pipeline.HotPath` runs), and `forward_dense` on a whole H||P
+    featuregram (2 * n_feat, Tc) (what `inference.patch_probabilities` runs).  `forward_from_x0` (which adds the two partials up),
+    the bf16 paths, the trunk tap, the keras-tcn 2.8 block and the single-head sub-model are B3_MTL only."""
 
     HEADS = HEADS_FUSION
     CLASS_NAME = "B3_MTL_Intermediate_Fusion"
@@ -461,10 +463,67 @@ class FusionMTL(B3MTL):
         return out
 
     def forward_from_x0(self, *args, **kwargs):
-        raise ValueError("the intermediate-fusion model has no fused layer-0 path (two inputs): use forward_device")
+        raise ValueError("the intermediate-fusion model does not add the two layer-0 partials up (its trunks take one half each): "
+                         "use forward_from_x0_halves, or forward_device on the two inputs")
 
-    def forward_dense(self, *args, **kwargs):
-        raise ValueError("the intermediate-fusion model has no dense file-level path: build the patches and use forward_device")
+    def w0_ptr(self):
+        """Device address of the (2 * n_feat, 32) layer-0 kernels, trunk H's then trunk P's (smh_fusion_w0_ptr): the `w0` of
+        Frontend.features_l0 for this model.  Follows the weights."""
+        self._sync_weights()
+        return self.lib.smh_fusion_w0_ptr(self._h)
+
+    def forward_from_x0_halves(self, x0p, out=None):
+        """x0p (N, 2, W, 32) as Frontend.features_l0(..., model=self) wrote it -- half 0 is trunk H's complete first layer, half 1
+        trunk P's -- -> (N, out_dim) on the device (smh_fusion_forward_x0_f32).  The same logits as forward_device on the two halves
+        of the patches within f32 tolerance."""
+        if not (isinstance(x0p, torch.Tensor) and x0p.is_cuda and x0p.dtype == torch.float32):
+            raise TypeError("forward_from_x0_halves expects a float32 CUDA tensor")
+        if x0p.dim() != 4 or tuple(x0p.shape[1:]) != (2, self.patch_size, 32):
+            raise ValueError("expected (N, 2, %d, 32), got %s" % (self.patch_size, tuple(x0p.shape)))
+        x0p = x0p.contiguous()
+        self._sync_weights()
+        N = x0p.shape[0]
+        if out is None:
+            out = torch.empty((N, self.out_dim), dtype=torch.float32, device=x0p.device)
+        elif tuple(out.shape) != (N, self.out_dim):
+            raise ValueError("out must be (%d, %d)" % (N, self.out_dim))
+        if N == 0:
+            return out
+        nbytes = self.lib.smh_fusion_x0_workspace_bytes(self._h, N)
+        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=x0p.device)
+        _lib.check(self.lib.smh_fusion_forward_x0_f32(self._h, C.c_void_p(x0p.data_ptr()), N, C.c_void_p(work.data_ptr()), nbytes,
+                                                      C.c_void_p(out.data_ptr()), _lib.current_stream()), "smh_fusion_forward_x0_f32")
+        return out
+
+    def forward_dense(self, fv, shift=1, out=None):
+        """Every hop-`shift` patch of a standardised featuregram batch fv (2 * n_feat, Tc) -- the H||P featuregram exactly as
+        B3MTL.forward_dense takes it: H rows, then P rows -- through the network without building the patches or their halves
+        (smh_fusion_forward_dense_f32): layer 0 of both trunks once per frame, every patch a window of it.  Returns (nP, out_dim), nP
+        = tools.extract_patches' count for Tc frames.  Needs Tc >= patch_size and n_feat % 4 == 0."""
+        if not (isinstance(fv, torch.Tensor) and fv.is_cuda and fv.dtype == torch.float32):
+            raise TypeError("forward_dense expects a float32 CUDA tensor")
+        if fv.dim() != 2 or fv.shape[0] != 2 * self.n_feat:
+            raise ValueError("expected the H||P featuregram (%d, Tc), got %s" % (2 * self.n_feat, tuple(fv.shape)))
+        fv = fv.contiguous()
+        Tc = int(fv.shape[1])
+        self._sync_weights()
+        nP = self.lib.smh_num_patches(Tc, self.patch_size, int(shift)) if Tc >= self.patch_size else -1
+        if nP < 0:
+            raise ValueError("forward_dense needs shift >= 1 and at least patch_size=%d frames, got Tc=%d shift=%d" % (self.patch_size, Tc, shift))
+        if out is None:
+            out = torch.empty((nP, self.out_dim), dtype=torch.float32, device=fv.device)
+        elif tuple(out.shape) != (nP, self.out_dim):
+            raise ValueError("out must be (%d, %d)" % (nP, self.out_dim))
+        if nP == 0:
+            return out
+        nbytes = self.lib.smh_fusion_dense_workspace_bytes(self._h, Tc, int(shift))
+        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=fv.device)
+        got = _lib.check(self.lib.smh_fusion_forward_dense_f32(
+            self._h, C.c_void_p(fv.data_ptr()), Tc, int(shift), C.c_void_p(work.data_ptr()), nbytes, C.c_void_p(out.data_ptr()),
+            _lib.current_stream()), "smh_fusion_forward_dense_f32")
+        if got != nP:
+            raise RuntimeError("smh_fusion_forward_dense_f32 produced %d patches, expected %d" % (got, nP))
+        return out
 
     def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
         """model.predict([x_H, x_P]) -> [S, M, (N,) R, 3C] numpy arrays (Intermediate_Fusion_Results.py)."""

@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .model import HEADS_FUSION
 
 STAGES = ("stft", "median", "features", "model")
 
@@ -31,7 +32,12 @@ class HotPath:
         ends with the featuregram; no patches, no logits).  fuse_l0: the network's first 1x1 convolution runs inside the feature kernel
         (smh_features_l0_f32 + smh_model_forward_x0_f32) instead of patches -> smh_model_forward_f32.
         keep_patches / keep_trunk: also write the standardised time-major patches / the TCN output (N, W, 32) -- parity taps
-        that `model.predict` does not return; never set by bench.py."""
+        that `model.predict` does not return; never set by bench.py.
+        model may be a FusionMTL whose 2 * n_feat equals the featuregram's rows (f32, no trunk tap).  fuse_l0=True: the feature
+        kernel applies both trunks' first layers (smh_fusion_w0_ptr) and the model starts from the per-half partials
+        (forward_from_x0_halves); nothing of the patches is built.  fuse_l0=False: patches -> their two halves -> forward_device;
+        the halves of a (N, W, 2 * n_feat) patch tensor are strided views, so this path COPIES them into two contiguous tensors
+        every step (preallocated; the model's C ABI takes contiguous inputs)."""
         self.fe, self.model, self.lib, self._h = fe, model, fe.lib, fe._h
         self.B, self.n_samples, self.W = int(batch), int(n_samples), int(patch)
         self.shift = int(patch if shift is None else shift)
@@ -39,12 +45,18 @@ class HotPath:
         if model_dtype not in ("f32", "bf16"):
             raise ValueError("model_dtype must be 'f32' or 'bf16'")
         self.fuse_l0 = bool(fuse_l0) and model is not None  # both network dtypes start from the layer-0 partials
+        self.fusion = model is not None and getattr(model, "HEADS", None) == HEADS_FUSION
+        if self.fusion and model_dtype != "f32":
+            raise ValueError("the intermediate-fusion model has the f32 forward only, got model_dtype=%r" % (model_dtype,))
+        if self.fusion and keep_trunk:
+            raise ValueError("the intermediate-fusion model has no trunk tap (keep_trunk)")
+        rows_in = (2 if self.fusion else 1) * model.n_feat if model is not None else 0
         self.T = fe.num_frames(self.n_samples)
         if self.T < 1:
             raise ValueError("clip of %d samples is shorter than n_fft=%d" % (n_samples, fe.cfg.n_fft))
-        if model is not None and (model.n_feat != 2 * fe.rows or model.patch_size != self.W):
+        if model is not None and (rows_in != 2 * fe.rows or model.patch_size != self.W):
             raise ValueError("model expects (W=%d, n_feat=%d), the front end produces (W=%d, n_feat=%d)"
-                             % (model.patch_size, model.n_feat, self.W, 2 * fe.rows))
+                             % (model.patch_size, rows_in, self.W, 2 * fe.rows))
         self.nP = fe.num_patches(self.T, self.W, self.shift) if model is not None else 0
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         B, K, T, F = self.B, fe.K, self.T, 2 * fe.rows
@@ -57,6 +69,9 @@ class HotPath:
         need_patches = (keep_patches or not self.fuse_l0) and model is not None
         self.patches = torch.empty((B * self.nP, self.W, F), **f32) if need_patches else None
         self.x0p = torch.empty((B * self.nP, 2, self.W, 32), **f32) if self.fuse_l0 else None
+        # fusion model on patches: the contiguous copies of the two halves
+        self.halves = ([torch.empty((B * self.nP, self.W, F // 2), **f32) for _ in range(2)]
+                       if self.fusion and not self.fuse_l0 else None)
         self.logits = torch.empty((B * self.nP, model.out_dim), **f32) if model is not None else None
         self.trunk = torch.empty((B * self.nP, self.W, 32), **f32) if (keep_trunk and model_dtype == "f32" and model is not None) else None
         # harmonic median layout: 16-frame blocks when the single feature kernel takes the clip, else time-major
@@ -85,9 +100,10 @@ class HotPath:
         if record is not None:
             record[2].record()
         if self.fuse_l0:
+            w0 = lib.smh_fusion_w0_ptr(m._h) if self.fusion else lib.smh_model_w0_ptr(m._h)
             got = _lib.check(lib.smh_features_l0_f32(h, _p(self.S), _p(self.harm), _p(self.perc), lay, self.B, self.T,
                                                      self.W, self.shift, _p(self.fv), _p(self.patches),
-                                                     C.c_void_p(lib.smh_model_w0_ptr(m._h)), _p(self.x0p),
+                                                     C.c_void_p(w0), _p(self.x0p),
                                                      _p(self.maxkeys), st), "smh_features_l0_f32")
         else:
             got = _lib.check(lib.smh_features_ex_f32(h, _p(self.S), _p(self.harm), _p(self.perc), lay, self.B, self.T,
@@ -101,7 +117,15 @@ class HotPath:
             if record is not None:
                 record[4].record()
             return self.fv
-        if self.fuse_l0:
+        if self.fusion:
+            if self.fuse_l0:
+                m.forward_from_x0_halves(self.x0p, out=self.logits)
+            else:
+                R = self.patches.shape[2] // 2
+                self.halves[0].copy_(self.patches[:, :, :R])
+                self.halves[1].copy_(self.patches[:, :, R:])
+                m.forward_device(self.halves, out=self.logits)
+        elif self.fuse_l0:
             m.forward_from_x0(self.x0p, out=self.logits, trunk=self.trunk, dtype=self.model_dtype)
         else:
             m.forward_device(self.patches, out=self.logits, trunk=self.trunk, dtype=self.model_dtype)
