@@ -5,8 +5,8 @@
   get_Jang_MTL_model         lib/proposed_architectures.py:650-764
 
 The layer graph, the parameter table (names, Keras shapes, order) and all arithmetic live in libsmh.so
-(csrc/smh_cnn.hip); this class only keeps the host copy of the weights, initialises them the way the reference's
-initialisers do, and moves tensors.  Training (`fit` / `train_on_batch` / `evaluate`, cnn_training.py over
+(csrc/smh_cnn.hip); this class initialises the weights the way the reference's initialisers do and moves tensors; the
+weight store, the Keras weight surface and `predict` are host.HostModel's, shared with model.B3MTL.  Training (`fit` / `train_on_batch` / `evaluate`, cnn_training.py over
 `smh_cnn_train_step_f32`) is built for all three.
 """
 from __future__ import annotations
@@ -19,17 +19,19 @@ import numpy as np
 import torch
 
 from . import _lib
-from .persistence import ModelSurfaceMixin
 from .cnn_training import CnnTrainingMixin
-from .model import head_spec
+from .host import HostModel, f32_cuda, ptr
 
 KINDS = {"Doukhan": 0, "Papakostas": 1, "Jang": 2}
 # initial learning rates returned next to the model (proposed_architectures.py:499, 574, 751)
 LEARNING_RATE = {"Doukhan": 0.0001, "Papakostas": 0.001, "Jang": 0.001}
 
 
-class CnnMTL(CnnTrainingMixin, ModelSurfaceMixin):
+class CnnMTL(CnnTrainingMixin, HostModel):
     """`model` object of get_{Doukhan,Papakostas,Jang}_MTL_model."""
+
+    _C_PREFIX = "smh_cnn"
+    _TRAINER_PREFIX = "smh_cnn_trainer"
 
     def __init__(self, kind, input_shape, n_classes=3, seed=None, n_mels=120, n_fft=512, fs=16000, fc_width=0,
                  loss_weights=None):
@@ -55,24 +57,13 @@ class CnnMTL(CnnTrainingMixin, ModelSurfaceMixin):
         for i in range(self.lib.smh_cnn_num_tensors(self._h)):
             _lib.check(self.lib.smh_cnn_tensor_info(self._h, i, name, 96, shape, C.byref(nd), C.byref(off)),
                        "smh_cnn_tensor_info")
+            assert int(off.value) == self.count_params()  # offsets are the running sum of the sizes: the store slices by it
             self._spec.append((name.value.decode(), tuple(shape[:nd.value]), int(off.value)))
         self.weights = OrderedDict()
         self._init_weights(np.random.default_rng(seed))
-        assert self.count_params() == self.lib.smh_cnn_num_params(self._h)
-        self._dirty = True
-        self._device_newer = False
+        self._init_store()
         self.loss_weights = loss_weights
         self._init_training_state()
-
-    def __del__(self):
-        tr = getattr(self, "_trainer", None)
-        if tr:
-            self.lib.smh_cnn_trainer_destroy(tr)
-            self._trainer = None
-        h = getattr(self, "_h", None)
-        if h:
-            self.lib.smh_cnn_destroy(h)
-            self._h = None
 
     # ---- initialisers of the reference ---------------------------------------------------------------------------
     def _init_weights(self, rng):
@@ -116,66 +107,8 @@ class CnnMTL(CnnTrainingMixin, ModelSurfaceMixin):
 
     # ---- Keras-style surface -------------------------------------------------------------------------------------
     @property
-    def output_names(self):
-        return [n for n, _, _ in head_spec(self.n_classes)] + ["3C"]
-
-    @property
-    def metrics_names(self):
-        return ["loss"] + [n + "_loss" for n in self.output_names] + ["3C_accuracy"]
-
-    @property
     def input_shape(self):
         return (None, self.in_h, self.in_w, 1)
-
-    def count_params(self):
-        return int(sum(int(np.prod(s)) for _, s, _ in self._spec))
-
-    def weight_names(self):
-        return [n for n, _, _ in self._spec]
-
-    def _pull_weights(self):
-        """After training steps the device copy is the master: refresh the host dict from it."""
-        if self._device_newer:
-            flat = np.empty(self.count_params(), np.float32)
-            _lib.check(self.lib.smh_cnn_get_weights(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
-                                                    _lib.current_stream()),
-                       "smh_cnn_get_weights")
-            for name, shape, off in self._spec:
-                self.weights[name] = flat[off:off + int(np.prod(shape))].reshape(shape).copy()
-            self._device_newer = False
-
-    def get_weights(self):
-        self._pull_weights()
-        return [self.weights[n].copy() for n, _, _ in self._spec]
-
-    def get_weights_dict(self):
-        self._pull_weights()
-        return self.weights
-
-    def set_weights(self, arrays):
-        arrays = list(arrays)
-        if len(arrays) != len(self._spec):
-            raise ValueError("set_weights: expected %d arrays, got %d" % (len(self._spec), len(arrays)))
-        for (name, shape, _), a in zip(self._spec, arrays):
-            a = np.asarray(a, dtype=np.float32)
-            if a.shape != tuple(shape):
-                raise ValueError("set_weights: %s expects shape %s, got %s" % (name, shape, a.shape))
-            self.weights[name] = a.copy()
-        self._dirty = True
-        self._device_newer = False
-
-    def set_weights_dict(self, d):
-        self.set_weights([d[n] for n, _, _ in self._spec])
-
-    def save_weights(self, path):
-        """`.h5` / `.hdf5`: HDF5 in Keras' weight-file layout (persistence.py); otherwise `<path>.npz`."""
-        from .persistence import save_weights_file
-        self._pull_weights()
-        return save_weights_file(path, self.weights)
-
-    def load_weights(self, path):
-        from .persistence import load_weights_file
-        self.set_weights_dict(load_weights_file(path))
 
     def to_json(self):
         return json.dumps({"class_name": self.kind + "_MTL", "config": {
@@ -183,59 +116,27 @@ class CnnMTL(CnnTrainingMixin, ModelSurfaceMixin):
             "n_fft": self.n_fft, "fs": self.fs, "fc_width": self.fc_width, "outputs": self.output_names}})
 
     def summary(self, print_fn=print):
-        print_fn("Model: %s_MTL, input (None, %d, %d, 1)" % (self.kind, self.in_h, self.in_w))
-        for name, shape, _ in self._spec:
-            print_fn("  %-40s %-22s %d" % (name, str(tuple(shape)), int(np.prod(shape))))
-        print_fn("Total params: %d" % self.count_params())
+        self._summary("Model: %s_MTL, input (None, %d, %d, 1)" % (self.kind, self.in_h, self.in_w), print_fn, width=22)
 
     # ---- inference -----------------------------------------------------------------------------------------------
-    def _sync_weights(self):
-        if self._dirty:
-            flat = np.concatenate([self.weights[n].ravel() for n, _, _ in self._spec]).astype(np.float32)
-            _lib.check(self.lib.smh_cnn_set_weights(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
-                                                    _lib.current_stream()),
-                       "smh_cnn_set_weights")
-            self._dirty = False
+    def _check_images(self, x):
+        """(N, H, W) or (N, H, W, 1) -> contiguous (N, H, W)."""
+        if x.dim() == 4 and x.shape[3] == 1:
+            x = x[..., 0]
+        if x.dim() != 3 or x.shape[1] != self.in_h or x.shape[2] != self.in_w:
+            raise ValueError("expected input (N, %d, %d[, 1]), got %s" % (self.in_h, self.in_w, tuple(x.shape)))
+        return x.contiguous()
 
     def forward_device(self, x, out=None, features=None, dtype="f32"):
         """x: float32 CUDA tensor (N, H, W) or (N, H, W, 1) -> (N, out_dim) [S|M|(N)|R|3C] on the device.
         dtype="bf16": bf16 GEMM operands with f32 accumulation (smh_cnn_forward_bf16) -- faster, not the parity path."""
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' or 'bf16'")
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
-            raise TypeError("forward_device expects a float32 CUDA tensor")
-        if x.dim() == 4 and x.shape[3] == 1:
-            x = x[..., 0]
-        x = x.contiguous()
-        if x.dim() != 3 or x.shape[1] != self.in_h or x.shape[2] != self.in_w:
-            raise ValueError("expected input (N, %d, %d[, 1]), got %s" % (self.in_h, self.in_w, tuple(x.shape)))
+        x = self._check_images(f32_cuda(x, "forward_device"))
         self._sync_weights()
         N = x.shape[0]
-        if out is None:
-            out = torch.empty((N, self.out_dim), dtype=torch.float32, device=x.device)
+        out = self._out(out, N, x.device)
         nbytes = self.lib.smh_cnn_workspace_bytes(self._h, N)
         work = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=x.device)
-        fn = self.lib.smh_cnn_forward_f32 if dtype == "f32" else self.lib.smh_cnn_forward_bf16
-        _lib.check(fn(
-            self._h, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()),
-            None if features is None else C.c_void_p(features.data_ptr()), C.c_void_p(work.data_ptr()), work.numel(),
-            _lib.current_stream()), "smh_cnn_forward_" + dtype)
+        self._call("smh_cnn_forward_" + dtype, self._h, ptr(x), N, ptr(out), ptr(features), ptr(work), work.numel())
         return out
-
-    def split_outputs(self, out):
-        res, col = [], 0
-        for _, odim, _ in head_spec(self.n_classes):
-            res.append(out[:, col:col + odim])
-            col += odim
-        res.append(out[:, col:col + self.n_classes])
-        return res
-
-    def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
-        """model.predict(x=batchData) -> [S, M, (N,) R, 3C] numpy arrays (Proposed_Work_Results.py:520,586)."""
-        if isinstance(x, np.ndarray):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        elif x.dtype != torch.float32:
-            x = x.float()
-        out = self.forward_device(x.cuda(), dtype=dtype)
-        host = out.cpu().numpy()  # one copy for all outputs
-        return [np.ascontiguousarray(o) for o in self.split_outputs(host)]

@@ -10,49 +10,55 @@ from __future__ import annotations
 
 import ctypes as C
 
+import os
+
 import numpy as np
 import torch
 
-import os
-
 from . import _lib
 from . import optimizers as _opt
-from .training import HEAD_DROPOUT, TrainingMixin, _cur_stream
+from .host import to_f32_cuda
+from .training import HEAD_DROPOUT, TrainingMixin, _p
 
 
 class CnnTrainingMixin(TrainingMixin):
-    """Mixed into sm_hpss_mtl_amd.cnn_models.CnnMTL; compile / fit / evaluate / pack_targets come from TrainingMixin."""
+    """Mixed into sm_hpss_mtl_amd.cnn_models.CnnMTL: the step over `smh_cnn_trainer_*`; compile / fit / evaluate / pack_targets and
+    the trainer's life cycle come from TrainingMixin."""
 
-    _TRAINER_API = ("smh_cnn_trainer_create", "smh_cnn_trainer_destroy", "smh_cnn_trainer_copy_state", "smh_cnn_trainer_grad_ptr",
-                    "smh_cnn_trainer_bucket_floats")
     _MIN_TRAINER_CAP = 48
+    deterministic_gradients = True  # the trainer sums its weight gradients in ordered partials: bit-reproducible as it stands
 
     def _init_training_state(self):
-        self._trainer = None
-        self._trainer_cap = 0
-        self._grad_view = None
-        self._drop_spec = []
-        self.iterations = 0
-        self.stop_training = False
         if self.kind == "Papakostas":  # lib/proposed_architectures.py:572-574
-            self.optimizer = _opt.SGD(learning_rate=_opt.ExponentialDecay(self.initial_learning_rate, 700, 0.1))
+            optimizer = _opt.SGD(learning_rate=_opt.ExponentialDecay(self.initial_learning_rate, 700, 0.1))
         else:                           # :499-500 (Doukhan, 1e-4), :750-751 (Jang, 1e-3)
-            self.optimizer = _opt.Adam(learning_rate=self.initial_learning_rate)
+            optimizer = _opt.Adam(learning_rate=self.initial_learning_rate)
+        super()._init_training_state(optimizer)
+        self._drop_spec = []
         self._rng = torch.Generator(device="cuda")
         self._rng.manual_seed(1234 + int(os.environ.get("RANK", "0")))
+
+    @property
+    def train_dtype(self):
+        return "f32"
+
+    @train_dtype.setter
+    def train_dtype(self, dtype):
+        if dtype not in ("f32", "bf16"):
+            raise ValueError("train_dtype must be 'f32' or 'bf16', got %r" % (dtype,))
+        if dtype == "bf16":
+            raise ValueError("train_dtype='bf16' exists for the B3_MTL trainer only")
 
     def _set_optimizer(self, optimizer):
         if optimizer.kind not in ("sgd", "adam"):
             raise ValueError("the Conv2D MTL models train with SGD or Adam (as the reference compiles them), not %s" % optimizer.kind)
         if optimizer.clipnorm:
             raise ValueError("clipnorm is not part of the Conv2D MTL models' optimisers")
-        self.optimizer = optimizer
-        self.iterations = 0
-        self._reset_optimizer_state()
+        super()._set_optimizer(optimizer)
 
     def _reset_optimizer_state(self):
         if self._trainer is not None:  # a new trainer starts from zeroed moments and step 0
-            self.lib.smh_cnn_trainer_destroy(self._trainer)
+            self._trainer_c("_destroy")(self._trainer)
             self._trainer, self._trainer_cap, self._grad_view = None, 0, None
 
     def _n_losses(self):
@@ -81,26 +87,17 @@ class CnnTrainingMixin(TrainingMixin):
 
     def gradients(self):
         """dict name -> gradient of the last train_on_batch(apply=False) (before grad_scale and the l2 term)."""
-        flat = self._grad_tensor().cpu().numpy()
-        return {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, shape, off in self._spec}
+        return self._flat_to_dict(self._grad_tensor().cpu().numpy())
 
     def train_on_batch(self, x, y, drop="auto", drop_heads="auto", apply=True, sync=True):
         """One optimiser step.  Returns [loss, <per-output losses>, 3C_accuracy] like Keras (sync=False: the raw device
         tensor of the step's losses, see TrainingMixin.losses_to_list).
         drop: "auto" draws masks with the model's rates, None disables dropout, or a list of (N, dim_i) mask tensors
         (0 or 1/(1-rate_i)) in graph order; drop_heads likewise with one (N, n_heads, 16) tensor."""
-        if isinstance(x, np.ndarray):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        x = x.to(device="cuda", dtype=torch.float32)
-        if x.dim() == 4 and x.shape[3] == 1:
-            x = x[..., 0]
-        x = x.contiguous()
+        x = self._check_images(to_f32_cuda(x))
         n = x.shape[0]
-        if x.dim() != 3 or x.shape[1] != self.in_h or x.shape[2] != self.in_w:
-            raise ValueError("expected input (N, %d, %d[, 1]), got %s" % (self.in_h, self.in_w, tuple(x.shape)))
-        yt = y if (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() == 2) else self.pack_targets(y)
-        self._sync_weights()
-        tr = self._get_trainer(n)
+        yt = self._device_targets(y)
+        tr, losses = self._begin_step(n)
         n_heads = len(self.output_names) - 1
         if isinstance(drop, str):
             drop = [(torch.rand((n, d), device="cuda", generator=self._rng) < 1.0 - r).float() / (1.0 - r)
@@ -120,10 +117,7 @@ class CnnTrainingMixin(TrainingMixin):
             drop_heads = (torch.rand((n, n_heads, 16), device="cuda", generator=self._rng) < keep).float() / keep
         elif drop_heads is not None:
             drop_heads = torch.as_tensor(drop_heads, dtype=torch.float32).to("cuda")
-        losses = torch.empty(self._n_losses(), dtype=torch.float32, device="cuda")
-        p = lambda t: None if t is None else C.c_void_p(t.contiguous().data_ptr())  # noqa: E731
-        _lib.check(self.lib.smh_cnn_train_step_f32(tr, p(x), p(yt), n, p(drop), p(drop_heads), self._loss_weight_array(),
-                                                   p(losses), _cur_stream()), "smh_cnn_train_step_f32")
+        self._call("smh_cnn_train_step_f32", tr, _p(x), _p(yt), n, _p(drop), _p(drop_heads), self._loss_weight_array(), _p(losses))
         if apply:
             self.apply_gradients()
         return self.losses_to_list(losses) if sync else losses
@@ -132,6 +126,5 @@ class CnnTrainingMixin(TrainingMixin):
         """The optimiser update on the device (the all-reduce of the bucket happens in TrainingMixin.apply_gradients)."""
         o = self.optimizer
         adam = o.kind == "adam"
-        _lib.check(self.lib.smh_cnn_trainer_apply_f32(self._trainer, 1 if adam else 0, lr, o.beta_1 if adam else o.momentum,
-                                                      getattr(o, "beta_2", 0.999), getattr(o, "epsilon", 1e-7), scale,
-                                                      _cur_stream()), "smh_cnn_trainer_apply_f32")
+        self._call("smh_cnn_trainer_apply_f32", self._trainer, 1 if adam else 0, lr, o.beta_1 if adam else o.momentum,
+                   getattr(o, "beta_2", 0.999), getattr(o, "epsilon", 1e-7), scale)

@@ -12,7 +12,9 @@ Weights are kept on the host as float32 numpy arrays in CANONICAL order (Keras a
    moving_variance and an out kernel of shape (18, 1))
   (FusionMTL: two trunks 'tcn_H/...' and 'tcn_P/...' in place of 'tcn/...', then the fused BatchNorm 'fusion_bn' gamma, beta,
    moving_mean, moving_variance (2*T*32 each); '3C' and the heads read the 2*T*32 fused features)
-and uploaded (re-packed into MFMA operand order by libsmh) whenever they change.
+and uploaded (re-packed into MFMA operand order by libsmh) whenever they change: the weight store, the Keras weight surface,
+`predict` and the call helpers are host.HostModel's, shared with cnn_models.CnnMTL; the training surface is
+training.TcnTrainingMixin's.
 """
 from __future__ import annotations
 
@@ -24,21 +26,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .persistence import ModelSurfaceMixin
-from .training import TrainingMixin
+from .host import HEADS_CASCADED, HEADS_FUSION, HEADS_MTL, HostModel, f32_cuda, head_spec, ptr, to_f32_cuda, workspace
+from .training import TcnTrainingMixin
 
-
-HEADS_MTL, HEADS_CASCADED, HEADS_FUSION = 0, 1, 2  # include/smh.h: SMH_HEADS_MTL / SMH_HEADS_CASCADED / SMH_HEADS_FUSION
 CAT = 18  # cascaded heads: width of concat[Dropout(16) of S or M, R's two outputs]
-
-
-def head_spec(n_classes: int, heads: int = HEADS_MTL):
-    """(name, out_dim, activation) of the auxiliary heads in Keras output order
-    (proposed_architectures.py:25-80,154; 5_class_classification.py:150-215,286).  The cascaded model
-    (cascade_MTL_modifications, :175-234) has S, M, R[2] whatever n_classes is."""
-    if n_classes == 5 and heads != HEADS_CASCADED:  # (the intermediate-fusion model has MTL_modifications' heads)
-        return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("N", 1, "sigmoid"), ("R", 3, "linear")]
-    return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("R", 2, "linear")]
 
 
 def weight_spec(n_feat, patch_size, n_classes, nb_filters=32, kernel_size=3, nb_stacks=3, n_dil=8, block_variant=0,
@@ -114,11 +105,11 @@ def initial_weights(n_feat=240, patch_size=68, n_classes=3, seed=None, nb_filter
     return dropout_rate, weights
 
 
-class B3MTL(TrainingMixin, ModelSurfaceMixin):
+class B3MTL(TcnTrainingMixin, HostModel):
     """`model` object of get_Lemaire_MTL_model.  Inference runs entirely in libsmh (HIP)."""
 
-    HEADS = HEADS_MTL
     CLASS_NAME = "B3_MTL"
+    _DENSE_ENTRY, _DENSE_WORKSPACE = "smh_model_forward_dense_f32", "smh_model_dense_workspace_bytes"
 
     def __init__(self, n_feat=240, patch_size=68, n_classes=3, TR_STEPS=1, loss_weights=None, seed=None,
                  nb_filters=32, kernel_size=3, nb_stacks=3, n_dilations=8, tcn_block="2.3"):
@@ -147,82 +138,8 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
         self.out_dim = self.lib.smh_model_out_dim(self._h)
         self._spec = weight_spec(self.n_feat, self.patch_size, self.n_classes, nb_filters, kernel_size, nb_stacks, n_dilations,
                                  self.block_variant, self.HEADS)
-        assert self.count_params() == self.lib.smh_model_num_params(self._h)
-        self._dirty = True          # host copy newer than the device master
-        self._device_newer = False  # device master newer than the host copy (after optimiser steps)
+        self._init_store()
         self._init_training_state()
-
-    def __del__(self):
-        t = getattr(self, "_trainer", None)
-        if t:
-            self.lib.smh_trainer_destroy(t)
-            self._trainer = None
-        h = getattr(self, "_h", None)
-        if h:
-            self.lib.smh_model_destroy(h)
-            self._h = None
-
-    # ---- Keras-style surface -----------------------------------------------------------------
-    @property
-    def output_names(self):
-        return [n for n, _, _ in head_spec(self.n_classes, self.HEADS)] + ["3C"]
-
-    @property
-    def metrics_names(self):
-        """Proposed_Work_Results.py:887 expects ['loss','S_loss','M_loss','R_loss','3C_loss','3C_accuracy']."""
-        return ["loss"] + [n + "_loss" for n in self.output_names] + ["3C_accuracy"]
-
-    def count_params(self):
-        return int(sum(int(np.prod(s)) for _, s, _, _ in self._spec))
-
-    def _pull_weights(self):
-        if self._device_newer:
-            flat = np.empty(self.count_params(), np.float32)
-            _lib.check(self.lib.smh_model_get_weights(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
-                                                      _lib.current_stream()),
-                       "smh_model_get_weights")
-            o = 0
-            for name, shape, _, _ in self._spec:
-                n = int(np.prod(shape))
-                self.weights[name] = flat[o:o + n].reshape(shape).copy()
-                o += n
-            self._device_newer = False
-
-    def get_weights(self):
-        self._pull_weights()
-        return [self.weights[n].copy() for n, _, _, _ in self._spec]
-
-    def get_weights_dict(self):
-        self._pull_weights()
-        return self.weights
-
-    def set_weights(self, arrays):
-        arrays = list(arrays)
-        if len(arrays) != len(self._spec):
-            raise ValueError("set_weights: expected %d arrays, got %d" % (len(self._spec), len(arrays)))
-        for (name, shape, _, _), a in zip(self._spec, arrays):
-            a = np.asarray(a, dtype=np.float32)
-            if a.shape != tuple(shape):
-                raise ValueError("set_weights: %s expects shape %s, got %s" % (name, shape, a.shape))
-            self.weights[name] = a.copy()
-        self._dirty = True
-        self._device_newer = False
-
-    def set_weights_dict(self, d):
-        self.set_weights([d[n] for n, _, _, _ in self._spec])
-
-    def save_weights(self, path):
-        """`.h5` / `.hdf5`: HDF5 in Keras' weight-file layout (persistence.py); otherwise `<path>.npz`."""
-        from .persistence import save_weights_file
-        self._pull_weights()
-        return save_weights_file(path, self.weights)
-
-    def load_weights(self, path, arch_json=None):
-        """Weights written by `save_weights` (.h5 / .npz), or an .h5 file written by Keras itself for this architecture:
-        its auto-generated layer names are mapped through the architecture JSON (`arch_json`: path or text; default
-        `<path without .h5>.json`, the file the reference writes next to the weights)."""
-        from .persistence import load_weights_file
-        self.set_weights_dict(load_weights_file(path, arch_json=arch_json))
 
     def to_json(self):
         return json.dumps({"class_name": self.CLASS_NAME, "config": {
@@ -234,150 +151,104 @@ class B3MTL(TrainingMixin, ModelSurfaceMixin):
     def summary(self, print_fn=print):
         kind = {HEADS_CASCADED: "cascaded MTL", HEADS_FUSION: "intermediate-fusion MTL"}.get(self.HEADS, "MTL")
         inputs = "2 x " if self.HEADS == HEADS_FUSION else ""
-        print_fn("Model: %s (Lemaire et al. TCN + %s heads), input %s(None, %d, %d)"
-                 % (self.CLASS_NAME, kind, inputs, self.patch_size, self.n_feat))
-        for name, shape, _, _ in self._spec:
-            print_fn("  %-40s %-18s %d" % (name, str(tuple(shape)), int(np.prod(shape))))
-        print_fn("Total params: %d" % self.count_params())
+        self._summary("Model: %s (Lemaire et al. TCN + %s heads), input %s(None, %d, %d)"
+                      % (self.CLASS_NAME, kind, inputs, self.patch_size, self.n_feat), print_fn)
 
     # ---- inference -----------------------------------------------------------------------------
-    def _sync_weights(self):
-        if self._dirty:
-            flat = np.concatenate([self.weights[n].ravel() for n, _, _, _ in self._spec]).astype(np.float32)
-            _lib.check(self.lib.smh_model_set_weights(self._h, flat.ctypes.data_as(C.c_void_p), flat.size,
-                                                      _lib.current_stream()),
-                       "smh_model_set_weights")
-            self._dirty = False
+    def _check_patches(self, x, what="input"):
+        if x.dim() != 3 or x.shape[1] != self.patch_size or x.shape[2] != self.n_feat:
+            raise ValueError("expected %s (N, %d, %d), got %s" % (what, self.patch_size, self.n_feat, tuple(x.shape)))
+        return x
+
+    def _check_x0p(self, x0p):
+        if x0p.dim() != 4 or tuple(x0p.shape[1:]) != (2, self.patch_size, 32):
+            raise ValueError("expected (N, 2, %d, 32), got %s" % (self.patch_size, tuple(x0p.shape)))
+        return x0p
 
     def _train_inputs(self, x):
-        """A training step's input -> [x] as a contiguous float32 CUDA tensor (N, W, n_feat) (TrainingMixin.train_on_batch)."""
-        if isinstance(x, np.ndarray):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        x = x.to(device="cuda", dtype=torch.float32).contiguous()
-        if x.dim() != 3 or x.shape[1] != self.patch_size or x.shape[2] != self.n_feat:
-            raise ValueError("expected input (N, %d, %d), got %s" % (self.patch_size, self.n_feat, tuple(x.shape)))
+        """A training step's input -> [x] as a contiguous float32 CUDA tensor (N, W, n_feat) (TcnTrainingMixin.train_on_batch)."""
+        x = self._check_patches(to_f32_cuda(x))
         if self.block_variant != 0:
             raise NotImplementedError("training is built for the keras-tcn 2.3.x block (tcn_block='2.3'); the 2.8 block is inference only")
         return [x]
 
-    def forward_device(self, x, out=None, trunk=None, dtype="f32"):
-        """x: float32 CUDA tensor (N, W, n_feat) -> (N, out_dim) tensor [S|M|(N)|R|3C] on the device.
-        dtype="bf16" selects the mixed-precision kernel (bf16 matrix-core operands, f32 everything else): faster,
-        not the parity path."""
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
-            raise TypeError("forward_device expects a float32 CUDA tensor")
-        x = x.contiguous()
-        if x.dim() != 3 or x.shape[1] != self.patch_size or x.shape[2] != self.n_feat:
-            raise ValueError("expected input (N, %d, %d), got %s" % (self.patch_size, self.n_feat, tuple(x.shape)))
+    def _forward(self, f32_entry, bf16_entry, x, out, trunk, dtype):
+        """The f32 entry point (with the trunk tap) or its split-bf16 twin on x -> out (N, out_dim), allocated unless given and
+        not validated (HotPath and bench.py pass preallocated buffers).  Once per step in their timed loops: `_out`, `ptr` and
+        `_call` are written out here (measured: 1.2 us of 5.6 per call through them)."""
         self._sync_weights()
         N = x.shape[0]
         if out is None:
             out = torch.empty((N, self.out_dim), dtype=torch.float32, device=x.device)
-        if dtype == "bf16":
+        if dtype == "f32":
+            _lib.check(getattr(self.lib, f32_entry)(self._h, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()),
+                                                    None if trunk is None else C.c_void_p(trunk.data_ptr()),
+                                                    _lib.current_stream()), f32_entry)
+        elif dtype == "bf16":
             # "bf16" = SPLIT bf16 operands: every f32 operand travels as hi + lo (two bf16 values) and every product is three
             # bf16 MFMA (hi*hi + hi*lo + lo*hi) accumulated in f32 -- f32-grade arithmetic on the bf16 matrix pipe (7e-5 from the
             # f32 kernel), not an 8-bit-mantissa network.  Operands rounded to ONE bf16 land 3.5-5e-2 from f32, outside SURVEY
             # 8(d')'s 2e-2, and are not offered here (C ABI: smh_model_forward_bf16_ex(split = 0), measurement only).
             if trunk is not None:
                 raise ValueError("the trunk tap is only available on the f32 path")
-            _lib.check(self.lib.smh_model_forward_bf16_ex(
-                self._h, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()), 1,
-                _lib.current_stream()), "smh_model_forward_bf16")
-            return out
-        if dtype != "f32":
+            self._call(bf16_entry, self._h, ptr(x), N, ptr(out), 1)
+        else:
             raise ValueError("dtype must be 'f32' or 'bf16' (split bf16 operands), got %r" % (dtype,))
-        _lib.check(self.lib.smh_model_forward_f32(
-            self._h, C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()),
-            None if trunk is None else C.c_void_p(trunk.data_ptr()),
-            _lib.current_stream()), "smh_model_forward_f32")
         return out
+
+    def forward_device(self, x, out=None, trunk=None, dtype="f32"):
+        """x: float32 CUDA tensor (N, W, n_feat) -> (N, out_dim) tensor [S|M|(N)|R|3C] on the device.
+        dtype="bf16" selects the mixed-precision kernel (bf16 matrix-core operands, f32 everything else): faster,
+        not the parity path."""
+        x = self._check_patches(f32_cuda(x, "forward_device"))
+        return self._forward("smh_model_forward_f32", "smh_model_forward_bf16_ex", x, out, trunk, dtype)
 
     def forward_from_x0(self, x0p, out=None, trunk=None, dtype="f32"):
         """Forward that starts from the per-half layer-0 partials (N, 2, W, 32) written by `Frontend.features_l0`.
         dtype as for `forward_device`; with "bf16" layer 0 stays exact f32 (it was computed by the feature kernel)."""
-        if not (isinstance(x0p, torch.Tensor) and x0p.is_cuda and x0p.dtype == torch.float32):
-            raise TypeError("forward_from_x0 expects a float32 CUDA tensor")
-        x0p = x0p.contiguous()
+        x0p = f32_cuda(x0p, "forward_from_x0")
         if self.block_variant != 0:
             raise ValueError("the layer-0 fusion exists for the keras-tcn 2.3.x block only")
-        if x0p.dim() != 4 or tuple(x0p.shape[1:]) != (2, self.patch_size, 32):
-            raise ValueError("expected (N, 2, %d, 32), got %s" % (self.patch_size, tuple(x0p.shape)))
-        self._sync_weights()
-        N = x0p.shape[0]
-        if out is None:
-            out = torch.empty((N, self.out_dim), dtype=torch.float32, device=x0p.device)
-        if dtype == "bf16":
-            if trunk is not None:
-                raise ValueError("the trunk tap is only available on the f32 path")
-            _lib.check(self.lib.smh_model_forward_x0_bf16(
-                self._h, C.c_void_p(x0p.data_ptr()), N, C.c_void_p(out.data_ptr()), 1,
-                _lib.current_stream()), "smh_model_forward_x0_bf16")
-            return out
-        if dtype != "f32":
-            raise ValueError("dtype must be 'f32' or 'bf16' (split bf16 operands), got %r" % (dtype,))
-        _lib.check(self.lib.smh_model_forward_x0_f32(
-            self._h, C.c_void_p(x0p.data_ptr()), N, C.c_void_p(out.data_ptr()),
-            None if trunk is None else C.c_void_p(trunk.data_ptr()),
-            _lib.current_stream()), "smh_model_forward_x0_f32")
-        return out
+        return self._forward("smh_model_forward_x0_f32", "smh_model_forward_x0_bf16", self._check_x0p(x0p), out, trunk, dtype)
+
+    def _dense_rows(self):
+        """(rows of forward_dense's featuregram, what they are called in its shape error)."""
+        return self.n_feat, ""
+
+    def _dense_workspace_args(self, Tc, shift):
+        return (Tc,)
 
     def forward_dense(self, fv, shift=1, out=None):
         """Every hop-`shift` patch of a standardised featuregram batch fv (n_feat, Tc) through the network (dense file-level
         inference, DAFx12_Speech_Music_Detection_B3_MTL_v2.py:634-665) WITHOUT building the (nP, W, n_feat) patches: layer 0 once
         per frame, every patch a window of it (`smh_model_forward_dense_f32`).  Returns (nP, out_dim); nP = tools.extract_patches'
         count for Tc frames.  Needs Tc >= patch_size; shorter batches are tiled by get_feature_patches and go through forward_device."""
-        if not (isinstance(fv, torch.Tensor) and fv.is_cuda and fv.dtype == torch.float32):
-            raise TypeError("forward_dense expects a float32 CUDA tensor")
-        if fv.dim() != 2 or fv.shape[0] != self.n_feat:
-            raise ValueError("expected (%d, Tc), got %s" % (self.n_feat, tuple(fv.shape)))
+        fv = f32_cuda(fv, "forward_dense")
+        rows, what = self._dense_rows()
+        if fv.dim() != 2 or fv.shape[0] != rows:
+            raise ValueError("expected %s(%d, Tc), got %s" % (what, rows, tuple(fv.shape)))
         if self.block_variant != 0:
             raise ValueError("the layer-0 fusion exists for the keras-tcn 2.3.x block only")
-        fv = fv.contiguous()
-        Tc = int(fv.shape[1])
+        Tc, shift = int(fv.shape[1]), int(shift)
         self._sync_weights()
-        nP = self.lib.smh_num_patches(Tc, self.patch_size, int(shift)) if Tc >= self.patch_size else -1
+        nP = self.lib.smh_num_patches(Tc, self.patch_size, shift) if Tc >= self.patch_size else -1
         if nP < 0:
             raise ValueError("forward_dense needs shift >= 1 and at least patch_size=%d frames, got Tc=%d shift=%d" % (self.patch_size, Tc, shift))
-        if out is None:
-            out = torch.empty((nP, self.out_dim), dtype=torch.float32, device=fv.device)
-        elif tuple(out.shape) != (nP, self.out_dim):
-            raise ValueError("out must be (%d, %d)" % (nP, self.out_dim))
+        out = self._out(out, nP, fv.device, validate=True)
         if nP == 0:
             return out
-        nbytes = self.lib.smh_model_dense_workspace_bytes(self._h, Tc)
-        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=fv.device)
-        got = _lib.check(self.lib.smh_model_forward_dense_f32(
-            self._h, C.c_void_p(fv.data_ptr()), Tc, int(shift), C.c_void_p(work.data_ptr()), nbytes, C.c_void_p(out.data_ptr()),
-            _lib.current_stream()), "smh_model_forward_dense_f32")
+        nbytes = getattr(self.lib, self._DENSE_WORKSPACE)(self._h, *self._dense_workspace_args(Tc, shift))
+        work = workspace(nbytes, fv.device)
+        got = self._call(self._DENSE_ENTRY, self._h, ptr(fv), Tc, shift, ptr(work), nbytes, ptr(out))
         if got != nP:
-            raise RuntimeError("smh_model_forward_dense_f32 produced %d patches, expected %d" % (got, nP))
+            raise RuntimeError("%s produced %d patches, expected %d" % (self._DENSE_ENTRY, got, nP))
         return out
-
-    def split_outputs(self, out):
-        """(N, out_dim) -> list in Keras output order [S, M, (N,) R, 3C]."""
-        res, col = [], 0
-        for _, odim, _ in head_spec(self.n_classes, self.HEADS):
-            res.append(out[:, col:col + odim])
-            col += odim
-        res.append(out[:, col:col + self.n_classes])
-        return res
-
-    def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
-        """model.predict(x=batchData) -> [S, M, (N,) R, 3C] numpy arrays (Proposed_Work_Results.py:520,586)."""
-        if isinstance(x, np.ndarray):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
-        elif x.dtype != torch.float32:
-            x = x.float()
-        out = self.forward_device(x.cuda(), dtype=dtype)
-        self.check_status()  # the forward is stream-ordered: a device-side give-up must become an exception, not a result
-        host = out.cpu().numpy()  # ONE copy for all outputs (a copy per output is a host synchronisation per output)
-        return [np.ascontiguousarray(o) for o in self.split_outputs(host)]
 
     def check_status(self):
         """Wait for the current stream and raise RuntimeError if a forward kernel recorded in the model's device error word
         that its outputs are not results (include/smh.h: smh_model_status).  `forward_device` / `forward_from_x0` only enqueue
         work; callers that keep results on the device call this before trusting them (`predict` and bench.py do)."""
-        _lib.check(self.lib.smh_model_status(self._h, _lib.current_stream()), "smh_model_status")
+        self._call("smh_model_status", self._h)
 
 
 class CascadedMTL(B3MTL):
@@ -404,6 +275,7 @@ class FusionMTL(B3MTL):
     HEADS = HEADS_FUSION
     CLASS_NAME = "B3_MTL_Intermediate_Fusion"
     INPUT_NAMES = ("harm_input", "perc_input")
+    _DENSE_ENTRY, _DENSE_WORKSPACE = "smh_fusion_forward_dense_f32", "smh_fusion_dense_workspace_bytes"
 
     def __init__(self, n_feat=120, patch_size=68, n_classes=3, TR_STEPS=1, loss_weights=None, seed=None, nb_filters=32,
                  kernel_size=3, nb_stacks=3, n_dilations=8, tcn_block="2.3"):
@@ -422,25 +294,15 @@ class FusionMTL(B3MTL):
             x = [x[k] for k in self.INPUT_NAMES]
         if not isinstance(x, (list, tuple)) or len(x) != 2:
             raise TypeError("the intermediate-fusion model takes two inputs: [x_H, x_P] or {'harm_input': x_H, 'perc_input': x_P}")
-        out = []
         for a in x:
-            if isinstance(a, np.ndarray):
-                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-            if not isinstance(a, torch.Tensor):
+            if not isinstance(a, (np.ndarray, torch.Tensor)):
                 raise TypeError("inputs must be numpy arrays or torch tensors, got %s" % type(a).__name__)
-            a = a.to(device="cuda", dtype=torch.float32).contiguous()
-            if a.dim() != 3 or a.shape[1] != self.patch_size or a.shape[2] != self.n_feat:
-                raise ValueError("expected each input (N, %d, %d), got %s" % (self.patch_size, self.n_feat, tuple(a.shape)))
-            out.append(a)
-        if out[0].shape[0] != out[1].shape[0]:
-            raise ValueError("harm_input has %d patches, perc_input %d" % (out[0].shape[0], out[1].shape[0]))
-        return out
+        xh, xp = (self._check_patches(to_f32_cuda(a), "each input") for a in x)
+        if xh.shape[0] != xp.shape[0]:
+            raise ValueError("harm_input has %d patches, perc_input %d" % (xh.shape[0], xp.shape[0]))
+        return [xh, xp]
 
-    def _device_input(self, x):
-        return self._pair(x)
-
-    def _train_inputs(self, x):
-        return self._pair(x)
+    _device_input = _train_inputs = _pair
 
     def forward_device(self, x, out=None, trunk=None, dtype="f32"):
         """x: [x_H, x_P] (or the dict) -> (N, out_dim) tensor [S|M|(N)|R|3C] on the device (smh_fusion_forward_f32)."""
@@ -451,15 +313,12 @@ class FusionMTL(B3MTL):
         xh, xp = self._pair(x)
         self._sync_weights()
         N = xh.shape[0]
-        if out is None:
-            out = torch.empty((N, self.out_dim), dtype=torch.float32, device=xh.device)
+        out = self._out(out, N, xh.device)
         if N == 0:
             return out
         nbytes = self.lib.smh_fusion_workspace_bytes(self._h, N)
-        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=xh.device)
-        _lib.check(self.lib.smh_fusion_forward_f32(self._h, C.c_void_p(xh.data_ptr()), C.c_void_p(xp.data_ptr()), N,
-                                                   C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()), nbytes,
-                                                   _lib.current_stream()), "smh_fusion_forward_f32")
+        work = workspace(nbytes, xh.device)
+        self._call("smh_fusion_forward_f32", self._h, ptr(xh), ptr(xp), N, ptr(out), ptr(work), nbytes)
         return out
 
     def forward_from_x0(self, *args, **kwargs):
@@ -476,61 +335,29 @@ class FusionMTL(B3MTL):
         """x0p (N, 2, W, 32) as Frontend.features_l0(..., model=self) wrote it -- half 0 is trunk H's complete first layer, half 1
         trunk P's -- -> (N, out_dim) on the device (smh_fusion_forward_x0_f32).  The same logits as forward_device on the two halves
         of the patches within f32 tolerance."""
-        if not (isinstance(x0p, torch.Tensor) and x0p.is_cuda and x0p.dtype == torch.float32):
-            raise TypeError("forward_from_x0_halves expects a float32 CUDA tensor")
-        if x0p.dim() != 4 or tuple(x0p.shape[1:]) != (2, self.patch_size, 32):
-            raise ValueError("expected (N, 2, %d, 32), got %s" % (self.patch_size, tuple(x0p.shape)))
-        x0p = x0p.contiguous()
+        x0p = self._check_x0p(f32_cuda(x0p, "forward_from_x0_halves"))
         self._sync_weights()
         N = x0p.shape[0]
-        if out is None:
-            out = torch.empty((N, self.out_dim), dtype=torch.float32, device=x0p.device)
-        elif tuple(out.shape) != (N, self.out_dim):
-            raise ValueError("out must be (%d, %d)" % (N, self.out_dim))
+        out = self._out(out, N, x0p.device, validate=True)
         if N == 0:
             return out
         nbytes = self.lib.smh_fusion_x0_workspace_bytes(self._h, N)
-        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=x0p.device)
-        _lib.check(self.lib.smh_fusion_forward_x0_f32(self._h, C.c_void_p(x0p.data_ptr()), N, C.c_void_p(work.data_ptr()), nbytes,
-                                                      C.c_void_p(out.data_ptr()), _lib.current_stream()), "smh_fusion_forward_x0_f32")
+        work = workspace(nbytes, x0p.device)
+        self._call("smh_fusion_forward_x0_f32", self._h, ptr(x0p), N, ptr(work), nbytes, ptr(out))
         return out
+
+    def _dense_rows(self):
+        return 2 * self.n_feat, "the H||P featuregram "
+
+    def _dense_workspace_args(self, Tc, shift):
+        return (Tc, shift)
 
     def forward_dense(self, fv, shift=1, out=None):
         """Every hop-`shift` patch of a standardised featuregram batch fv (2 * n_feat, Tc) -- the H||P featuregram exactly as
         B3MTL.forward_dense takes it: H rows, then P rows -- through the network without building the patches or their halves
         (smh_fusion_forward_dense_f32): layer 0 of both trunks once per frame, every patch a window of it.  Returns (nP, out_dim), nP
         = tools.extract_patches' count for Tc frames.  Needs Tc >= patch_size and n_feat % 4 == 0."""
-        if not (isinstance(fv, torch.Tensor) and fv.is_cuda and fv.dtype == torch.float32):
-            raise TypeError("forward_dense expects a float32 CUDA tensor")
-        if fv.dim() != 2 or fv.shape[0] != 2 * self.n_feat:
-            raise ValueError("expected the H||P featuregram (%d, Tc), got %s" % (2 * self.n_feat, tuple(fv.shape)))
-        fv = fv.contiguous()
-        Tc = int(fv.shape[1])
-        self._sync_weights()
-        nP = self.lib.smh_num_patches(Tc, self.patch_size, int(shift)) if Tc >= self.patch_size else -1
-        if nP < 0:
-            raise ValueError("forward_dense needs shift >= 1 and at least patch_size=%d frames, got Tc=%d shift=%d" % (self.patch_size, Tc, shift))
-        if out is None:
-            out = torch.empty((nP, self.out_dim), dtype=torch.float32, device=fv.device)
-        elif tuple(out.shape) != (nP, self.out_dim):
-            raise ValueError("out must be (%d, %d)" % (nP, self.out_dim))
-        if nP == 0:
-            return out
-        nbytes = self.lib.smh_fusion_dense_workspace_bytes(self._h, Tc, int(shift))
-        work = torch.empty((nbytes // 4,), dtype=torch.float32, device=fv.device)
-        got = _lib.check(self.lib.smh_fusion_forward_dense_f32(
-            self._h, C.c_void_p(fv.data_ptr()), Tc, int(shift), C.c_void_p(work.data_ptr()), nbytes, C.c_void_p(out.data_ptr()),
-            _lib.current_stream()), "smh_fusion_forward_dense_f32")
-        if got != nP:
-            raise RuntimeError("smh_fusion_forward_dense_f32 produced %d patches, expected %d" % (got, nP))
-        return out
-
-    def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
-        """model.predict([x_H, x_P]) -> [S, M, (N,) R, 3C] numpy arrays (Intermediate_Fusion_Results.py)."""
-        out = self.forward_device(x, dtype=dtype)
-        self.check_status()
-        host = out.cpu().numpy()
-        return [np.ascontiguousarray(o) for o in self.split_outputs(host)]
+        return super().forward_dense(fv, shift, out)
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_data=None,
             steps_per_epoch=None, validation_steps=None, initial_epoch=0, **kwargs):

@@ -1,4 +1,4 @@
-"""Keras-style training surface of B3MTL: `compile`, `train_on_batch`, `fit`, `evaluate`.
+"""Keras-style training surface of the models: `compile`, `train_on_batch`, `fit`, `evaluate`.
 
 Mirrors how the reference drives the model (Proposed_Work_Results.py:275-312, 678-700):
   model.fit(generator, steps_per_epoch, epochs, validation_data=generator, validation_steps, verbose=1,
@@ -106,29 +106,25 @@ def _as_callbacks(callbacks, csv_log, checkpoint_path, early_stopping):
     return cbs
 
 
-class TrainingMixin:
-    """Mixed into sm_hpss_mtl_amd.model.B3MTL (and, through CnnTrainingMixin, into CnnMTL)."""
+def _p(t):
+    """Device pointer of a step's tensor argument (made contiguous: masks arrive as views), None for an absent one."""
+    return None if t is None else C.c_void_p(t.contiguous().data_ptr())
 
-    # C entry points of this model family's trainer: create, destroy, copy_state, grad_ptr, bucket_floats
-    _TRAINER_API = ("smh_trainer_create", "smh_trainer_destroy", "smh_trainer_copy_state", "smh_trainer_grad_ptr",
-                    "smh_trainer_bucket_floats")
-    _MIN_TRAINER_CAP = 64
+
+class TrainingMixin:
+    """What the trainers of both model families share: compile, the native trainer's life cycle (`_TRAINER_PREFIX` of
+    host.HostModel names its C entry points), targets, losses, apply_gradients, evaluate, fit.  Mixed into the models through
+    TcnTrainingMixin below (model.B3MTL and its subclasses) and cnn_training.CnnTrainingMixin (cnn_models.CnnMTL), which add the
+    step itself: `train_on_batch`, `_apply_native`, `_n_losses`, `_reset_optimizer_state`, `_on_new_trainer`."""
 
     # ---- optimiser state --------------------------------------------------------------------
-    def _init_training_state(self):
+    def _init_training_state(self, optimizer):
         self._trainer = None
         self._trainer_cap = 0
         self._grad_view = None
         self.iterations = 0
         self.stop_training = False
-        # lib/proposed_architectures.py:156-158
-        self.optimizer = _opt.SGD(learning_rate=_opt.ExponentialDecay(self.initial_learning_rate, 3 * max(int(self.TR_STEPS), 1), 0.1),
-                                  clipnorm=1, momentum=0.9)
-        self._mask_seed = 1234 + int(os.environ.get("RANK", "0"))  # data parallel: every rank draws its own masks
-        self._mask_calls = 0
-        # bit-reproducible weight gradients (include/smh.h: smh_trainer_set_deterministic); SMH_DETERMINISTIC=1 turns it on for
-        # every model of the process, `model.deterministic_gradients = True` for one
-        self._deterministic = os.environ.get("SMH_DETERMINISTIC", "0") == "1"
+        self.optimizer = optimizer
 
     def learning_rate(self, step=None):
         """Learning rate of optimiser step `step` (default: the next one), e.g. ExponentialDecay(0.002, 3*TR_STEPS, 0.1)."""
@@ -178,16 +174,8 @@ class TrainingMixin:
         self.iterations = 0
         self._reset_optimizer_state()  # a freshly compiled Keras model starts a fresh optimiser
 
-    def _reset_optimizer_state(self):
-        if self._trainer is not None:
-            _lib.check(self.lib.smh_trainer_reset_state(self._trainer, _cur_stream()), "smh_trainer_reset_state")
-
-    def _head_spec(self):
-        from .model import head_spec
-        return head_spec(self.n_classes, getattr(self, "HEADS", 0))
-
-    def _trainer_fn(self, i):
-        return getattr(self.lib, self._TRAINER_API[i])
+    def _trainer_c(self, suffix):
+        return getattr(self.lib, self._TRAINER_PREFIX + suffix)
 
     def _get_trainer(self, n):
         """The native trainer, grown when a batch exceeds its capacity.  Only the activation scratch depends on the
@@ -196,64 +184,20 @@ class TrainingMixin:
         if self._trainer is None or n > self._trainer_cap:
             cap = max(n, self._MIN_TRAINER_CAP)
             h = C.c_void_p()
-            _lib.check(self._trainer_fn(0)(self._h, cap, C.byref(h)), self._TRAINER_API[0])
+            _lib.check(self._trainer_c("_create")(self._h, cap, C.byref(h)), self._TRAINER_PREFIX + "_create")
             if self._trainer is not None:
-                _lib.check(self._trainer_fn(2)(h, self._trainer, _cur_stream()), self._TRAINER_API[2])
-                self._trainer_fn(1)(self._trainer)
+                _lib.check(self._trainer_c("_copy_state")(h, self._trainer, _cur_stream()), self._TRAINER_PREFIX + "_copy_state")
+                self._trainer_c("_destroy")(self._trainer)
             self._trainer, self._trainer_cap = h, cap
             self._grad_view = None
             self._on_new_trainer()
         return self._trainer
 
-    def _on_new_trainer(self):
-        self._apply_deterministic()
-        self._apply_train_dtype()
-
-    def _apply_train_dtype(self):
-        if self._trainer is not None and self._TRAINER_API[0] == "smh_trainer_create":
-            _lib.check(self.lib.smh_trainer_set_dtype(self._trainer, 1 if getattr(self, "_train_dtype", "f32") == "bf16" else 0),
-                       "smh_trainer_set_dtype")
-
-    @property
-    def train_dtype(self):
-        """'f32' (default) or 'bf16': the training step's forward on the bf16 matrix pipe with split operands (f32-grade products,
-        f32 accumulators and master weights; include/smh.h: smh_trainer_set_dtype).  B3_MTL only."""
-        return getattr(self, "_train_dtype", "f32")
-
-    @train_dtype.setter
-    def train_dtype(self, dtype):
-        if dtype not in ("f32", "bf16"):
-            raise ValueError("train_dtype must be 'f32' or 'bf16', got %r" % (dtype,))
-        if dtype == "bf16" and self._TRAINER_API[0] != "smh_trainer_create":
-            raise ValueError("train_dtype='bf16' exists for the B3_MTL trainer only")
-        if dtype == "bf16" and getattr(self, "HEADS", 0) != 0:
-            raise ValueError("train_dtype='bf16' exists for the B3_MTL heads only; the cascaded and intermediate-fusion models train in f32")
-        if dtype == "bf16":  # the trainer is created at the first step: refuse a model the bf16 forward cannot run now
-            _lib.check(self.lib.smh_model_check_train_dtype(self._h, 1), "train_dtype='bf16'")
-        self._train_dtype = dtype
-        self._apply_train_dtype()
-
-    def _apply_deterministic(self):
-        if self._trainer is not None and hasattr(self.lib, "smh_trainer_set_deterministic") and self._TRAINER_API[0] == "smh_trainer_create":
-            _lib.check(self.lib.smh_trainer_set_deterministic(self._trainer, 1 if self._deterministic else 0, _cur_stream()),
-                       "smh_trainer_set_deterministic")
-
-    @property
-    def deterministic_gradients(self):
-        """Weight gradients summed in 64-bit fixed point (integer atomics) instead of float atomics: bit-identical from run to
-        run.  The Conv2D baselines' trainer sums in ordered partials and is deterministic as it stands."""
-        return self._deterministic
-
-    @deterministic_gradients.setter
-    def deterministic_gradients(self, on):
-        self._deterministic = bool(on)
-        self._apply_deterministic()
-
     def _bucket_tensor(self):
         """torch view of the trainer's data-parallel bucket [flat gradient | BatchNorm batch statistics]."""
         if self._grad_view is None:
-            ptr = self._trainer_fn(3)(self._trainer)
-            n = int(self._trainer_fn(4)(self._trainer))
+            ptr = self._trainer_c("_grad_ptr")(self._trainer)
+            n = int(self._trainer_c("_bucket_floats")(self._trainer))
 
             class _Holder:
                 __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
@@ -288,9 +232,6 @@ class TrainingMixin:
             w = [1.0 if n == only else 0.0 for n in self.output_names]
         return (C.c_float * len(w))(*w)
 
-    def _n_losses(self):
-        return 3 * (len(self.output_names) - 1) + 4
-
     def losses_to_list(self, raw):
         """Raw device losses of one step (or their mean over steps) -> Keras order [loss, <per-output losses>, 3C_accuracy]."""
         lv = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
@@ -298,54 +239,13 @@ class TrainingMixin:
         return [float(lv[nh + 1] + lv[nh + 3])] + [float(v) for v in lv[: nh + 1]] + [float(lv[nh + 2])]
 
     # ---- one step ---------------------------------------------------------------------------------
-    def train_on_batch(self, x, y, drop_tcn="auto", drop_heads="auto", apply=True, sync=True, _only=None, _mask=TRAIN_ALL):
-        """One optimiser step.  Returns [loss, <per-output losses>, 3C_accuracy] like Keras; with sync=False the raw
-        device tensor of the step's losses (no host round trip: feed it to `losses_to_list` later).
-        drop_*: "auto" draws masks with the model's rates, None disables dropout, or pass mask tensors: drop_tcn (N, n_blocks, 32),
-        (2, N, n_blocks, 32) for a model with two trunks (trunk H, then trunk P), drop_heads (N, n_heads, 16)."""
-        xs = self._train_inputs(x)
-        if _only is not None and len(xs) != 1:
-            raise ValueError("single-output sub-models are built for the B3_MTL heads only")
-        n = xs[0].shape[0]
-        yt = y if (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() == 2) else self.pack_targets(y)
-        if yt.shape[0] != n:
-            raise ValueError("%d inputs but %d target rows" % (n, yt.shape[0]))
-        self._sync_weights()
-        tr = self._get_trainer(n)
-        n_blocks, n_heads = self.nb_stacks * self.n_dilations, len(self.output_names) - 1
-        tcn_shape = ((len(xs),) if len(xs) > 1 else ()) + (n, n_blocks, 32)
-        if isinstance(drop_tcn, str) or isinstance(drop_heads, str):
-            # both masks from ONE launch (csrc/smh_rng.hip; until round 3 a torch Bernoulli draw and a scaling): Philox keyed by this
-            # replica's seed (1234 + RANK: every rank draws its own masks), one stream per step; one rate, independent masks per trunk
-            from .device_rng import dropout_masks
-            n_t, n_h = len(xs) * n * n_blocks * 32, n * n_heads * 16
-            masks = dropout_masks(n_t, 1.0 - self.dropout_rate, n_h, 1.0 - HEAD_DROPOUT, self._mask_seed, self._mask_calls)
-            self._mask_calls += 1
-            if isinstance(drop_tcn, str):
-                drop_tcn = masks[:n_t].view(tcn_shape)
-            if isinstance(drop_heads, str):
-                drop_heads = masks[n_t:].view(n, n_heads, 16)
-        if drop_tcn is not None and tuple(drop_tcn.shape) != tcn_shape:
-            raise ValueError("drop_tcn must be %s, got %s" % (tcn_shape, tuple(drop_tcn.shape)))
-        losses = torch.empty(self._n_losses(), dtype=torch.float32, device="cuda")
-        p = lambda t: None if t is None else C.c_void_p(t.contiguous().data_ptr())  # noqa: E731
-        entry = "smh_train_step_f32" if len(xs) == 1 else "smh_fusion_train_step_f32"
-        _lib.check(getattr(self.lib, entry)(tr, *map(p, xs), p(yt), n, p(drop_tcn), p(drop_heads), self._loss_weight_array(_only),
-                                            p(losses), _cur_stream()), entry)
-        if apply:
-            self.apply_gradients(_mask)
-        if not sync:
-            return losses
-        self._check_device_status()  # the step's forward may have given up on the device: never report its losses as a step
-        return self.losses_to_list(losses)
+    def _device_targets(self, y):
+        return y if (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() == 2) else self.pack_targets(y)
 
-    def _apply_native(self, lr, scale, mask):
-        o = self.optimizer
-        kind = {"sgd": 0, "adam": 1, "nadam": 2}[o.kind]
-        b1 = o.momentum if kind == 0 else o.beta_1
-        _lib.check(self.lib.smh_trainer_apply_f32(self._trainer, kind, lr, b1, getattr(o, "beta_2", 0.0),
-                                                  getattr(o, "epsilon", 0.0), o.clipnorm or 0.0, scale, mask, _cur_stream()),
-                   "smh_trainer_apply_f32")
+    def _begin_step(self, n):
+        """Weights on the device, a trainer that holds n rows -> (trainer, the step's raw losses tensor)."""
+        self._sync_weights()
+        return self._get_trainer(n), torch.empty(self._n_losses(), dtype=torch.float32, device="cuda")
 
     def apply_gradients(self, mask=TRAIN_ALL):
         """All-reduce the bucket [gradient | BatchNorm batch statistics] (if torch.distributed is initialised) -- SUM over
@@ -444,47 +344,8 @@ class TrainingMixin:
         return list(tot / max(cnt, 1.0))
 
     def _device_evaluate_ok(self):
-        """B3_MTL with libsmh's evaluate kernel: the per-batch losses are summed on the device (smh_model_eval_losses_f32)."""
-        return (getattr(self, "_TRAINER_API", ("",))[0] == "smh_trainer_create" and hasattr(self, "forward_device")
-                and hasattr(getattr(self, "lib", None), "smh_model_eval_losses_f32") and getattr(self, "block_variant", 0) == 0
-                and os.environ.get("SMH_EVAL_HOST", "0") != "1")
-
-    def _evaluate_device(self, x, y, steps, weight):
-        """evaluate() without a host round trip per batch: forward, then `smh_model_eval_losses_f32` adds the batch's mean losses and
-        accuracy (float64, Keras' clipping: the arithmetic of `_losses_inference`) to device sums; ONE read-back at the end.
-        Returns (unnormalised sums in metrics order, total weight) like the host loop.  SMH_EVAL_HOST=1 keeps the host loop."""
-        nh = len(self.output_names) - 1
-        sums = torch.zeros(nh + 3, dtype=torch.float64, device="cuda")  # [total | per-output losses | 3C accuracy]
-        cnt = 0.0
-        lw = (C.c_double * (nh + 1))(*[float((self.loss_weights or {}).get(n, 1.0)) for n in self.output_names])
-        l2 = float(self._l2_penalty())  # the weights do not change while evaluating
-
-        def one(bx, by, weight_of):
-            out = self.forward_device(self._device_input(bx))
-            tgt = by if (isinstance(by, torch.Tensor) and by.is_cuda and by.dim() == 2) else self.pack_targets(by)
-            if tgt.shape[0] != out.shape[0]:
-                raise ValueError("%d inputs but %d target rows" % (out.shape[0], tgt.shape[0]))
-            w = float(weight_of(out.shape[0]))  # Keras averages the batch values; data parallel: row-weighted (see evaluate)
-            _lib.check(self.lib.smh_model_eval_losses_f32(self._h, C.c_void_p(out.data_ptr()), C.c_void_p(tgt.data_ptr()), out.shape[0],
-                                                          C.c_double(w), lw, C.c_double(l2), C.c_void_p(sums.data_ptr()), _cur_stream()),
-                       "smh_model_eval_losses_f32")
-            return w
-
-        if y is not None:
-            cnt = one(x, y, float)  # arrays: one batch, weighted by its rows like the host path
-        else:
-            if steps is None:
-                raise ValueError("evaluate(generator) needs steps=")
-            for _ in range(int(steps)):
-                cnt += one(*next(x), weight)
-        self.check_status()  # one synchronisation for the whole pass; a device-side give-up raises here
-        return sums.cpu().numpy(), cnt  # already in metrics order: [loss, <per-output losses>, 3C_accuracy]
-
-    def _device_input(self, bx):
-        """A batch's input as forward_device takes it (the fusion model: two inputs)."""
-        if isinstance(bx, np.ndarray):
-            bx = torch.from_numpy(np.ascontiguousarray(bx, dtype=np.float32))
-        return bx.to(device="cuda", dtype=torch.float32)
+        """Whether evaluate() can sum the per-batch losses on the device (`_evaluate_device`; the TCN models)."""
+        return False
 
     def _check_device_status(self):
         """Raise if a kernel of this model set the device error word (B3_MTL: smh_model_status); models without one: nothing."""
@@ -609,3 +470,147 @@ class TrainingMixin:
         for cb in cbs:
             cb.on_train_end()
         return hist
+
+
+class TcnTrainingMixin(TrainingMixin):
+    """Mixed into sm_hpss_mtl_amd.model.B3MTL (and so CascadedMTL, FusionMTL): the step over `smh_trainer_*`, and what only that
+    trainer has -- the bf16 training dtype, bit-reproducible gradients, an optimiser reset in place, Philox dropout masks, the
+    single-head sub-model (`_only` / `_mask`, persistence.HeadModel) and evaluate() with device-side sums."""
+
+    _MIN_TRAINER_CAP = 64
+
+    def _init_training_state(self):
+        # lib/proposed_architectures.py:156-158
+        super()._init_training_state(_opt.SGD(
+            learning_rate=_opt.ExponentialDecay(self.initial_learning_rate, 3 * max(int(self.TR_STEPS), 1), 0.1), clipnorm=1, momentum=0.9))
+        self._mask_seed = 1234 + int(os.environ.get("RANK", "0"))  # data parallel: every rank draws its own masks
+        self._mask_calls = 0
+        # bit-reproducible weight gradients (include/smh.h: smh_trainer_set_deterministic); SMH_DETERMINISTIC=1 turns it on for
+        # every model of the process, `model.deterministic_gradients = True` for one
+        self._deterministic = os.environ.get("SMH_DETERMINISTIC", "0") == "1"
+        self._train_dtype = "f32"
+
+    def _reset_optimizer_state(self):
+        if self._trainer is not None:
+            _lib.check(self.lib.smh_trainer_reset_state(self._trainer, _cur_stream()), "smh_trainer_reset_state")
+
+    def _on_new_trainer(self):
+        self._apply_deterministic()
+        self._apply_train_dtype()
+
+    def _apply_train_dtype(self):
+        if self._trainer is not None:
+            _lib.check(self.lib.smh_trainer_set_dtype(self._trainer, 1 if self._train_dtype == "bf16" else 0), "smh_trainer_set_dtype")
+
+    @property
+    def train_dtype(self):
+        """'f32' (default) or 'bf16': the training step's forward on the bf16 matrix pipe with split operands (f32-grade products,
+        f32 accumulators and master weights; include/smh.h: smh_trainer_set_dtype).  B3_MTL only."""
+        return self._train_dtype
+
+    @train_dtype.setter
+    def train_dtype(self, dtype):
+        if dtype not in ("f32", "bf16"):
+            raise ValueError("train_dtype must be 'f32' or 'bf16', got %r" % (dtype,))
+        if dtype == "bf16" and self.HEADS != 0:
+            raise ValueError("train_dtype='bf16' exists for the B3_MTL heads only; the cascaded and intermediate-fusion models train in f32")
+        if dtype == "bf16":  # the trainer is created at the first step: refuse a model the bf16 forward cannot run now
+            _lib.check(self.lib.smh_model_check_train_dtype(self._h, 1), "train_dtype='bf16'")
+        self._train_dtype = dtype
+        self._apply_train_dtype()
+
+    def _apply_deterministic(self):
+        if self._trainer is not None:
+            _lib.check(self.lib.smh_trainer_set_deterministic(self._trainer, 1 if self._deterministic else 0, _cur_stream()),
+                       "smh_trainer_set_deterministic")
+
+    @property
+    def deterministic_gradients(self):
+        """Weight gradients summed in 64-bit fixed point (integer atomics) instead of float atomics: bit-identical from run to
+        run."""
+        return self._deterministic
+
+    @deterministic_gradients.setter
+    def deterministic_gradients(self, on):
+        self._deterministic = bool(on)
+        self._apply_deterministic()
+
+    def _n_losses(self):
+        return 3 * (len(self.output_names) - 1) + 4
+
+    def train_on_batch(self, x, y, drop_tcn="auto", drop_heads="auto", apply=True, sync=True, _only=None, _mask=TRAIN_ALL):
+        """One optimiser step.  Returns [loss, <per-output losses>, 3C_accuracy] like Keras; with sync=False the raw
+        device tensor of the step's losses (no host round trip: feed it to `losses_to_list` later).
+        drop_*: "auto" draws masks with the model's rates, None disables dropout, or pass mask tensors: drop_tcn (N, n_blocks, 32),
+        (2, N, n_blocks, 32) for a model with two trunks (trunk H, then trunk P), drop_heads (N, n_heads, 16)."""
+        xs = self._train_inputs(x)
+        if _only is not None and len(xs) != 1:
+            raise ValueError("single-output sub-models are built for the B3_MTL heads only")
+        n = xs[0].shape[0]
+        yt = self._device_targets(y)
+        if yt.shape[0] != n:
+            raise ValueError("%d inputs but %d target rows" % (n, yt.shape[0]))
+        tr, losses = self._begin_step(n)
+        n_blocks, n_heads = self.nb_stacks * self.n_dilations, len(self.output_names) - 1
+        tcn_shape = ((len(xs),) if len(xs) > 1 else ()) + (n, n_blocks, 32)
+        if isinstance(drop_tcn, str) or isinstance(drop_heads, str):
+            # both masks from ONE launch (csrc/smh_rng.hip; until round 3 a torch Bernoulli draw and a scaling): Philox keyed by this
+            # replica's seed (1234 + RANK: every rank draws its own masks), one stream per step; one rate, independent masks per trunk
+            from .device_rng import dropout_masks
+            n_t, n_h = len(xs) * n * n_blocks * 32, n * n_heads * 16
+            masks = dropout_masks(n_t, 1.0 - self.dropout_rate, n_h, 1.0 - HEAD_DROPOUT, self._mask_seed, self._mask_calls)
+            self._mask_calls += 1
+            if isinstance(drop_tcn, str):
+                drop_tcn = masks[:n_t].view(tcn_shape)
+            if isinstance(drop_heads, str):
+                drop_heads = masks[n_t:].view(n, n_heads, 16)
+        if drop_tcn is not None and tuple(drop_tcn.shape) != tcn_shape:
+            raise ValueError("drop_tcn must be %s, got %s" % (tcn_shape, tuple(drop_tcn.shape)))
+        entry = "smh_train_step_f32" if len(xs) == 1 else "smh_fusion_train_step_f32"
+        self._call(entry, tr, *map(_p, xs), _p(yt), n, _p(drop_tcn), _p(drop_heads), self._loss_weight_array(_only), _p(losses))
+        if apply:
+            self.apply_gradients(_mask)
+        if not sync:
+            return losses
+        self._check_device_status()  # the step's forward may have given up on the device: never report its losses as a step
+        return self.losses_to_list(losses)
+
+    def _apply_native(self, lr, scale, mask):
+        o = self.optimizer
+        kind = {"sgd": 0, "adam": 1, "nadam": 2}[o.kind]
+        b1 = o.momentum if kind == 0 else o.beta_1
+        self._call("smh_trainer_apply_f32", self._trainer, kind, lr, b1, getattr(o, "beta_2", 0.0), getattr(o, "epsilon", 0.0),
+                   o.clipnorm or 0.0, scale, mask)
+
+    def _device_evaluate_ok(self):
+        """The keras-tcn 2.3.x block with libsmh's evaluate kernel (smh_model_eval_losses_f32); SMH_EVAL_HOST=1 keeps the host loop."""
+        return self.block_variant == 0 and os.environ.get("SMH_EVAL_HOST", "0") != "1"
+
+    def _evaluate_device(self, x, y, steps, weight):
+        """evaluate() without a host round trip per batch: forward, then `smh_model_eval_losses_f32` adds the batch's mean losses and
+        accuracy (float64, Keras' clipping: the arithmetic of `_losses_inference`) to device sums; ONE read-back at the end.
+        Returns (unnormalised sums in metrics order, total weight) like the host loop."""
+        nh = len(self.output_names) - 1
+        sums = torch.zeros(nh + 3, dtype=torch.float64, device="cuda")  # [total | per-output losses | 3C accuracy]
+        cnt = 0.0
+        lw = (C.c_double * (nh + 1))(*[float((self.loss_weights or {}).get(n, 1.0)) for n in self.output_names])
+        l2 = float(self._l2_penalty())  # the weights do not change while evaluating
+
+        def one(bx, by, weight_of):
+            out = self.forward_device(self._device_input(bx))
+            tgt = self._device_targets(by)
+            if tgt.shape[0] != out.shape[0]:
+                raise ValueError("%d inputs but %d target rows" % (out.shape[0], tgt.shape[0]))
+            w = float(weight_of(out.shape[0]))  # Keras averages the batch values; data parallel: row-weighted (see evaluate)
+            self._call("smh_model_eval_losses_f32", self._h, _p(out), _p(tgt), out.shape[0], C.c_double(w), lw, C.c_double(l2), _p(sums))
+            return w
+
+        if y is not None:
+            cnt = one(x, y, float)  # arrays: one batch, weighted by its rows like the host path
+        else:
+            if steps is None:
+                raise ValueError("evaluate(generator) needs steps=")
+            for _ in range(int(steps)):
+                cnt += one(*next(x), weight)
+        self.check_status()  # one synchronisation for the whole pass; a device-side give-up raises here
+        return sums.cpu().numpy(), cnt  # already in metrics order: [loss, <per-output losses>, 3C_accuracy]
