@@ -1186,7 +1186,8 @@ int smh_tcn::launch_heads_train(const HeadsArgs &a, const float *pre, const floa
     ad.stamps = getenv("SMH_HEADS_STAMPS") ? 1 : 0;
     const int NHc = a.n_classes + a.n_heads * kHidden;
     const size_t lds = sizeof(float) * ((size_t)a.N * (NHc | 1) + (size_t)a.N * (a.out_dim | 1));
-    // 160 KB of LDS per CU minus the kernel's static 37 KB (per-wave accumulator rows): 3-class batches up to 528 patches
+    // 160 KB of LDS per CU minus the kernel's static 37 KB (per-wave accumulator rows): 3-class batches up to 538 patches, 5-class
+    // up to 390 (232 and 320 bytes per patch; tests/heads_plans.py restates this, tests/test_heads_plans.py pins it)
     const bool staged = lds <= 122 * 1024 && !getenv("SMH_HEADS_GLOBAL");
 #define SMH_LAUNCH_HEADS(ST, TH)                                                                                        \
     do {                                                                                                                \

@@ -87,14 +87,15 @@ def forward(x, w, n_classes=3):
 
 
 def torch_forward_backward(x, y, w, n_classes=3, drop_tcn=None, drop_heads=None, loss_weights=None, heads="cascaded",
-                           nb_stacks=3, n_dil=8):
+                           nb_stacks=3, n_dil=8, dtype=np.float64):
     """One training step in float64 torch autograd.  y: dict output -> targets; drop_tcn (N, n_blocks, 32); drop_heads: dict
     head -> (N, 16).  Returns dict(loss (with the l2 term), losses{name}, acc, grads{name} (incl. the l2 term, like the oracle),
-    bn_batch{'<head>/bn' | '<head>/cat_bn': (mean, population var)}, outputs{name})."""
+    bn_batch{'<head>/bn' | '<head>/cat_bn': (mean, population var)}, outputs{name}).  dtype: the precision of the whole graph
+    (np.float32: the same graph at the kernels' precision, for a measured rounding floor)."""
     import torch
     import torch.nn.functional as F
-    T = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in w.items()}
-    xt = torch.tensor(np.asarray(x, np.float64))
+    T = {k: torch.tensor(np.asarray(v, dtype), requires_grad=True) for k, v in w.items()}
+    xt = torch.tensor(np.asarray(x, dtype))
     N = xt.shape[0]
     spec = b3_mtl.head_spec(n_classes) if heads == "mtl" else HEADS
     lw = {n: 1.0 for n, _, _ in spec}
@@ -114,7 +115,7 @@ def torch_forward_backward(x, y, w, n_classes=3, drop_tcn=None, drop_heads=None,
             r = torch.relu(conv(h, T[p + "/conv/kernel"], T[p + "/conv/bias"], d))
             yn = r / (torch.amax(r, dim=2, keepdim=True) + NORM_EPS)  # amax shares the gradient among tied maxima
             if drop_tcn is not None:
-                yn = yn * torch.tensor(np.asarray(drop_tcn, np.float64)[:, bi][:, None, :])
+                yn = yn * torch.tensor(np.asarray(drop_tcn, dtype)[:, bi][:, None, :])
             h = h + conv(yn, T[p + "/conv1x1/kernel"], T[p + "/conv1x1/bias"], 1)
             bi += 1
     flat = torch.relu(h).reshape(N, -1)
@@ -129,7 +130,7 @@ def torch_forward_backward(x, y, w, n_classes=3, drop_tcn=None, drop_heads=None,
         v = flat @ T[name + "/dense/kernel"] + T[name + "/dense/bias"]
         a = torch.relu(bn_train(v, name + "/bn", T[name + "/bn/gamma"], T[name + "/bn/beta"]))
         if drop_heads is not None and name in drop_heads:
-            a = a * torch.tensor(np.asarray(drop_heads[name], np.float64))
+            a = a * torch.tensor(np.asarray(drop_heads[name], dtype))
         return a
 
     out = {}
@@ -145,7 +146,7 @@ def torch_forward_backward(x, y, w, n_classes=3, drop_tcn=None, drop_heads=None,
             out[name] = torch.sigmoid(z @ T[name + "/out/kernel"] + T[name + "/out/bias"])
     losses = {}
     for name, odim, act in spec:
-        t = torch.tensor(np.asarray(y[name], np.float64).reshape(N, odim))
+        t = torch.tensor(np.asarray(y[name], dtype).reshape(N, odim))
         o = out[name]
         if act == "sigmoid":
             oc = torch.clamp(o, KERAS_EPS, 1 - KERAS_EPS)
@@ -154,7 +155,7 @@ def torch_forward_backward(x, y, w, n_classes=3, drop_tcn=None, drop_heads=None,
             losses[name] = torch.mean((o - t) ** 2)
     logits = flat @ T["3C/kernel"] + T["3C/bias"]
     p = torch.softmax(logits, dim=1)
-    t3 = torch.tensor(np.asarray(y["3C"], np.float64).reshape(N, n_classes))
+    t3 = torch.tensor(np.asarray(y["3C"], dtype).reshape(N, n_classes))
     losses["3C"] = torch.mean(-torch.sum(t3 * torch.log(torch.clamp(p, KERAS_EPS, 1 - KERAS_EPS)), dim=1))
     out["3C"] = p
     reg = sum(L2 * torch.sum(T[n + "/dense/kernel"] ** 2) for n, _, _ in spec)

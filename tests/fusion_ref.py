@@ -80,13 +80,14 @@ def forward(xH, xP, w, n_classes=3, nb_stacks=3, n_dil=8):
 
 
 def torch_forward_backward(xH, xP, y, w, n_classes=3, drop_tcn=None, drop_heads=None, loss_weights=None, fuse=True, nb_stacks=3,
-                           n_dil=8):
+                           n_dil=8, dtype=np.float64):
     """One training step in float64 torch autograd.  drop_tcn: (2, N, n_blocks, 32) masks of trunks H and P, or None; drop_heads:
     dict head -> (N, 16).  Returns dict(loss (with the l2 term), losses{name}, acc, grads{name} (incl. the l2 term), bn_batch{'<head>'
-    | 'fusion_bn': (mean, population var)}, outputs{name})."""
+    | 'fusion_bn': (mean, population var)}, outputs{name}).  dtype: the precision of the whole graph (np.float32: the same graph at
+    the kernels' precision, for a measured rounding floor)."""
     import torch
     import torch.nn.functional as F
-    T = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in w.items()}
+    T = {k: torch.tensor(np.asarray(v, dtype), requires_grad=True) for k, v in w.items()}
     spec = b3_mtl.head_spec(n_classes)
     lw = {n: 1.0 for n, _, _ in spec}
     lw["3C"] = 1.0
@@ -97,7 +98,7 @@ def torch_forward_backward(xH, xP, y, w, n_classes=3, drop_tcn=None, drop_heads=
         return F.conv1d(h.transpose(1, 2), k.permute(2, 1, 0), b, padding=(taps // 2) * d, dilation=d).transpose(1, 2)
 
     def trunk(x, t, drop):
-        h = conv(torch.tensor(np.asarray(x, np.float64)), T[t + "/initial_conv/kernel"], T[t + "/initial_conv/bias"], 1)
+        h = conv(torch.tensor(np.asarray(x, dtype)), T[t + "/initial_conv/kernel"], T[t + "/initial_conv/bias"], 1)
         bi = 0
         for s in range(nb_stacks):
             for i in range(n_dil):
@@ -105,7 +106,7 @@ def torch_forward_backward(xH, xP, y, w, n_classes=3, drop_tcn=None, drop_heads=
                 r = torch.relu(conv(h, T[p + "/conv/kernel"], T[p + "/conv/bias"], d))
                 yn = r / (torch.amax(r, dim=2, keepdim=True) + NORM_EPS)
                 if drop is not None:
-                    yn = yn * torch.tensor(np.asarray(drop, np.float64)[:, bi][:, None, :])
+                    yn = yn * torch.tensor(np.asarray(drop, dtype)[:, bi][:, None, :])
                 h = h + conv(yn, T[p + "/conv1x1/kernel"], T[p + "/conv1x1/bias"], 1)
                 bi += 1
         return torch.relu(h).reshape(h.shape[0], -1)
@@ -127,12 +128,12 @@ def torch_forward_backward(xH, xP, y, w, n_classes=3, drop_tcn=None, drop_heads=
         v = flat @ T[name + "/dense/kernel"] + T[name + "/dense/bias"]
         a = torch.relu(bn_train(v, name, T[name + "/bn/gamma"], T[name + "/bn/beta"]))
         if drop_heads is not None and name in drop_heads:
-            a = a * torch.tensor(np.asarray(drop_heads[name], np.float64))
+            a = a * torch.tensor(np.asarray(drop_heads[name], dtype))
         zo = a @ T[name + "/out/kernel"] + T[name + "/out/bias"]
         out[name] = torch.sigmoid(zo) if act == "sigmoid" else zo
     losses = {}
     for name, odim, act in spec:
-        t = torch.tensor(np.asarray(y[name], np.float64).reshape(N, odim))
+        t = torch.tensor(np.asarray(y[name], dtype).reshape(N, odim))
         o = out[name]
         if act == "sigmoid":
             oc = torch.clamp(o, KERAS_EPS, 1 - KERAS_EPS)
@@ -141,7 +142,7 @@ def torch_forward_backward(xH, xP, y, w, n_classes=3, drop_tcn=None, drop_heads=
             losses[name] = torch.mean((o - t) ** 2)
     logits = flat @ T["3C/kernel"] + T["3C/bias"]
     p = torch.softmax(logits, dim=1)
-    t3 = torch.tensor(np.asarray(y["3C"], np.float64).reshape(N, n_classes))
+    t3 = torch.tensor(np.asarray(y["3C"], dtype).reshape(N, n_classes))
     losses["3C"] = torch.mean(-torch.sum(t3 * torch.log(torch.clamp(p, KERAS_EPS, 1 - KERAS_EPS)), dim=1))
     out["3C"] = p
     reg = sum(L2 * torch.sum(T[n + "/dense/kernel"] ** 2) for n, _, _ in spec)

@@ -169,6 +169,26 @@ def test_optimisers_and_deterministic_mode(opt):
     assert all(np.array_equal(a, b) for a, b in zip(runs[0][1], runs[1][1]))
 
 
+@pytest.mark.parametrize("N", [904, 1617])
+def test_global_memory_heads_are_bit_reproducible(N):
+    """The cascaded heads kernels add their batch sums per wave and then in wave order (smh_train_cascade.hip: "reproducible
+    whatever smh_trainer_set_deterministic says"), in the global-memory forms too: N = 904 (the S / M / 3C kernel reads global
+    memory) and N = 1617 (the R kernel as well; tests/heads_plans.py).  With deterministic_gradients the trunk's weight gradients are
+    order-independent as well: three runs, `torch.equal` on the whole bucket (gradient and batch statistics)."""
+    m = _model()
+    m.set_weights_dict(_weights(m, 5, 68, 3))
+    m.deterministic_gradients = True
+    x, y, dt, dh = _train_problem(N, seed=N)
+    xd, dtd, dhd = torch.from_numpy(x).cuda(), torch.from_numpy(dt).cuda(), torch.from_numpy(dh).cuda()
+    runs = []
+    for _ in range(3):
+        m.train_on_batch(xd, y, drop_tcn=dtd, drop_heads=dhd, apply=False)
+        torch.cuda.synchronize()
+        runs.append(m._bucket_tensor().clone())
+    assert torch.isfinite(runs[0]).all() and float(runs[0][:m.count_params()].abs().max()) > 0
+    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
+
+
 def test_fit_loss_falls(tmp_path):
     rng = np.random.default_rng(0)
     m = _model(seed=1)
