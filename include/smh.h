@@ -479,6 +479,41 @@ int smh_fusion_forward_x0_f32(smh_model *m, const float *d_x0p, int N, void *d_w
 size_t smh_fusion_dense_workspace_bytes(const smh_model *m, int Tc, int shift);
 int smh_fusion_forward_dense_f32(smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes, float *d_out,
                                  void *stream);
+/* Late fusion (Late_Fusion_Results.py:388-513): an ensemble of two complete single-input models of one architecture, model H on the
+ * harmonic half of the H||P featuregram and model P on the percussive half, whose '3C' outputs are blended:
+ *   pred[n][c] = fl(fl(a * pH[n][c]) + fl(b * pP[n][c])),  a = (float)alpha, b = (float)(1.0 - alpha)   (no FMA: numpy's
+ *   alpha * pred_H + (1 - alpha) * pred_P on float32 arrays, bit for bit),   label[n] = the first maximum of pred[n] (np.argmax).
+ *   smh_late_fusion_create   both models f32 TCN models (SMH_HEADS_MTL or both SMH_HEADS_CASCADED, block_variant 0) of one geometry
+ *                            (n_feat, patch_size, n_classes, stacks, dilations); anything else, or the same model twice, is
+ *                            SMH_E_INVALID.  The ensemble borrows the models: they must outlive it, and it follows their weights.
+ *   Every forward takes alpha in [0, 1], d_work (16-byte aligned, the entry's *_workspace_bytes) and writes d_pred (N, n_classes),
+ *   d_labels (N) int32 or NULL, d_heads (2, N, out_dim) or NULL: each model's own [S | M | (N) | R | 3C], bit-identical to its
+ *   smh_model_forward_f32 / _x0 / _dense output.  Both models run as ONE grid (a second grid row is model P);
+ *   SMH_LATE_FUSION_TWO_LAUNCH=1 in the environment, read per call, runs two launches instead -- bit-identical, for A/B timing.
+ *   smh_late_fusion_forward_f32        d_xH, d_xP (N, W, n_feat) time-major
+ *   smh_late_fusion_w0_ptr             device pointer to (2 * n_feat, 32) floats, model H's initial-conv kernel then model P's: the
+ *                                      d_w0 of smh_features_l0_f32 for the ensemble.  Brought up to date on `stream` whenever either
+ *                                      model's weights changed since the last call.
+ *   smh_late_fusion_forward_x0_f32     d_x0p (N, 2, W, 32) as smh_features_l0_f32 wrote it with that kernel: half 0 is model H's
+ *                                      complete first layer, half 1 model P's
+ *   smh_late_fusion_forward_dense_f32  d_fv (2 * n_feat, Tc), the standardised H||P featuregram: layer 0 of both models once per
+ *                                      frame, every hop-`shift` patch a window of it, in chunks of 2048 patches; returns the patch
+ *                                      count nP = smh_num_patches(Tc, W, shift); outputs sized by nP.  Needs Tc >= W, shift >= 1,
+ *                                      n_feat a multiple of 4.  d_work = 4 * (2 * Tc * 32 + 2 * min(nP, 2048) * out_dim) bytes, rounded up to 16.
+ * Stream-ordered, no host synchronisation; N = 0: no launch.  The models' device error words are theirs: smh_model_status on each. */
+typedef struct smh_late_fusion smh_late_fusion;
+int smh_late_fusion_create(smh_model *mH, smh_model *mP, smh_late_fusion **out);
+void smh_late_fusion_destroy(smh_late_fusion *e);
+const float *smh_late_fusion_w0_ptr(smh_late_fusion *e, void *stream);
+size_t smh_late_fusion_workspace_bytes(const smh_late_fusion *e, int N);
+int smh_late_fusion_forward_f32(smh_late_fusion *e, const float *d_xH, const float *d_xP, int N, double alpha, void *d_work,
+                                size_t work_bytes, float *d_pred, int *d_labels, float *d_heads, void *stream);
+size_t smh_late_fusion_x0_workspace_bytes(const smh_late_fusion *e, int N);
+int smh_late_fusion_forward_x0_f32(smh_late_fusion *e, const float *d_x0p, int N, double alpha, void *d_work, size_t work_bytes,
+                                   float *d_pred, int *d_labels, float *d_heads, void *stream);
+size_t smh_late_fusion_dense_workspace_bytes(const smh_late_fusion *e, int Tc, int shift);
+int smh_late_fusion_forward_dense_f32(smh_late_fusion *e, const float *d_fv, int Tc, int shift, double alpha, void *d_work,
+                                      size_t work_bytes, float *d_pred, int *d_labels, float *d_heads, void *stream);
 /* g = grad * grad_scale (+ l2 term); per-tensor clip to `clipnorm` (<= 0: off); v = momentum*v - lr*g; w += v;
  * BN moving statistics <- 0.99*old + 0.01*batch; operand buffers re-packed on the device.              */
 int smh_trainer_apply_sgd_f32(smh_trainer *t, float lr, float momentum, float clipnorm, float grad_scale, void *stream);

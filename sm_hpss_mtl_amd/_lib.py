@@ -138,6 +138,15 @@ SIGNATURES = {
     "smh_fusion_forward_x0_f32": (_i, [_vp, _fp, _i, _vp, _sz, _fp, _vp]),
     "smh_fusion_dense_workspace_bytes": (_sz, [_vp, _i, _i]),
     "smh_fusion_forward_dense_f32": (_i, [_vp, _fp, _i, _i, _vp, _sz, _fp, _vp]),
+    "smh_late_fusion_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "smh_late_fusion_destroy": (None, [_vp]),
+    "smh_late_fusion_w0_ptr": (_vp, [_vp, _vp]),
+    "smh_late_fusion_workspace_bytes": (_sz, [_vp, _i]),
+    "smh_late_fusion_forward_f32": (_i, [_vp, _fp, _fp, _i, C.c_double, _vp, _sz, _fp, _vp, _fp, _vp]),
+    "smh_late_fusion_x0_workspace_bytes": (_sz, [_vp, _i]),
+    "smh_late_fusion_forward_x0_f32": (_i, [_vp, _fp, _i, C.c_double, _vp, _sz, _fp, _vp, _fp, _vp]),
+    "smh_late_fusion_dense_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "smh_late_fusion_forward_dense_f32": (_i, [_vp, _fp, _i, _i, C.c_double, _vp, _sz, _fp, _vp, _fp, _vp]),
 }
 
 _lib = None

@@ -47,6 +47,13 @@ struct TcnArgs {
     // from that they do exactly what a launch of their own would
     const float *pair_X, *pair_W0, *pair_Wb;
     float *pair_trunk;
+    // A second COMPLETE model in the same grid (the late-fusion ensemble, smh_late_fusion.hip; inference, not trunk_only): row 1 also
+    // reads pair_WhA / pair_hp and writes its own (N, out_dim) pair_out.  pair_status: the error word row 1 reports to -- the second model's
+    // here, `status` itself for the trunk pair.  The kernel copies these into locals: do not write to the kernel-argument struct in
+    // device code, or the compiler copies the whole struct to scratch
+    const float *pair_WhA, *pair_hp;
+    float *pair_out;
+    int *pair_status;
 };
 
 // training-mode extras of the forward kernel (all optional)
@@ -151,6 +158,9 @@ struct ForwardOpts {
     const smh_model *pair = nullptr;
     const float *pair_x = nullptr;
     float *pair_trunk = nullptr;
+    // pair_out != nullptr: the paired launch runs the WHOLE forward of both models (not trunk_only): `pair`'s Dense-on-trunk and
+    // heads too, its (N, out_dim) output to pair_out; pair_trunk is then optional like d_trunk.  Same geometry and head kind as m
+    float *pair_out = nullptr;
 };
 int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
                    hipStream_t st, const ForwardOpts &opt = {});

@@ -397,7 +397,11 @@ b3mtl_forward_kernel(TcnArgs a, const float *__restrict__ X, const float *__rest
     const int units = (GR + 15) >> 4;
     const int ZR = a.GRP;  // all-zero row behind the GRP activation rows of each buffer (padding taps of the dilated conv)
     float *xa = lds, *xb = lds + (size_t)(a.GRP + 1) * SX;
-    if (a.pair_Wb && blockIdx.y) X = a.pair_X, W0 = a.pair_W0, Wb = a.pair_Wb, trunk = a.pair_trunk;  // (uniform) second trunk of a paired launch
+    int *status = a.status;  // the error word this workgroup reports to
+    if (!TRAIN && a.pair_Wb && blockIdx.y) {  // (uniform) second trunk / second model of a paired launch (inference only)
+        X = a.pair_X, W0 = a.pair_W0, Wb = a.pair_Wb, trunk = a.pair_trunk;
+        WhA = a.pair_WhA, hp = a.pair_hp, out = a.pair_out, status = a.pair_status;
+    }
     const bool tracing = TRACE && a.trace != nullptr;
     if (tracing && blockIdx.x < 256 && threadIdx.x == 0) a.trace[4 * 3000 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 
@@ -575,7 +579,7 @@ b3mtl_forward_kernel(TcnArgs a, const float *__restrict__ X, const float *__rest
     auto one_block = [&](int blk, BlockW &w, auto prefetch) {
         save_acts(xin, blk);
         run_block<TRAIN>(w, 1 << (blk % a.n_dil), T, GR, ZR, ti, q, xin, xout, drop0 ? drop0 + (size_t)blk * C : nullptr, dstride,
-                         ub0 ? ub0 + (size_t)blk * T * C : nullptr, ustride, prefetch, lane, xch, blk + 1, a.spin_limit, a.status);
+                         ub0 ? ub0 + (size_t)blk * T * C : nullptr, ustride, prefetch, lane, xch, blk + 1, a.spin_limit, status);
         float *tmp = xin;
         xin = xout;
         xout = tmp;
@@ -1013,7 +1017,7 @@ b3mtl_forward_kernel(TcnArgs a, const float *__restrict__ X, const float *__rest
     if (gave_up) {  // a dependency never arrived: the outputs are not results -- say so in the model's error word
         __syncthreads();
         for (int i = threadIdx.x; i < (a.trunk_only ? 0 : g_here * a.out_dim); i += blockDim.x) out[(size_t)n0 * a.out_dim + i] = 0.f;
-        if (threadIdx.x == 0 && a.status) atomicOr(a.status, 1);
+        if (threadIdx.x == 0 && status) atomicOr(status, 1);
     }
 }
 
@@ -1187,6 +1191,7 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     a.trace = nullptr;
     a.from_x0 = 0, a.x0_shift = 0, a.x0_T = 0, a.x0_one = 0;
     a.pair_X = a.pair_W0 = a.pair_Wb = nullptr, a.pair_trunk = nullptr;
+    a.pair_WhA = a.pair_hp = nullptr, a.pair_out = nullptr, a.pair_status = nullptr;
     a.status = m->d_status, a.spin_limit = kSkewSpinLimit;
     a.D = m->D, a.NH = m->NH, a.n_mt = m->n_mt, a.n_classes = m->cfg.n_classes, a.n_heads = m->n_heads;
     a.out_dim = m->out_dim;
@@ -1238,13 +1243,24 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
     a.trunk_only = opt.trunk_only;
     a.from_x0 = opt.from_x0, a.x0_shift = opt.x0_shift, a.x0_T = opt.x0_T;
     a.x0_one = opt.from_x0 ? opt.x0_one : 0;
-    if (opt.pair) {
+    if (opt.pair && opt.pair_out) {  // two complete models in one grid (the late-fusion ensemble)
+        const smh_model *p = opt.pair;
+        SMH_REQUIRE(!tio && !opt.trunk_only && d_out && opt.pair_x, "paired full forward: inference of two whole models, each to its own output");
+        SMH_REQUIRE(p->cfg.n_feat == m->cfg.n_feat && p->cfg.patch_size == m->cfg.patch_size && p->n_blocks == m->n_blocks &&
+                        p->cfg.n_dilations == m->cfg.n_dilations && p->nW0 == m->nW0 && p->nWb == m->nWb && p->nW0 > 0 &&
+                        p->heads == m->heads && p->cfg.n_classes == m->cfg.n_classes && p->nWhA == m->nWhA && p->nhp == m->nhp &&
+                        p->out_dim == m->out_dim,
+                    "paired full forward: the two models differ in geometry or head kind");
+        a.pair_X = opt.pair_x, a.pair_W0 = p->d_W0, a.pair_Wb = p->d_Wb, a.pair_trunk = opt.pair_trunk;
+        a.pair_WhA = p->d_WhA, a.pair_hp = p->d_hp, a.pair_out = opt.pair_out, a.pair_status = p->d_status;
+    } else if (opt.pair) {
         const smh_model *p = opt.pair;
         SMH_REQUIRE(!tio && opt.trunk_only && d_trunk && opt.pair_x && opt.pair_trunk, "paired trunk launch: inference to the trunk taps only");
         SMH_REQUIRE(p->cfg.n_feat == m->cfg.n_feat && p->cfg.patch_size == m->cfg.patch_size && p->n_blocks == m->n_blocks &&
                         p->cfg.n_dilations == m->cfg.n_dilations && p->nW0 == m->nW0 && p->nWb == m->nWb && p->nW0 > 0,
                     "paired trunk launch: the two trunks differ in geometry");
         a.pair_X = opt.pair_x, a.pair_W0 = p->d_W0, a.pair_Wb = p->d_Wb, a.pair_trunk = opt.pair_trunk;
+        a.pair_status = a.status;  // both trunks belong to one model: row 1 reports to m's error word, as it always has
     }
     // timing probes (outputs invalid; training would read stale activations): only under SMH_ENABLE_PROBES=1, announced on stderr
     if (const char *ev = smh::probe_env("SMH_TCN_BLOCKS")) a.n_blocks = atoi(ev);  // tools/tune_model.py

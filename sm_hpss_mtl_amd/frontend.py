@@ -31,8 +31,11 @@ STFT_PRECISIONS = {"f32": _lib.SMH_STFT_F32, "f64": _lib.SMH_STFT_F64}
 def _l0_kernel(model):
     """(device address of the (rows_in, 32) layer-0 kernel the feature kernel multiplies by, rows_in) of a model with a fused
     layer-0 path: B3MTL / cascaded -- its initial-conv kernel, rows_in = n_feat; FusionMTL -- trunk H's kernel followed by trunk
-    P's, rows_in = 2 * n_feat.  Anything else raises."""
+    P's, rows_in = 2 * n_feat; late_fusion.LateFusion -- model H's kernel followed by model P's, rows_in = 2 * n_feat.  Anything else
+    raises."""
     from .model import HEADS_FUSION
+    if getattr(model, "LATE_FUSION", False):
+        return model.w0_ptr(), 2 * model.n_feat
     model._sync_weights()
     fusion = getattr(model, "HEADS", None) == HEADS_FUSION
     w0 = model.lib.smh_fusion_w0_ptr(model._h) if fusion else model.lib.smh_model_w0_ptr(model._h)
@@ -244,7 +247,8 @@ class Frontend:
         """`features` fused with the first layer of `model` (B3MTL): returns dict(fv, x0p (B*nP, 2, W, 32)[, patches]).
         Feed x0p to `model.forward_from_x0`.  Same logits as features -> forward_device within f32 tolerance.
         A FusionMTL whose 2 * n_feat equals the featuregram's rows works too: half 0 of x0p is then trunk H's first layer,
-        half 1 trunk P's, and x0p goes to `model.forward_from_x0_halves`."""
+        half 1 trunk P's, and x0p goes to `model.forward_from_x0_halves`.  The same holds for a late_fusion.LateFusion ensemble
+        (half 0 is model H's first layer, half 1 model P's)."""
         S, harm, perc = _f32c(S, "S"), _f32c(harm, "harm"), _f32c(perc, "perc")
         B, K, T = S.shape
         if int(harm_layout) == 2 and harm.numel() < B * self.lib.smh_harm_buffer_floats(K, T):

@@ -93,7 +93,8 @@ def smooth_labels(Predictions, PtdLabels, win_size, smooth_type="prediction"):
 def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000):
     """fv (2R, nFrames) HarmPerc featuregram of one file -> 1-D float32 numpy track of the chosen head's
     probability, one value per patch, batches concatenated (DAFx12...:612-676).  model: B3MTL, cascaded, or FusionMTL (per-branch
-    n_feat = R; the file-wise predict of Intermediate_Fusion_Results.py:441-590)."""
+    n_feat = R; the file-wise predict of Intermediate_Fusion_Results.py:441-590).  A late_fusion.LateFusion ensemble (per-model n_feat
+    = R) has the one output '3C' and returns its blended (nP, n_classes) track instead of a 1-D one."""
     fe = _frontend()
     d = _dev(fv)
     if d.dim() != 2 or d.shape[0] % 2:
@@ -106,6 +107,9 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
         if n == output:
             break
         col += o.shape[1]
+    # the ensemble's one output is the whole blended row; every other model gives one column of its output
+    late = getattr(model, "LATE_FUSION", False)
+    sel = slice(None) if late else col
     R = d.shape[0] // 2
     # the intermediate-fusion model reads the two halves as two inputs; its n_feat is the per-branch width
     fusion = hasattr(model, "forward_from_x0_halves")
@@ -125,7 +129,7 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
             # get_feature_patches does (:647), layer 0 once per frame, every hop-W_shift patch a window of it
             o = model.forward_dense(fe.standardize_rows(chunk), W_shift)
             if o.shape[0]:
-                preds.append(o[:, col])
+                preds.append(o[:, sel])
             continue
         # get_feature_patches on the batch (:647): tile if short, standardise each half over the batch, hop-W_shift
         # patches; written time-major = the transposed TCN input of :660
@@ -134,9 +138,9 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
         if h.shape[0] == 0:
             continue
         x = [h, p] if fusion else torch.cat([h, p], dim=2)  # (the fusion model takes the halves as they are: no copy)
-        preds.append(model.forward_device(x)[:, col])
+        preds.append(model.forward_device(x)[:, sel])
     if not preds:
-        return np.zeros((0,), np.float32)
+        return np.zeros((0, model.out_dim) if late else (0,), np.float32)
     out = torch.cat(preds)
     if hasattr(model, "check_status"):
         model.check_status()  # the forwards above only enqueued work: a device-side give-up raises here, before the track leaves

@@ -37,7 +37,11 @@ class HotPath:
         kernel applies both trunks' first layers (smh_fusion_w0_ptr) and the model starts from the per-half partials
         (forward_from_x0_halves); nothing of the patches is built.  fuse_l0=False: patches -> their two halves -> forward_device;
         the halves of a (N, W, 2 * n_feat) patch tensor are strided views, so this path COPIES them into two contiguous tensors
-        every step (preallocated; the model's C ABI takes contiguous inputs)."""
+        every step (preallocated; the model's C ABI takes contiguous inputs).
+        model may also be a late_fusion.LateFusion ensemble (f32, no trunk tap), fed exactly like the FusionMTL: fuse_l0=True -- the
+        feature kernel applies both models' first layers (`w0_ptr()`) and forward_from_x0_halves starts from the per-half partials;
+        fuse_l0=False -- the two contiguous halves of the patches go to forward_device.  `logits` is then the blended '3C'
+        (B * nP, n_classes)."""
         self.fe, self.model, self.lib, self._h = fe, model, fe.lib, fe._h
         self.B, self.n_samples, self.W = int(batch), int(n_samples), int(patch)
         self.shift = int(patch if shift is None else shift)
@@ -45,7 +49,13 @@ class HotPath:
         if model_dtype not in ("f32", "bf16"):
             raise ValueError("model_dtype must be 'f32' or 'bf16'")
         self.fuse_l0 = bool(fuse_l0) and model is not None  # both network dtypes start from the layer-0 partials
-        self.fusion = model is not None and getattr(model, "HEADS", None) == HEADS_FUSION
+        self.late = model is not None and getattr(model, "LATE_FUSION", False)
+        if self.late and model_dtype != "f32":
+            raise ValueError("the late-fusion ensemble has the f32 forward only, got model_dtype=%r" % (model_dtype,))
+        if self.late and keep_trunk:
+            raise ValueError("the late-fusion ensemble has no trunk tap (keep_trunk)")
+        # (two per-half inputs: the ensemble takes the FusionMTL's route through the step)
+        self.fusion = model is not None and (getattr(model, "HEADS", None) == HEADS_FUSION or self.late)
         if self.fusion and model_dtype != "f32":
             raise ValueError("the intermediate-fusion model has the f32 forward only, got model_dtype=%r" % (model_dtype,))
         if self.fusion and keep_trunk:
@@ -100,7 +110,7 @@ class HotPath:
         if record is not None:
             record[2].record()
         if self.fuse_l0:
-            w0 = lib.smh_fusion_w0_ptr(m._h) if self.fusion else lib.smh_model_w0_ptr(m._h)
+            w0 = m.w0_ptr() if self.late else (lib.smh_fusion_w0_ptr(m._h) if self.fusion else lib.smh_model_w0_ptr(m._h))
             got = _lib.check(lib.smh_features_l0_f32(h, _p(self.S), _p(self.harm), _p(self.perc), lay, self.B, self.T,
                                                      self.W, self.shift, _p(self.fv), _p(self.patches),
                                                      C.c_void_p(w0), _p(self.x0p),
