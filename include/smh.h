@@ -250,7 +250,8 @@ typedef struct smh_model_cfg {
                             * 1 = keras-tcn >= 2.8 (no initial conv; per block two dilated convs, relu each, shortcut = input or
                             * a 1x1 'matching' conv, relu of the sum) -- inference forward only (smh_model_forward_f32).
                             * Canonical weight order for 1: per block [conv0 kernel (3,Cin,32), bias, conv1 kernel (3,32,32),
-                            * bias, (first block: matching kernel (1,n_feat,32), bias)], then '3C' and the heads as for 0. */
+                            * bias, (first block, unless n_feat == 32: matching kernel (1,n_feat,32), bias)], then '3C' and the
+                            * heads as for 0.  n_feat == 32: the channel counts agree, identity shortcut in every block. */
 } smh_model_cfg;
 #define SMH_TCN_BLOCK_2_3 0
 #define SMH_TCN_BLOCK_2_8 1

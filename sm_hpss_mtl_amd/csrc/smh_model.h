@@ -143,6 +143,16 @@ struct Offsets {
 inline size_t trunk_floats(const smh_model_cfg &c) {
     return (size_t)c.n_feat * C + C + (size_t)c.nb_stacks * c.n_dilations * (3 * C * C + C + C * C + C);
 }
+// floats of one keras-tcn >= 2.8 trunk (block_variant 1) in canonical order: block 0 = [conv0 (3, F, 32), b, conv1 (3, 32, 32), b] and,
+// only where n_feat != 32, [matching (1, F, 32), b] -- Keras builds the 1x1 'matching' convolution when the channel counts differ
+// and takes the identity shortcut otherwise; later blocks = [conv0 (3, 32, 32), b, conv1 (3, 32, 32), b]
+__host__ __device__ inline size_t v2_block0_floats(int F) {
+    return (size_t)3 * F * C + C + 3 * C * C + C + (F != C ? (size_t)F * C + C : 0);
+}
+constexpr size_t kV2BlockFloats = 2 * (3 * C * C + C);
+inline size_t trunk_floats_v2(const smh_model_cfg &c) {
+    return v2_block0_floats(c.n_feat) + (size_t)(c.nb_stacks * c.n_dilations - 1) * kV2BlockFloats;
+}
 Offsets offsets(const smh_model *m);
 void fill_args(const smh_model *m, int N, TcnArgs *a, size_t *lds);
 int repack(smh_model *m, hipStream_t st);  // d_flat -> packed operand buffers

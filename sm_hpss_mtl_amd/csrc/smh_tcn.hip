@@ -1045,7 +1045,7 @@ static void pack_host(const smh_model *m, const float *h, std::vector<float> &W0
     if (m->heads == SMH_HEADS_FUSION) {  // the trunks are packed by m->trunk[0 / 1]; the fused BN is read in canonical order
         p += 2 * trunk_floats(m->cfg) + (size_t)4 * D;
     } else if (m->cfg.block_variant == 1) {  // smh_tcn_v2.hip reads the trunk from the canonical tensor: only the heads are packed
-        p += (size_t)3 * F * C + C + 3 * C * C + C + (size_t)F * C + C + (size_t)(m->n_blocks - 1) * 2 * (3 * C * C + C);
+        p += trunk_floats_v2(m->cfg);
     } else {
     for (int s = 0; s < FQ; ++s)
         for (int mt = 0; mt < 2; ++mt)
@@ -1396,8 +1396,7 @@ extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_m
     SMH_REQUIRE(cfg->block_variant == 0 || cfg->block_variant == 1, "block_variant must be 0 (keras-tcn 2.3.x) or 1 (>= 2.8)");
     size_t n = (size_t)cfg->n_feat * C + C;
     n += (size_t)m->n_blocks * (3 * C * C + C + C * C + C);
-    if (cfg->block_variant == 1)
-        n = (size_t)3 * cfg->n_feat * C + C + 3 * C * C + C + (size_t)cfg->n_feat * C + C + (size_t)(m->n_blocks - 1) * 2 * (3 * C * C + C);
+    if (cfg->block_variant == 1) n = trunk_floats_v2(*cfg);  // (no 'matching' tensors at n_feat == 32: identity shortcut)
     if (heads == SMH_HEADS_FUSION) n = 2 * trunk_floats(*cfg) + (size_t)4 * m->D;  // two trunks, the fused BatchNorm
     n += (size_t)m->D * cfg->n_classes + cfg->n_classes;
     for (int i = 0; i < m->n_heads; ++i) n += (size_t)m->D * kHidden + kHidden + head_tail_floats(m, i);

@@ -82,9 +82,11 @@ b3mtl_forward_v2_kernel(TcnArgs a, const float *__restrict__ X, const float *__r
     float *xa = lds, *ya = lds + (size_t)(a.GRP + 1) * SX;
     if (threadIdx.x < SX) xa[(size_t)ZR * SX + threadIdx.x] = 0.f, ya[(size_t)ZR * SX + threadIdx.x] = 0.f;
 
-    // canonical offsets: block 0 = [conv0 (3,F,32), b, conv1 (3,32,32), b, matching (1,F,32), b]; later blocks = [conv0, b, conv1, b]
-    const size_t blk0_floats = (size_t)3 * F * C + C + 3 * C * C + C + (size_t)F * C + C;
-    const size_t blk_floats = 2 * (3 * C * C + C);
+    // canonical offsets: block 0 = [conv0 (3,F,32), b, conv1 (3,32,32), b, matching (1,F,32), b]; later blocks = [conv0, b, conv1, b].
+    // F == 32: the channel counts match, Keras builds no matching convolution and block 0 has the identity shortcut too
+    const bool matching = F != C;
+    const size_t blk0_floats = v2_block0_floats(F);
+    const size_t blk_floats = kV2BlockFloats;
 
     // ---- block 0, phase A: y = relu(conv0(x)) straight from the HBM patches; K order per tap: channel q*FQ + s ----
     for (int u = wave; u < units; u += nw) {
@@ -123,15 +125,23 @@ b3mtl_forward_v2_kernel(TcnArgs a, const float *__restrict__ X, const float *__r
             const int g = Rc / T, t = Rc - g * T;
             f32x4 y0, y1;
             conv_tile(cw, ya, Rc, t, 1, T, ZR, q, y0, y1);
-            f32x4 s0 = *reinterpret_cast<const f32x4 *>(km + (size_t)F * C + 4 * q);
-            f32x4 s1 = *reinterpret_cast<const f32x4 *>(km + (size_t)F * C + 16 + 4 * q);
-            const float *xr = X + ((size_t)(n0 + g) * T + t) * F + (size_t)q * a.FQ;
-            const float *wk = km + (size_t)q * a.FQ * C + j;
-            for (int s = 0; s < a.FQ; ++s) {
-                const bool live = q * a.FQ + s < F;
-                const float xv = live ? xr[s] : 0.f;
-                s0 = mfma4(live ? wk[(size_t)s * C] : 0.f, xv, s0);
-                s1 = mfma4(live ? wk[(size_t)s * C + 16] : 0.f, xv, s1);
+            f32x4 s0, s1;
+            if (matching) {
+                s0 = *reinterpret_cast<const f32x4 *>(km + (size_t)F * C + 4 * q);
+                s1 = *reinterpret_cast<const f32x4 *>(km + (size_t)F * C + 16 + 4 * q);
+                const float *xr = X + ((size_t)(n0 + g) * T + t) * F + (size_t)q * a.FQ;
+                const float *wk = km + (size_t)q * a.FQ * C + j;
+                for (int s = 0; s < a.FQ; ++s) {
+                    const bool live = q * a.FQ + s < F;
+                    const float xv = live ? xr[s] : 0.f;
+                    s0 = mfma4(live ? wk[(size_t)s * C] : 0.f, xv, s0);
+                    s1 = mfma4(live ? wk[(size_t)s * C + 16] : 0.f, xv, s1);
+                }
+            } else {  // identity shortcut: this lane's accumulator channels 4 q + r (+ 16) of its own input row (F == 32; the
+                      // patches carry no alignment promise: dword loads)
+                const float *xr = X + ((size_t)(n0 + g) * T + t) * C + 4 * q;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s0[r] = xr[r], s1[r] = xr[16 + r];
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

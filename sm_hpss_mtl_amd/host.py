@@ -80,7 +80,10 @@ class HostModel(ModelSurfaceMixin):
         return [(t[0], tuple(t[1])) for t in self._spec]
 
     def _init_store(self):
-        assert self.count_params() == getattr(self.lib, self._C_PREFIX + "_num_params")(self._h)
+        n_host, n_lib = self.count_params(), getattr(self.lib, self._C_PREFIX + "_num_params")(self._h)
+        if n_host != n_lib:
+            raise RuntimeError("%s: the host weight spec has %d parameters, libsmh's %s object has %d -- the two canonical layouts "
+                               "disagree" % (type(self).__name__, n_host, self._C_PREFIX, n_lib))
         self._dirty = True          # host copy newer than the device master
         self._device_newer = False  # device master newer than the host copy (after optimiser steps)
 

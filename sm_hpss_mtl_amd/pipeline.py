@@ -30,7 +30,9 @@ class HotPath:
                  model_dtype="f32", keep_patches=False, keep_trunk=False, device=None):
         """fe: Frontend, model: B3MTL, or None for the front end alone (BASELINE config 2, "HPSS-only": three launches, the step
         ends with the featuregram; no patches, no logits).  fuse_l0: the network's first 1x1 convolution runs inside the feature kernel
-        (smh_features_l0_f32 + smh_model_forward_x0_f32) instead of patches -> smh_model_forward_f32.
+        (smh_features_l0_f32 + smh_model_forward_x0_f32) instead of patches -> smh_model_forward_f32.  A model of the keras-tcn 2.8
+        block (tcn_block="2.8") has no such convolution: fuse_l0 falls back to the patch path (`self.fuse_l0` is False) and
+        model_dtype="bf16" is refused here.
         keep_patches / keep_trunk: also write the standardised time-major patches / the TCN output (N, W, 32) -- parity taps
         that `model.predict` does not return; never set by bench.py.
         model may be a FusionMTL whose 2 * n_feat equals the featuregram's rows (f32, no trunk tap).  fuse_l0=True: the feature
@@ -49,6 +51,13 @@ class HotPath:
         if model_dtype not in ("f32", "bf16"):
             raise ValueError("model_dtype must be 'f32' or 'bf16'")
         self.fuse_l0 = bool(fuse_l0) and model is not None  # both network dtypes start from the layer-0 partials
+        if model is not None and getattr(model, "block_variant", 0) != 0:
+            # the keras-tcn 2.8 block has no initial 1x1 convolution to fuse and no split-bf16 forward: decided here, not by a
+            # refusal in the middle of step()
+            if model_dtype != "f32":
+                raise ValueError("the keras-tcn 2.8 block (tcn_block=%r) has the f32 forward only, got model_dtype=%r"
+                                 % (model.tcn_block, model_dtype))
+            self.fuse_l0 = False  # patches -> forward_device
         self.late = model is not None and getattr(model, "LATE_FUSION", False)
         if self.late and model_dtype != "f32":
             raise ValueError("the late-fusion ensemble has the f32 forward only, got model_dtype=%r" % (model_dtype,))

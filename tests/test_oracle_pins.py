@@ -375,6 +375,63 @@ def test_b3mtl_forward_outputs_vs_torch_nn(ncls, W):
         np.testing.assert_allclose(a, b.numpy(), atol=1e-6)
 
 
+def _scaled_v2_weights(F, W, nb, nd, scale=0.5, seed=9):
+    """init_weights_v2 with the convolution kernels scaled as the GPU tests of the 2.8 block scale them (no channel normalisation:
+    the trunk of unscaled glorot kernels grows with every block)."""
+    w = b3_mtl.init_weights_v2(seed=seed, n_feat=F, patch_size=W, n_classes=3, nb_stacks=nb, n_dil=nd, randomize_bn=True)
+    for k in w:
+        if "/conv" in k and k.endswith("kernel"):
+            w[k] = (w[k] * scale).astype(np.float32)
+    return w
+
+
+@pytest.mark.parametrize("F,nb,nd,W", [(240, 3, 8, 68), (32, 1, 1, 25), (61, 3, 3, 50), (32, 3, 8, 68), (20, 1, 1, 25)])
+def test_b3mtl_v2_trunk_vs_torch_conv1d(F, nb, nd, W):
+    """oracle.b3_mtl.tcn_forward_v2 (the residual block of keras-tcn >= 2.8) against a float64 build of the same trunk from
+    torch.nn.functional.conv1d with the same weights: per (stack, dilation d) two Conv1D(32, 3, dilation d, 'same') -- padding d,
+    kernels permuted from Keras' (k, cin, cout) to torch's (cout, cin, k) -- each followed by relu, a 1x1 'matching' convolution
+    on the shortcut only where the block's input does not have 32 channels (the first block, unless n_feat == 32: identity), relu
+    of the sum.  No initial convolution, nothing behind the last block.  The same 1e-6 as the 2.3 cross-check above; the outputs
+    are mtl_heads on the flattened trunk, which that cross-check pins."""
+    import torch
+    import torch.nn.functional as tf
+    w = _scaled_v2_weights(F, W, nb, nd)
+    assert (("tcn/s0_d1/matching/kernel" in w) == (F != 32)) and not any("/matching/" in k for k in w if not k.startswith("tcn/s0_d1/"))
+    x = np.random.default_rng(F + W).standard_normal((4, W, F)).astype(np.float32)
+
+    def t(a):
+        return torch.tensor(np.asarray(a, np.float64))
+
+    def conv(h, p, d):                                                                  # h: (N, C, T)
+        return tf.conv1d(h, t(w[p + "/kernel"]).permute(2, 1, 0), t(w[p + "/bias"]), padding=d * (w[p + "/kernel"].shape[0] // 2),
+                         dilation=d)
+
+    h = t(x).permute(0, 2, 1)
+    for s in range(nb):
+        for i in range(nd):
+            d, p = 2 ** i, "tcn/s%d_d%d" % (s, 2 ** i)
+            y = torch.relu(conv(torch.relu(conv(h, p + "/conv0", d)), p + "/conv1", d))
+            sc = conv(h, p + "/matching", 1) if h.shape[1] != 32 else h
+            h = torch.relu(sc + y)
+    ref = h.permute(0, 2, 1).numpy()                                                    # (N, T, C): Keras Flatten order
+    got = b3_mtl.tcn_forward_v2(x, w, nb, nd)
+    assert got.shape == ref.shape == (4, W, 32) and got.dtype == np.float32
+    assert 0.1 <= ref.max() <= 200 and np.mean(ref == 0) <= 0.9                         # a live trunk, not a dead or exploded one
+    np.testing.assert_allclose(got, ref, atol=1e-6, rtol=1e-6)
+
+
+def test_b3mtl_forward_follows_the_weight_dict_to_the_v2_block():
+    """b3_mtl.forward (and through it oracle.inference.patch_probabilities) takes the two-convolution trunk for a dict from
+    init_weights_v2, identity first block included."""
+    for F in (32, 40):
+        w = _scaled_v2_weights(F, 25, 3, 8)
+        x = np.random.default_rng(F).standard_normal((3, 25, F)).astype(np.float32)
+        outs, trunk = b3_mtl.forward(x, w, return_trunk=True)
+        assert np.array_equal(trunk, b3_mtl.tcn_forward_v2(x, w))
+        for a, b in zip(outs, b3_mtl.mtl_heads(trunk.reshape(3, -1), w, 3)):
+            assert np.array_equal(a, b)
+
+
 # ---- transformers.audio_utils: an independent, librosa-compatible implementation of the mel filter bank, the dB conversion and
 # the spectrogram (the feature extraction behind Whisper etc., written to reproduce librosa's numbers) that IS installed here.
 def test_mel_basis_vs_transformers_audio_utils():

@@ -720,6 +720,18 @@ def test_b3mtl_two_conv_block_variant_vs_oracle(ncls, W, N, tmp_path):
         assert m2.tcn_block == "2.8"
         m2.load_weights(str(tmp_path / "v2.h5"))
         assert np.array_equal(m2.predict(x)[-1], m.predict(x)[-1])
+        # n_feat == nb_filters: Keras builds no 'matching' convolution (identity shortcut in the first block); a model saved
+        # from one instance reloads and predicts the same bits in another
+        from sm_hpss_mtl_amd.model import B3MTL
+        m32 = B3MTL(n_feat=32, patch_size=W, n_classes=ncls, seed=4, tcn_block="2.8")
+        assert not any("/matching/" in n for n in m32.weight_names()) and any("/matching/" in n for n in m.weight_names())
+        x32 = np.random.default_rng(13).standard_normal((N, W, 32)).astype(np.float32)
+        m32.save_weights(str(tmp_path / "v2_32.h5"))
+        m3 = model_from_json(m32.to_json())
+        assert (m3.n_feat, m3.tcn_block, m3.weight_names()) == (32, "2.8", m32.weight_names())
+        m3.load_weights(str(tmp_path / "v2_32.h5"))
+        for a, b in zip(m3.predict(x32), m32.predict(x32)):
+            assert np.array_equal(a, b) and np.isfinite(a).all()
         with pytest.raises(NotImplementedError):
             m.train_on_batch(x, {"S": np.zeros((N, 1)), "M": np.zeros((N, 1)), "R": np.zeros((N, 2)), "3C": np.eye(3)[np.zeros(N, int)]})
         with pytest.raises(ValueError):

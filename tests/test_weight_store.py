@@ -111,3 +111,11 @@ def test_refused_weights_leave_the_store_unchanged(store, bad):
         np.testing.assert_array_equal(got, want)
     store._sync_weights()
     assert store.lib.calls == []
+
+
+def test_a_parameter_count_the_library_does_not_share_is_an_error_naming_both(store):
+    """The host weight spec and the library's canonical layout are two statements of one order: where they disagree (a tensor one
+    side has and the other does not) construction stops with both counts, not with a bare assertion."""
+    setattr(store.lib, store._C_PREFIX + "_num_params", lambda h: N_PARAMS + 1056)
+    with pytest.raises(RuntimeError, match=r"\b%d\b.*\b%d\b" % (N_PARAMS, N_PARAMS + 1056)):
+        store._init_store()
