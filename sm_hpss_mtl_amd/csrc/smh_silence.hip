@@ -544,6 +544,23 @@ __global__ __launch_bounds__(kThreads) void mix_write_kernel(const float *__rest
     for (int i = lo + threadIdx.x; i < hi; i += kThreads) o[i] = __fadd_rn(__fmul_rn(fs, s[i]), __fmul_rn(fm, m[i % Nmu]));
 }
 
+// The route of smh_preprocess_signal_f32: the clip-in-LDS kernel needs N <= kFusedMaxN AND its samples + tables within
+// 155 KiB of LDS (short hops grow the tables); SMH_SILENCE_MULTIPASS (test hook) forces the general path.
+struct FusedPlan {
+    bool fused;
+    int maxrun;
+    size_t lds;
+};
+
+FusedPlan fused_plan(int N, int nF) {
+    FusedPlan p{};
+    p.maxrun = nF / 2 + 2;
+    p.lds = (size_t)((N + 3) & ~3) * 4 + (size_t)nF * 4 + (size_t)p.maxrun * 12 + 2 * (size_t)nF;
+    const bool multipass = getenv("SMH_SILENCE_MULTIPASS") != nullptr;
+    p.fused = N <= kFusedMaxN && !multipass && p.lds <= 155 * 1024;
+    return p;
+}
+
 int check_common(const char *fn, const void *d_x, int B, int N) {
     SMH_REQUIRE(B >= 0 && B <= 65535, "%s: B must be in [0, 65535]", fn);
     SMH_REQUIRE(N >= 1, "%s: N must be >= 1", fn);
@@ -655,17 +672,13 @@ extern "C" int smh_preprocess_signal_f32(const float *d_x, int B, int N, int fs,
     SMH_REQUIRE(d_out != d_x, "smh_preprocess_signal_f32: in-place operation is not supported");
     hipStream_t st = (hipStream_t)stream;
     const int nF = 1 + (N + 2 * (frameSize / 2) - frameSize) / hop;
-    const bool multipass = getenv("SMH_SILENCE_MULTIPASS") != nullptr;  // test hook: force the general path
-    if (N <= kFusedMaxN && !multipass) {  // clip fits in LDS: one read, one write
-        const int maxrun = nF / 2 + 2;
-        const size_t lds = (size_t)((N + 3) & ~3) * 4 + (size_t)nF * 4 + (size_t)maxrun * 12 + 2 * (size_t)nF;
-        if (lds <= 155 * 1024) {
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)preprocess_fused_kernel,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(preprocess_fused_kernel, dim3(B), dim3(kFusedThreads), lds, st, d_x, N, frameSize, hop, nF,
-                               maxrun, fs, 0.025, 0.075, d_out, d_n_keep);
-            return smh::launch_status("preprocess_fused_kernel");
-        }
+    const FusedPlan plan = fused_plan(N, nF);
+    if (plan.fused) {  // clip fits in LDS: one read, one write
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)preprocess_fused_kernel,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+        hipLaunchKernelGGL(preprocess_fused_kernel, dim3(B), dim3(kFusedThreads), plan.lds, st, d_x, N, frameSize, hop, nF,
+                           plan.maxrun, fs, 0.025, 0.075, d_out, d_n_keep);
+        return smh::launch_status("preprocess_fused_kernel");
     }
     const SilWork w = carve(d_work, B, N, hop);
     if (work_bytes < w.bytes)
@@ -678,6 +691,16 @@ extern "C" int smh_preprocess_signal_f32(const float *d_x, int B, int N, int fs,
                                true, st))
         return rc;                                                                          // :339
     return launch_normalize(d_out, B, N, d_out, w, st);                                     // :348-349
+}
+
+// Test-only (not in include/smh.h): the route smh_preprocess_signal_f32 takes for these arguments in this process --
+// 1 = clip-in-LDS kernel, 0 = multi-pass, -1 = arguments the call itself rejects.
+extern "C" int smh_internal_preprocess_route(int N, int fs, int Tw, int Ts) {
+    if (N < 1 || fs < 1 || Tw < 1 || Ts < 1) return -1;
+    const int frameSize = (int)((double)Tw * fs / 1000.0);
+    const int hop = (int)((double)Ts * fs / 1000.0);
+    if (frameSize < 1 || hop < 1 || N <= frameSize / 2) return -1;
+    return fused_plan(N, 1 + (N + 2 * (frameSize / 2) - frameSize) / hop).fused ? 1 : 0;
 }
 
 extern "C" int smh_mix_signals_f32(const float *d_sp, const float *d_mu, int B, int N, int N_mu, const float *d_target_db,
