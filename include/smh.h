@@ -186,6 +186,39 @@ int smh_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long
                             int W, int shift, float *d_fv, float *d_patches /* or NULL */, void *d_work, size_t work_bytes,
                             void *stream);
 
+/* ---- the four feature branches WITHOUT harmonic-percussive separation (lib/preprocessing.py:378-402): Spec, LogSpec, MelSpec,
+ * LogMelSpec.  One featuregram of `rows` = smh_ctx_feat_rows() rows per clip (no H || P pair), no medians, no soft masks:
+ *     n_mels <= 0, log_db = 0   Spec        fv = |S|
+ *     n_mels <= 0, log_db = 1   LogSpec     fv = power_to_db(|S|**2)
+ *     n_mels >  0, log_db = 0   MelSpec     fv = mel @ |S|**2                  (melspectrogram(y=..., sr=fs): power = 2.0)
+ *     n_mels >  0, log_db = 1   LogMelSpec  fv = power_to_db((mel @ |S|**2)**2)
+ * The mel branches project the POWER spectrogram, and the reference builds their basis for sr = fs: create the context with
+ * mel_sr = fs (16000), not the 22050 of the '*HarmPerc*' branches.  power_to_db: ref 1, amin 1e-10 on the f32 square, top_db 80 below
+ * the maximum of the clip's whole array.  Read from the context: n_fft, win_length, hop, n_mels, log_db, mel_sr and the STFT
+ * precision; l_harm and l_perc are ignored.  The mel projection keeps a K x 64-frame image in LDS: n_fft <= 1198 with a filterbank.
+ * Any T >= 1 takes the same two kernels (smh_plain.hip), so a clip gets the same bits alone, in a batch and in a ragged call.
+ *
+ * smh_plain_features_f32: d_S (B, K, T) -> d_fv (B, rows, T) and, with d_patches, the standardised time-major patches
+ *   (B*nP, W, rows) of get_feature_patches (tile-if-short, StandardScaler per row over the frames, tools.extract_patches, transpose).
+ *   d_maxkeys: B int32 of scratch.  Returns nP per clip.
+ * smh_plain_frontend_f32: d_audio (B, n_samples) -> the same, through the context's STFT; d_work of
+ *   smh_plain_frontend_workspace_bytes() bytes; d_S (B, K, T): optional tap of the magnitude spectrogram, or NULL.
+ * smh_plain_frontend_ragged_sizes / _f32: the contract of smh_frontend_ragged_sizes / smh_frontend_ragged_f32 above -- host offset and
+ *   length tables, one launch per stage over all clips, concatenated outputs, sub-batches when the workspace is smaller than asked
+ *   for -- with h_fv_off counting rows * T_b floats per clip and patches of (W, rows) floats.
+ * Bad arguments return SMH_E_INVALID (text in smh_last_error) before any launch. */
+int smh_plain_features_f32(const smh_ctx *ctx, const float *d_S, int B, int T, int W, int shift, float *d_fv,
+                           float *d_patches /* or NULL */, int32_t *d_maxkeys /* B */, void *stream);
+size_t smh_plain_frontend_workspace_bytes(const smh_ctx *ctx, int B, int n_samples);
+int smh_plain_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int W, int shift, float *d_fv,
+                           float *d_patches /* or NULL */, void *d_work, size_t work_bytes, float *d_S /* or NULL */, void *stream);
+int smh_plain_frontend_ragged_sizes(const smh_ctx *ctx, const long long *h_offsets, const int *h_lengths, int B, int W, int shift,
+                                    long long *h_fv_off /* B+1 */, long long *h_patch_off /* B+1 */, int *h_T /* B */,
+                                    int *h_nP /* B */, size_t *work_bytes);
+int smh_plain_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets, const int *h_lengths, int B,
+                                  int W, int shift, float *d_fv, float *d_patches /* or NULL */, void *d_work, size_t work_bytes,
+                                  void *stream);
+
 /* ---- 8f rank 1: load_and_preprocess_signal after the decode (lib/preprocessing.py:330-350) ------------------
  * Batched over B clips of N samples each, resident on the device.  Floating point: the mean is accumulated in
  * f64 in a fixed order (numpy: pairwise f32), everything else is the same f32 arithmetic as numpy.           */

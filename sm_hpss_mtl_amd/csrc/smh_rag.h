@@ -36,6 +36,10 @@ struct Item {
 //   2  the streaming kernels of smh_ragged.hip           3  neither: launch_hp_feat + launch_std_patch on the whole clip
 int feature_route(const smh_ctx *ctx, int T);
 
+// host -> device copy of a call's tables through a pinned slot of the context (smh_ragged.hip: stage_upload), stream-ordered on st;
+// the plain front end's ragged entry (smh_plain.hip) uploads its tables the same way
+int upload_tables(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst, hipStream_t st);
+
 }  // namespace smh_rag
 
 namespace smh_stft {

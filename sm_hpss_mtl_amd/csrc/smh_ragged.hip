@@ -567,6 +567,10 @@ int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, in
     return rc ? rc : 1;
 }
 
+int upload_tables(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst, hipStream_t st) {
+    return stage_upload(ctx, src, bytes, d_dst, st);
+}
+
 int feature_route(const smh_ctx *ctx, int T) {
     if (smh_features_blocked_ok(ctx, T, 0)) {
         if (!smh_median::blocked_harm_ok(ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc)) return 3;

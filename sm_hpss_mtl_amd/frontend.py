@@ -24,6 +24,14 @@ FEATS = {
 # One-half feature names (the intermediate-fusion driver, Intermediate_Fusion_Results.py:704-706) -> their '*HarmPercSpec' sibling:
 # get_featuregram computes the same H||P featuregram for them (lib/preprocessing.py:404-444); get_feature_patches keeps one half.
 HALF_FEATS = {h + t: h + "HarmPercSpec" for h in ("Mel", "LogMel", "", "Log") for t in ("HarmSpec", "PercSpec")}
+# The four branches without harmonic-percussive separation (lib/preprocessing.py:378-402), same (n_mels used?, log?) meaning.  Their
+# mel basis is built for sr = fs and applied to the POWER spectrogram (melspectrogram(y=Xin, sr=fs, ...): include/smh.h, smh_plain_*).
+PLAIN_FEATS = {
+    "Spec": (False, False),
+    "LogSpec": (False, True),
+    "MelSpec": (True, False),
+    "LogMelSpec": (True, True),
+}
 # FrontendConfig.stft_precision -> the C ABI's stft_precision (include/smh.h: SMH_STFT_F32 / SMH_STFT_F64)
 STFT_PRECISIONS = {"f32": _lib.SMH_STFT_F32, "f64": _lib.SMH_STFT_F64}
 
@@ -57,6 +65,9 @@ class FrontendConfig:
     # "f32": the fast STFT (|S| within 1e-5 of max|S| of the reference's); "f64": an f64 transform whose |S| equals
     # np.abs(librosa.core.stft(...)) bit for bit (include/smh.h: smh_ctx_create_ex).  Everything after the STFT is the same.
     stft_precision: str = "f32"
+    # False: one of PLAIN_FEATS -- no medians, no soft masks, one featuregram of `rows` rows per clip instead of the H || P pair
+    # (l_harm / l_perc are then ignored, and mel_sr is the audio's sampling rate)
+    hpss: bool = True
 
     def __post_init__(self):
         if self.stft_precision not in STFT_PRECISIONS:
@@ -65,9 +76,16 @@ class FrontendConfig:
     @staticmethod
     def from_params(PARAMS, n_fft, n_mels, featName, fs=16000):
         """Build from the reference's PARAMS dict (Proposed_Work_Results.py:723-807)."""
+        if featName in PLAIN_FEATS:  # PARAMS needs no l_harm / l_perc for these
+            use_mel, log = PLAIN_FEATS[featName]
+            return FrontendConfig(
+                n_fft=int(n_fft), win_length=int(PARAMS["Tw"] * fs / 1000), hop=int(PARAMS["Ts"] * fs / 1000),
+                n_mels=int(n_mels) if use_mel else 0, log_db=log, mel_sr=float(fs),
+                stft_precision=PARAMS.get("stft_precision", "f32"), hpss=False)
         featName = HALF_FEATS.get(featName, featName)
         if featName not in FEATS:
-            raise ValueError("featName %r is not one of the HPSS feature names %s" % (featName, sorted(FEATS) + sorted(HALF_FEATS)))
+            raise ValueError("featName %r is not one of the feature names %s"
+                             % (featName, sorted(FEATS) + sorted(HALF_FEATS) + sorted(PLAIN_FEATS)))
         use_mel, log = FEATS[featName]
         model = PARAMS["Model"]
         return FrontendConfig(
@@ -150,7 +168,13 @@ class Frontend:
         _lib.check(self.lib.smh_stft_mag_f32(self._h, _ptr(audio), B, N, _ptr(S), _stream()), "smh_stft_mag_f32")
         return S
 
+    def _need_hpss(self, what):
+        if not self.cfg.hpss:
+            raise ValueError("%s belongs to the harmonic-percussive path; this Frontend has a plain configuration (hpss=False): "
+                             "use plain_features / run" % what)
+
     def hpss_median(self, S, l_harm=None, l_perc=None):
+        self._need_hpss("hpss_median")
         S = _f32c(S, "S")
         B, K, T = S.shape
         lh = self.cfg.l_harm if l_harm is None else l_harm
@@ -224,6 +248,7 @@ class Frontend:
 
     def features(self, S, harm, perc, W=None, shift=None, out=None):
         """(S, harm, perc) -> dict(fv[, patches]): masks + mel + dB, then standardise + time-major patches."""
+        self._need_hpss("features")
         S, harm, perc = _f32c(S, "S"), _f32c(harm, "harm"), _f32c(perc, "perc")
         B, K, T = S.shape
         dev = S.device
@@ -249,6 +274,7 @@ class Frontend:
         A FusionMTL whose 2 * n_feat equals the featuregram's rows works too: half 0 of x0p is then trunk H's first layer,
         half 1 trunk P's, and x0p goes to `model.forward_from_x0_halves`.  The same holds for a late_fusion.LateFusion ensemble
         (half 0 is model H's first layer, half 1 model P's)."""
+        self._need_hpss("features_l0")
         S, harm, perc = _f32c(S, "S"), _f32c(harm, "harm"), _f32c(perc, "perc")
         B, K, T = S.shape
         if int(harm_layout) == 2 and harm.numel() < B * self.lib.smh_harm_buffer_floats(K, T):
@@ -273,10 +299,40 @@ class Frontend:
         assert got == nP
         return {"fv": fv, "x0p": x0p, "patches": pt, "n_patches": nP, "maxkeys": keys}
 
+    def plain_features(self, S, W=None, shift=None, out=None):
+        """Plain configurations (hpss=False): S (B, K, T) -> dict(fv (B, rows, T)[, patches (B*nP, W, rows)]) -- Spec / LogSpec /
+        MelSpec / LogMelSpec of lib/preprocessing.py:378-402 behind the STFT, then tile-if-short, StandardScaler per row and
+        time-major patches (`smh_plain_features_f32`)."""
+        if self.cfg.hpss:
+            raise ValueError("plain_features needs a plain configuration (FrontendConfig(hpss=False)); this one is harmonic-percussive")
+        S = _f32c(S, "S")
+        if S.dim() != 3 or S.shape[1] != self.K:
+            raise ValueError("plain_features: S must be (B, %d, T), got %s" % (self.K, tuple(S.shape)))
+        B, K, T = S.shape
+        dev = S.device
+        fv = _out(out, "fv", (B, self.rows, T), torch.float32, dev)
+        nP, patches = 0, None
+        if W is not None:
+            nP = self.num_patches(T, W, shift)
+            patches = _out(out, "patches", (B * nP, W, self.rows), torch.float32, dev)
+        keys = (out or {}).get("maxkeys")
+        if keys is None:
+            keys = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+        elif not (keys.is_cuda and keys.dtype == torch.int32 and keys.numel() >= B and keys.is_contiguous()):
+            raise ValueError("out['maxkeys'] must be a contiguous int32 device tensor with at least B = %d entries" % B)
+        got = _lib.check(self.lib.smh_plain_features_f32(self._h, _ptr(S), B, T, W or 0, shift or 0, _ptr(fv),
+                                                         _ptr(patches) if nP else None, _ptr(keys), _stream()),
+                         "smh_plain_features_f32")
+        assert got == nP
+        return {"fv": fv, "patches": patches, "n_patches": nP, "maxkeys": keys}
+
     # ---- fused fast path ----
     def run(self, audio, W=None, shift=None, taps=False, out=None):
         """audio (B, n_samples) -> dict(fv=(B, 2*rows, T)[, patches=(B*nP, W, 2*rows)][, S, harm, perc]).
-        `out` may carry preallocated 'fv' / 'patches' tensors (steady-state loops allocate nothing)."""
+        `out` may carry preallocated 'fv' / 'patches' tensors (steady-state loops allocate nothing).
+        A plain configuration (hpss=False) gives fv=(B, rows, T) and patches=(B*nP, W, rows); its only tap is S."""
+        if not self.cfg.hpss:
+            return self._run_plain(audio, W, shift, taps, out)
         audio = _f32c(audio, "audio")
         B, N = audio.shape
         T = self.num_frames(N)
@@ -309,6 +365,38 @@ class Frontend:
             res["patches"] = patches
         if taps:
             res.update(S=S, harm=harm, perc=perc)
+        return res
+
+    def _run_plain(self, audio, W, shift, taps, out):
+        audio = _f32c(audio, "audio")
+        B, N = audio.shape
+        T = self.num_frames(N)
+        if T < 1:
+            raise ValueError("clip of %d samples is shorter than n_fft=%d" % (N, self.cfg.n_fft))
+        dev = audio.device
+        out = {} if out is None else out
+        fv = out.get("fv")
+        if fv is None or fv.shape != (B, self.rows, T):
+            fv = torch.empty((B, self.rows, T), dtype=torch.float32, device=dev)
+        patches, nP = None, 0
+        if W is not None:
+            nP = self.num_patches(T, W, shift)
+            patches = out.get("patches")
+            if patches is None or patches.shape != (B * nP, W, self.rows):
+                patches = torch.empty((B * nP, W, self.rows), dtype=torch.float32, device=dev)
+        need = self.lib.smh_plain_frontend_workspace_bytes(self._h, B, N)
+        if self._work is None or self._work.numel() < need or self._work.device != dev:
+            self._work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        S = torch.empty((B, self.K, T), dtype=torch.float32, device=dev) if taps else None
+        got = _lib.check(self.lib.smh_plain_frontend_f32(
+            self._h, _ptr(audio), B, N, W or 0, shift or 0, _ptr(fv), _ptr(patches) if nP else None,
+            _ptr(self._work), self._work.numel(), _ptr(S), _stream()), "smh_plain_frontend_f32")
+        assert got == nP, (got, nP)
+        res = {"fv": fv, "n_patches": nP}
+        if W is not None:
+            res["patches"] = patches
+        if taps:
+            res["S"] = S
         return res
 
     # ---- ragged batches ----
@@ -347,16 +435,19 @@ class Frontend:
         fv_off, p_off = (C.c_longlong * (B + 1))(), (C.c_longlong * (B + 1))()
         hT, hnP = (C.c_int * B)(), (C.c_int * B)()
         work = C.c_size_t()
-        _lib.check(self.lib.smh_frontend_ragged_sizes(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP,
-                                                      C.byref(work)), "smh_frontend_ragged_sizes")
-        F = 2 * self.rows
+        # a plain configuration (hpss=False) takes the plain pair of entries: same contract, (rows, T_b) and (nP_b, W, rows) per clip
+        sizes, ragged = ((self.lib.smh_frontend_ragged_sizes, self.lib.smh_frontend_ragged_f32) if self.cfg.hpss else
+                         (self.lib.smh_plain_frontend_ragged_sizes, self.lib.smh_plain_frontend_ragged_f32))
+        _lib.check(sizes(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP, C.byref(work)),
+                   "smh_frontend_ragged_sizes")
+        F = (2 if self.cfg.hpss else 1) * self.rows
         fv = torch.empty(max(int(fv_off[B]), 1), dtype=torch.float32, device=dev)
         patches = torch.empty((max(int(p_off[B]), 1), W or 1, F), dtype=torch.float32, device=dev) if W else None
         if self._work is None or self._work.numel() < work.value or self._work.device != dev:
             self._work = torch.empty(max(work.value, 1), dtype=torch.uint8, device=dev)
-        _lib.check(self.lib.smh_frontend_ragged_f32(self._h, _ptr(audio), h_off, h_len, B, W or 0, shift or 0, _ptr(fv),
-                                                    _ptr(patches) if (W and int(p_off[B]) > 0) else None, _ptr(self._work),
-                                                    self._work.numel(), _stream()), "smh_frontend_ragged_f32")
+        _lib.check(ragged(self._h, _ptr(audio), h_off, h_len, B, W or 0, shift or 0, _ptr(fv),
+                          _ptr(patches) if (W and int(p_off[B]) > 0) else None, _ptr(self._work), self._work.numel(), _stream()),
+                   "smh_frontend_ragged_f32")
         res = {"fv": [fv[int(fv_off[b]):int(fv_off[b + 1])].view(F, int(hT[b])) for b in range(B)],
                "T": [int(hT[b]) for b in range(B)], "n_patches": [int(hnP[b]) for b in range(B)]}
         if W:

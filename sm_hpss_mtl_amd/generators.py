@@ -176,7 +176,7 @@ def _cached_featuregram(path, fresh=None):
 def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
     """specs: list of (classname, sp_path, mu_path, target_dB).  Loads / conditions / mixes the signals (the 'next' row in
     front of the path: lib.preprocessing.load_and_preprocess_signal, mix_signals), then ONE ragged pass of the front end.
-    Returns a list of (nP_i, W, 2F) float32 device tensors."""
+    Returns a list of (nP_i, W, 2F) float32 device tensors ((nP_i, W, F) for the feature names without an H / P pair)."""
     import torch
     from . import frontend as _fe
     from .lib import preprocessing as pp

@@ -1,7 +1,7 @@
 """Counterpart of lib/preprocessing.py for the hot path -- same function names, argument meaning and
 return types as the reference, computed by the HIP library.
 
-  get_featuregram      (preprocessing.py:355-457)  '*HarmPerc*' branches 404-444
+  get_featuregram      (preprocessing.py:355-457)  '*HarmPerc*' branches 404-444, Spec / LogSpec / MelSpec / LogMelSpec 378-402
   get_feature_patches  (preprocessing.py:137-292)
   normalize_signal     (preprocessing.py:114-132)
   mix_signals          (preprocessing.py:297-325)
@@ -155,13 +155,14 @@ def load_and_preprocess_signal(fName, Tw, Ts):
 # ---- featuregram ------------------------------------------------------------------------------------------
 def featuregram_batch(PARAMS, Xin, n_fft, n_mels, featName, W=None, shift=None, taps=False, fs=16000):
     """Device fast path: Xin float32 CUDA tensor (B, n_samples) of equal-length clips ->
-    dict(fv=(B, 2*rows, T)[, patches=(B*nP, W, 2*rows) time-major, standardised])."""
+    dict(fv=(B, 2*rows, T)[, patches=(B*nP, W, 2*rows) time-major, standardised]); for Spec / LogSpec / MelSpec / LogMelSpec
+    fv=(B, rows, T) and patches=(B*nP, W, rows)."""
     cfg = _fe.FrontendConfig.from_params(PARAMS, n_fft, n_mels, featName, fs)
     return _frontend_for(cfg).run(Xin, W=W, shift=shift, taps=taps)
 
 
 def featuregram_from_signal(PARAMS, Xin, n_fft, n_mels, featName, fs=16000):
-    """One clip: the arithmetic of get_featuregram from `Xin` on (preprocessing.py:404-444)."""
+    """One clip: the arithmetic of get_featuregram from `Xin` on (preprocessing.py:378-444)."""
     x = torch.from_numpy(np.ascontiguousarray(Xin, dtype=np.float32)).cuda()[None]
     return featuregram_batch(PARAMS, x, n_fft, n_mels, featName, fs=fs)["fv"][0].cpu().numpy()
 
@@ -172,8 +173,9 @@ def get_featuregram(PARAMS, classname, feature_opDir, fName_path_sp, fName_path_
     cache = feature_cache_path(feature_opDir, classname, fName_path_sp, fName_path_mu, target_dB)
     if os.path.exists(cache):
         return np.load(cache, allow_pickle=False)
-    if featName not in _fe.FEATS and featName not in _fe.HALF_FEATS:
-        raise ValueError("featName %r: only the HPSS features %s are on the built path" % (featName, sorted(_fe.FEATS) + sorted(_fe.HALF_FEATS)))
+    if featName not in _fe.FEATS and featName not in _fe.HALF_FEATS and featName not in _fe.PLAIN_FEATS:
+        raise ValueError("featName %r is not one of get_featuregram's feature names %s"
+                         % (featName, sorted(_fe.FEATS) + sorted(_fe.HALF_FEATS) + sorted(_fe.PLAIN_FEATS)))
     if classname == 'speech_music':
         Xin_sp, fs = load_and_preprocess_signal(fName_path_sp, PARAMS['Tw'], PARAMS['Ts'])
         Xin_mu, fs = load_and_preprocess_signal(fName_path_mu, PARAMS['Tw'], PARAMS['Ts'])

@@ -44,6 +44,11 @@ class HotPath:
         feature kernel applies both models' first layers (`w0_ptr()`) and forward_from_x0_halves starts from the per-half partials;
         fuse_l0=False -- the two contiguous halves of the patches go to forward_device.  `logits` is then the blended '3C'
         (B * nP, n_classes)."""
+        if not fe.cfg.hpss:
+            # Spec / LogSpec / MelSpec / LogMelSpec: no medians and no layer-0 fusion to schedule; audio -> logits on that path is
+            # fe.run(...)["patches"] -> model.forward_device
+            raise ValueError("HotPath drives the harmonic-percussive front end; a plain Frontend (hpss=False) goes "
+                             "fe.run(audio, W, shift)['patches'] -> model.forward_device")
         self.fe, self.model, self.lib, self._h = fe, model, fe.lib, fe._h
         self.B, self.n_samples, self.W = int(batch), int(n_samples), int(patch)
         self.shift = int(patch if shift is None else shift)
