@@ -307,6 +307,19 @@ int smh_model_create(const smh_model_cfg *cfg, smh_model **out);
  * Only the two-input entry points below serve it: every single-input forward, smh_train_step_f32, the bf16 forwards, trainer
  * dtype 1 and block_variant 1 refuse a fusion model. */
 #define SMH_HEADS_FUSION 2
+/* SMH_HEADS_SINGLE: the single-task Lemaire TCN baseline, get_Lemaire_model (lib/baseline_architectures.py:196-300; 5-class twin:
+ * 5_class_classification.py:54-145): B3_MTL's trunk, then Flatten -> Dense(n_classes) -> softmax.  No heads (n_heads = 0), n_classes
+ * 2, 3 or 5, out_dim = n_classes: a row of d_out is the softmax alone.  Canonical order: the trunk exactly as for SMH_HEADS_MTL, then
+ * 'dense' kernel (patch_size * 32, n_classes), bias.  Served by smh_model_forward_f32 (with the d_trunk tap),
+ * smh_model_forward_dense_f32, smh_model_eval_losses_f32 (d_sums = [total | loss | accuracy]) and the f32 trainer:
+ *   n_classes == 2: Keras' binary_crossentropy on the two softmax outputs (clipped to [1e-7, 1 - 1e-7], + 1e-7 inside the logs, mean
+ *     over the two outputs, then over the batch) and BINARY accuracy, the mean over all N x 2 outputs of (p > 0.5) == y;
+ *   n_classes 3 / 5: categorical cross-entropy and categorical accuracy.
+ * smh_train_step_f32: d_y (N, n_classes) one-hot, d_drop_heads ignored, h_loss_weights one float or NULL, d_losses four floats
+ * [loss, weighted loss, accuracy, 0].  The trainer's bucket is the gradient alone (no BatchNorm statistics): smh_model_num_params
+ * floats.  smh_model_forward_x0_* (the plain front end writes no layer-0 partials), the bf16 forwards, trainer dtype 1, block_variant
+ * 1, the fusion entries and smh_late_fusion_create refuse a single-task model. */
+#define SMH_HEADS_SINGLE 3
 int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_model **out);
 void smh_model_destroy(smh_model *m);
 /* number of float32 parameters in canonical (Keras-layout) order, see DESIGN.md "weight order" */

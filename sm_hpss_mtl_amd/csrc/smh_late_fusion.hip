@@ -88,6 +88,8 @@ extern "C" int smh_late_fusion_create(smh_model *mH, smh_model *mP, smh_late_fus
     for (const smh_model *m : {mH, mP}) {
         SMH_REQUIRE(m->heads != SMH_HEADS_FUSION, "smh_late_fusion_create: an intermediate-fusion model has two inputs; the ensemble takes "
                     "two single-input B3_MTL or cascaded models");
+        SMH_REQUIRE(m->heads != SMH_HEADS_SINGLE, "smh_late_fusion_create: a single-task model has no H / P counterpart to blend with; the "
+                    "ensemble takes two B3_MTL or two cascaded models");
         SMH_REQUIRE(m->cfg.block_variant == 0, "smh_late_fusion_create: built for the keras-tcn 2.3.x block (block_variant 0) only");
     }
     SMH_REQUIRE(mH->heads == mP->heads, "smh_late_fusion_create: the two models differ in head kind (%d and %d): both B3_MTL or both cascaded",

@@ -38,6 +38,7 @@ struct TcnArgs {
     int head_odim[kMaxHeads];
     int head_sigmoid[kMaxHeads];
     int cascade;  // SMH_HEADS_CASCADED: heads S and M read BN18(concat[their Dropout(16), R's output]) (smh_tcn_heads.h)
+    int single;   // SMH_HEADS_SINGLE: the tail is single_tail (smh_tcn_heads.h) -- one softmax per patch, no heads
     int trunk_only;  // 1: the forward ends at the trunk (its tap / saved activations); no Dense-on-trunk, no heads (the fusion model's trunks)
     int x0_one;   // from_x0 with ONE partial per frame and channel: X (advanced by the caller to its half) already holds the complete
                   // layer-0 product of this trunk and nothing but the bias is added.  The two addressing forms of the two-half mode:
@@ -87,6 +88,11 @@ int launch_heads_train(const HeadsArgs &a, const float *pre, const float *y, con
 // S and M; bnstat also receives the BN18 batch statistics of S and M at kMaxHeads * 32 + h * 2 * kCat (means, then variances).
 int launch_cascade_heads_train(const HeadsArgs &a, const float *pre, const float *y, const float *hp, const float *drop,
                                float *dpre, float *dxh, float *dr, float *grad, float *bnstat, float *losses, hipStream_t st);
+// The head of the single-task baseline (smh_train_single.hip; a.n_heads = 0): softmax, the loss (binary cross-entropy over the two
+// outputs for n_classes == 2, else categorical cross-entropy), the accuracy, d loss / d logits (-> dpre) and the Dense bias gradient.
+// losses: [loss, lw[0] * loss, accuracy, 0]
+int launch_single_head_train(const HeadsArgs &a, const float *pre, const float *y, float *dpre, float *grad, float *losses,
+                             hipStream_t st);
 // floats of the BatchNorm batch-statistics part of the trainer's bucket
 constexpr int kBnStatFloats = kMaxHeads * 32;
 constexpr int kCatStatFloats = 2 * 2 * kCat;
@@ -97,7 +103,7 @@ struct smh_model {
     smh_model_cfg cfg;
     int n_blocks, n_heads, NH, n_mt, D, out_dim, FQ;
     int head_odim[smh_tcn::kMaxHeads], head_sigmoid[smh_tcn::kMaxHeads];
-    int heads = 0;                      // SMH_HEADS_MTL / SMH_HEADS_CASCADED / SMH_HEADS_FUSION
+    int heads = 0;                      // SMH_HEADS_MTL / SMH_HEADS_CASCADED / SMH_HEADS_FUSION / SMH_HEADS_SINGLE
     // SMH_HEADS_FUSION: the two trunks as models of their own (B3_MTL objects whose Dense / heads are never run).  Their master
     // weights are copies of the fusion model's trunk tensors, refreshed by repack(); their operand buffers are what the trunk
     // forwards read.  The fusion model itself packs only the Dense layers on the fused features (D = 2 W 32) and the heads.

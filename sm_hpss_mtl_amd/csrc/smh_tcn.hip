@@ -1144,6 +1144,7 @@ Offsets offsets(const smh_model *m) {
     Offsets o;
     const size_t F = m->cfg.n_feat, D = m->D, ncls = m->cfg.n_classes;
     size_t p = 0;
+    for (int h = 0; h < kMaxHeads; ++h) o.head[h] = 0;
     o.w0_k = p, p += F * C;
     o.w0_b = p, p += C;
     o.blk0 = p, o.blk_stride = 3 * C * C + C + C * C + C;
@@ -1197,6 +1198,7 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     a.out_dim = m->out_dim;
     for (int i = 0; i < kMaxHeads; ++i) a.head_odim[i] = m->head_odim[i], a.head_sigmoid[i] = m->head_sigmoid[i];
     a.cascade = m->heads == SMH_HEADS_CASCADED;
+    a.single = m->heads == SMH_HEADS_SINGLE;
     // patches per workgroup: up to 272 rows (17 column tiles) of LDS-resident activations, at most one
     // MFMA tile of patches, and never fewer workgroups than CUs when the batch allows it
     int gmax = 272 / T;
@@ -1357,14 +1359,20 @@ extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
 
 extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_model **out) {
     SMH_REQUIRE(cfg && out, "smh_model_create: null argument");
-    SMH_REQUIRE(heads == SMH_HEADS_MTL || heads == SMH_HEADS_CASCADED || heads == SMH_HEADS_FUSION,
-                "smh_model_create_heads: heads must be %d (MTL), %d (cascaded) or %d (intermediate fusion), got %d", SMH_HEADS_MTL,
-                SMH_HEADS_CASCADED, SMH_HEADS_FUSION, heads);
+    SMH_REQUIRE(heads == SMH_HEADS_MTL || heads == SMH_HEADS_CASCADED || heads == SMH_HEADS_FUSION || heads == SMH_HEADS_SINGLE,
+                "smh_model_create_heads: heads must be %d (MTL), %d (cascaded), %d (intermediate fusion) or %d (single task), got %d",
+                SMH_HEADS_MTL, SMH_HEADS_CASCADED, SMH_HEADS_FUSION, SMH_HEADS_SINGLE, heads);
+    SMH_REQUIRE(heads != SMH_HEADS_SINGLE || cfg->block_variant == 0,
+                "smh_model_create_heads: the single-task model is built for block_variant 0 (keras-tcn 2.3.x) only");
     SMH_REQUIRE(heads != SMH_HEADS_FUSION || cfg->block_variant == 0,
                 "smh_model_create_heads: the intermediate-fusion model is built for block_variant 0 (keras-tcn 2.3.x) only");
     SMH_REQUIRE(cfg->nb_filters == C, "B3_MTL kernel is tiled for nb_filters=32 (got %d)", cfg->nb_filters);
     SMH_REQUIRE(cfg->kernel_size == 3, "B3_MTL kernel supports kernel_size=3 (got %d)", cfg->kernel_size);
-    SMH_REQUIRE(cfg->n_classes == 3 || cfg->n_classes == 5, "n_classes must be 3 or 5 (got %d)", cfg->n_classes);
+    if (heads == SMH_HEADS_SINGLE)  // lib/baseline_architectures.py:196-300 (2 or 3 classes), 5_class_classification.py:54-145
+        SMH_REQUIRE(cfg->n_classes == 2 || cfg->n_classes == 3 || cfg->n_classes == 5,
+                    "smh_model_create_heads: a single-task model has n_classes 2, 3 or 5 (got %d)", cfg->n_classes);
+    else
+        SMH_REQUIRE(cfg->n_classes == 3 || cfg->n_classes == 5, "n_classes must be 3 or 5 (got %d)", cfg->n_classes);
     SMH_REQUIRE(cfg->n_feat >= 1 && cfg->patch_size >= 1 && cfg->patch_size <= 512, "bad n_feat/patch_size");
     SMH_REQUIRE(cfg->nb_stacks >= 1 && cfg->n_dilations >= 1 && cfg->n_dilations <= 16, "bad stacks/dilations");
     SMH_REQUIRE(smh_device_count() > 0, "no HIP device visible: libsmh has no CPU path");
@@ -1372,8 +1380,10 @@ extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_m
     m->cfg = *cfg;
     m->n_blocks = cfg->nb_stacks * cfg->n_dilations;
     m->heads = heads;
-    for (int i = 0; i < kMaxHeads; ++i) m->head_cat[i] = 0;
-    if (heads == SMH_HEADS_CASCADED) {  // proposed_architectures.py:175-323: S, M, R(2) whatever n_classes is
+    for (int i = 0; i < kMaxHeads; ++i) m->head_cat[i] = 0, m->head_odim[i] = 0, m->head_sigmoid[i] = 0;
+    if (heads == SMH_HEADS_SINGLE) {  // Flatten -> Dense(n_classes) -> softmax: the '3C' slot of the canonical order is Keras' 'dense'
+        m->n_heads = 0;
+    } else if (heads == SMH_HEADS_CASCADED) {  // proposed_architectures.py:175-323: S, M, R(2) whatever n_classes is
         m->n_heads = 3;
         const int od[3] = {1, 1, 2}, sg[3] = {1, 1, 0};
         for (int i = 0; i < 3; ++i) m->head_odim[i] = od[i], m->head_sigmoid[i] = sg[i];
@@ -1587,6 +1597,7 @@ extern "C" int smh_model_forward_dense_f32(const smh_model *m, const float *d_fv
 namespace {
 struct EvalArgs {
     int N, n_heads, n_classes, out_dim;
+    int bce2;  // the two-class single-task model: binary cross-entropy on the two softmax outputs, binary accuracy
     int head_odim[kMaxHeads], head_sigmoid[kMaxHeads];
     double weight, l2, lw[kMaxHeads + 1];
 };
@@ -1613,6 +1624,16 @@ __global__ void __launch_bounds__(256) eval_losses_kernel(EvalArgs a, const floa
                         acc -= tv * log(oc + eps) + (1.0 - tv) * log(1.0 - oc + eps);
                     } else {
                         acc += (ov - tv) * (ov - tv);
+                    }
+                }
+            } else if (a.bce2) {  // Keras' binary_crossentropy / binary accuracy over the N x 2 outputs
+                for (int c = 0; c < od; ++c) {
+                    const double ov = (double)o[c], tv = (double)t[c];
+                    if (slot == a.n_heads) {
+                        const double oc = fmin(fmax(ov, eps), 1.0 - eps);
+                        acc -= (tv * log(oc + eps) + (1.0 - tv) * log(1.0 - oc + eps)) / od;
+                    } else {
+                        acc += ((ov > 0.5) == (tv > 0.5) ? 1.0 : 0.0) / od;
                     }
                 }
             } else if (slot == a.n_heads) {
@@ -1656,6 +1677,7 @@ extern "C" int smh_model_eval_losses_f32(const smh_model *m, const float *d_out,
     SMH_REQUIRE(N >= 1, "smh_model_eval_losses_f32: N=%d", N);
     EvalArgs a;
     a.N = N, a.n_heads = m->n_heads, a.n_classes = m->cfg.n_classes, a.out_dim = m->out_dim, a.weight = weight, a.l2 = l2_penalty;
+    a.bce2 = m->heads == SMH_HEADS_SINGLE && m->cfg.n_classes == 2;
     for (int i = 0; i < kMaxHeads; ++i) a.head_odim[i] = m->head_odim[i], a.head_sigmoid[i] = m->head_sigmoid[i];
     for (int i = 0; i <= kMaxHeads; ++i) a.lw[i] = i <= m->n_heads ? h_loss_weights[i] : 0.0;
     hipLaunchKernelGGL(eval_losses_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, d_out, d_targets, d_sums);
@@ -1668,6 +1690,8 @@ extern "C" int smh_model_forward_x0_f32(const smh_model *m, const float *d_x0p, 
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_model_forward_x0_f32: the layer-0 fusion exists for block_variant 0 only");
     SMH_REQUIRE(m->heads != SMH_HEADS_FUSION, "smh_model_forward_x0_f32: an intermediate-fusion model has two inputs and no fused-x0 "
                 "path; use smh_fusion_forward_f32");
+    SMH_REQUIRE(m->heads != SMH_HEADS_SINGLE, "smh_model_forward_x0_f32: a single-task model reads one plain featuregram, and the plain "
+                "front end produces no layer-0 partials; use smh_model_forward_f32");
     SMH_REQUIRE(N >= 0, "smh_model_forward_x0_f32: N=%d", N);
     if (N == 0) return SMH_OK;
     smh_tcn::ForwardOpts fo;

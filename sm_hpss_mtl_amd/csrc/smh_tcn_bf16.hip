@@ -917,8 +917,8 @@ struct SplitPlan {
 // the refusals of forward_bf16 that depend on the model alone
 static int model_bf16_ok(const smh_model *m) {
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_model_forward_bf16: built for block_variant 0 only");
-    SMH_REQUIRE(m->heads == SMH_HEADS_MTL, "smh_model_forward_bf16: the bf16 forward has the B3_MTL heads only, not the cascaded "
-                "or intermediate-fusion heads of this model (use smh_model_forward_f32 / smh_fusion_forward_f32)");
+    SMH_REQUIRE(m->heads == SMH_HEADS_MTL, "smh_model_forward_bf16: the bf16 forward has the B3_MTL heads only, not the cascaded, "
+                "intermediate-fusion or single-task tail of this model (use smh_model_forward_f32 / smh_fusion_forward_f32)");
     SMH_REQUIRE(m->cfg.n_feat <= 256, "smh_model_forward_bf16: n_feat=%d exceeds the 256 features of the bf16 layer-0 tiling",
                 m->cfg.n_feat);
     return SMH_OK;

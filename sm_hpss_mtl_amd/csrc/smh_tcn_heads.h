@@ -105,6 +105,35 @@ __device__ __forceinline__ void heads_tail(const TcnArgs &a, const float *pre, c
     }
 }
 
+// Inference tail of the single-task baseline (SMH_HEADS_SINGLE; get_Lemaire_model, lib/baseline_architectures.py:196-300): Flatten ->
+// Dense(n_classes) -> softmax and nothing else, so the Dense-on-trunk outputs ARE the logits.  One thread per patch (tid < g_here)
+// reads its NH = n_classes <= 5 sums from `pre` (row stride kPS, without bias), adds the biases `bh` and writes the out_dim =
+// n_classes probabilities of row n0 + tid.  What heads_tail asks of its caller shrinks accordingly: no (patch, head) threads, so no
+// g_here * n_heads <= 128 bound -- g_here <= kMaxG = 16 threads are needed and every forward launches at least 256; with NH <= 64
+// a lane owns one output (OPL = 1, ld = 64) and the partial sums are [kDenseParts][4][64] floats in front of pre[kMaxG][kPS],
+// inside the 8 * 4 * 128 + kMaxG * kPS floats fill_args reserves.  The kDenseParts ranges and their summation order are
+// dense_and_heads' own: a patch's bits depend neither on N, nor on the patches per workgroup, nor on the wave count.
+__device__ __forceinline__ void single_tail(const TcnArgs &a, const float *pre, const float *bh, float *__restrict__ out, int n0,
+                                            int g_here) {
+    const int p = threadIdx.x;
+    if (p >= g_here) return;
+    constexpr int kMaxC = 5;
+    float z[kMaxC], mx = -INFINITY, den = 0.f;
+#pragma unroll
+    for (int c = 0; c < kMaxC; ++c) {
+        z[c] = c < a.n_classes ? pre[p * kPS + c] + bh[c] : -INFINITY;
+        mx = fmaxf(mx, z[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < kMaxC; ++c) {
+        z[c] = c < a.n_classes ? expf(z[c] - mx) : 0.f;
+        den += z[c];
+    }
+#pragma unroll
+    for (int c = 0; c < kMaxC; ++c)
+        if (c < a.n_classes) out[(size_t)(n0 + p) * a.out_dim + c] = z[c] / den;
+}
+
 template <bool TRAIN>
 __device__ __forceinline__ void dense_and_heads(const TcnArgs &a, const float *xin, float *xout, const float *__restrict__ WhA,
                                                 const float *__restrict__ hp, float *__restrict__ out, const TrainIO &tio,
@@ -195,7 +224,8 @@ __device__ __forceinline__ void dense_and_heads(const TcnArgs &a, const float *x
         }
         return;
     }
-    heads_tail(a, pre, bh, hp, out, n0, g_here);
+    if (a.single) single_tail(a, pre, bh, out, n0, g_here);  // (uniform)
+    else heads_tail(a, pre, bh, hp, out, n0, g_here);
 }
 
 }  // namespace smh_tcn

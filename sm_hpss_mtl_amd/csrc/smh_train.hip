@@ -1237,6 +1237,7 @@ extern "C" int smh_trainer_create(smh_model *m, int max_batch, smh_trainer **out
     t->m = m, t->max_batch = max_batch;
     const bool fusion = m->heads == SMH_HEADS_FUSION;
     t->bn_floats = kBnStatFloats + (m->heads == SMH_HEADS_CASCADED ? kCatStatFloats : 0) + (fusion ? 2 * (size_t)m->D : 0);
+    if (m->heads == SMH_HEADS_SINGLE) t->bn_floats = 0;  // no BatchNorm anywhere: the bucket is the gradient alone
     const Offsets off = offsets(m);
     std::vector<Segment> segs;
     int group = 0;
@@ -1364,8 +1365,8 @@ extern "C" int smh_model_check_train_dtype(const smh_model *m, int dtype) {
     SMH_REQUIRE(m, "smh_model_check_train_dtype: null model");
     SMH_REQUIRE(dtype == 0 || dtype == 1, "smh_trainer_set_dtype: dtype must be 0 (f32) or 1 (split bf16 operands)");
     SMH_REQUIRE(dtype == 0 || m->heads == SMH_HEADS_MTL,
-                "smh_trainer_set_dtype: the split-bf16 training step has the B3_MTL heads only; a cascaded or intermediate-fusion model "
-                "trains in f32 (dtype 0)");
+                "smh_trainer_set_dtype: the split-bf16 training step has the B3_MTL heads only; a cascaded, intermediate-fusion or "
+                "single-task model trains in f32 (dtype 0)");
     // a model the split-bf16 forward refuses would otherwise fail only at its first training step
     return dtype == 0 ? SMH_OK : forward_bf16_supported(m);
 }
@@ -1502,7 +1503,9 @@ static int train_step(smh_trainer *t, const float *const *x, int nx, const float
     if (rc) return rc;
     const Offsets off = offsets(m);
     const HeadsArgs ha = heads_args(m, off, N, h_loss_weights);
-    if (m->heads == SMH_HEADS_CASCADED)
+    if (m->heads == SMH_HEADS_SINGLE)  // no heads: heads_train_kernel's grid of n_heads + 1 workgroups has nothing to run here
+        rc = launch_single_head_train(ha, t->d_pre, d_y, t->d_dpre, t->d_grad, d_losses, st);
+    else if (m->heads == SMH_HEADS_CASCADED)
         rc = launch_cascade_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_dr, t->d_grad,
                                         t->d_bnstat, d_losses, st);
     else
@@ -1510,10 +1513,12 @@ static int train_step(smh_trainer *t, const float *const *x, int nx, const float
                                 reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
     if (rc) return rc;
     BwdArgs ba = bwd_args(t, off, N, sw.split3, fusion ? 0 : sw.stamps);
-    hipLaunchKernelGGL(l2_penalty_kernel, dim3(m->n_heads * kL2Chunks), dim3(256), 0, st, ba, m->d_flat, d_losses + m->n_heads + 3,
-                       t->d_l2part, reinterpret_cast<unsigned *>(t->d_l2part + kMaxHeads * kL2Chunks));
-    rc = smh::launch_status("l2_penalty_kernel");
-    if (rc) return rc;
+    if (m->n_heads > 0) {  // (a model without heads has no regularised kernel: its head kernel wrote the zero penalty itself)
+        hipLaunchKernelGGL(l2_penalty_kernel, dim3(m->n_heads * kL2Chunks), dim3(256), 0, st, ba, m->d_flat, d_losses + m->n_heads + 3,
+                           t->d_l2part, reinterpret_cast<unsigned *>(t->d_l2part + kMaxHeads * kL2Chunks));
+        rc = smh::launch_status("l2_penalty_kernel");
+        if (rc) return rc;
+    }
     if (fusion) {
         rc = launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats, t->d_dpre,
                                  t->d_grad, 1, st);

@@ -18,12 +18,15 @@ from . import _lib
 from .persistence import ModelSurfaceMixin, load_weights_file, save_weights_file
 
 HEADS_MTL, HEADS_CASCADED, HEADS_FUSION = 0, 1, 2  # include/smh.h: SMH_HEADS_MTL / SMH_HEADS_CASCADED / SMH_HEADS_FUSION
+HEADS_SINGLE = 3  # SMH_HEADS_SINGLE: the single-task baseline, Flatten -> Dense(n_classes) -> softmax, no auxiliary heads
 
 
 def head_spec(n_classes: int, heads: int = HEADS_MTL):
     """(name, out_dim, activation) of the auxiliary heads in Keras output order
     (proposed_architectures.py:25-80,154; 5_class_classification.py:150-215,286).  The cascaded model
     (cascade_MTL_modifications, :175-234) has S, M, R[2] whatever n_classes is."""
+    if heads == HEADS_SINGLE:
+        return []
     if n_classes == 5 and heads != HEADS_CASCADED:  # (the intermediate-fusion model has MTL_modifications' heads)
         return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("N", 1, "sigmoid"), ("R", 3, "linear")]
     return [("S", 1, "sigmoid"), ("M", 1, "sigmoid"), ("R", 2, "linear")]

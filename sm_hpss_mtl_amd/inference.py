@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .frontend import Frontend, FrontendConfig, _ptr, _stream
+from .host import HEADS_SINGLE
 
 _fe = None
 
@@ -94,10 +95,12 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
     """fv (2R, nFrames) HarmPerc featuregram of one file -> 1-D float32 numpy track of the chosen head's
     probability, one value per patch, batches concatenated (DAFx12...:612-676).  model: B3MTL, cascaded, or FusionMTL (per-branch
     n_feat = R; the file-wise predict of Intermediate_Fusion_Results.py:441-590).  A late_fusion.LateFusion ensemble (per-model n_feat
-    = R) has the one output '3C' and returns its blended (nP, n_classes) track instead of a 1-D one."""
+    = R) has the one output '3C' and returns its blended (nP, n_classes) track instead of a 1-D one.  So does a model.SingleTaskTCN
+    (output 'dense'), whose fv is ONE (n_feat, nFrames) featuregram such as LogMelSpec: no halves, the rows are standardised once."""
     fe = _frontend()
     d = _dev(fv)
-    if d.dim() != 2 or d.shape[0] % 2:
+    single = getattr(model, "HEADS", 0) == HEADS_SINGLE  # one plain featuregram in, one output
+    if d.dim() != 2 or (d.shape[0] % 2 and not single):
         raise ValueError("fv must be (2R, nFrames), got %s" % (tuple(d.shape),))
     names = model.output_names
     if output not in names:
@@ -108,12 +111,14 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
             break
         col += o.shape[1]
     # the ensemble's one output is the whole blended row; every other model gives one column of its output
-    late = getattr(model, "LATE_FUSION", False)
+    late = getattr(model, "LATE_FUSION", False) or single
     sel = slice(None) if late else col
     R = d.shape[0] // 2
     # the intermediate-fusion model reads the two halves as two inputs; its n_feat is the per-branch width
     fusion = hasattr(model, "forward_from_x0_halves")
     rows_ok = d.shape[0] == (2 if fusion else 1) * getattr(model, "n_feat", d.shape[0])
+    if single and not rows_ok:
+        raise ValueError("fv must be (%d, nFrames) for this model, got %s" % (model.n_feat, tuple(d.shape)))
     # batches longer than a patch skip the (nP, W, 2R) patch tensor (648 MB per 10 000 frames at W = 68, hop 1) when the model has
     # the entry for it; SMH_DENSE_PATCHES=1 keeps the patch path (A/B, tests)
     dense = (hasattr(model, "forward_dense") and getattr(model, "block_variant", 1) == 0 and d.shape[0] % 8 == 0 and rows_ok
@@ -130,6 +135,11 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
             o = model.forward_dense(fe.standardize_rows(chunk), W_shift)
             if o.shape[0]:
                 preds.append(o[:, sel])
+            continue
+        if single:  # one input: the whole batch standardised row by row, hop-W_shift patches, time-major
+            x = fe.extract_patches(fe.standardize_rows(chunk)[None], W, W_shift, time_major=True)
+            if x.shape[0]:
+                preds.append(model.forward_device(x))
             continue
         # get_feature_patches on the batch (:647): tile if short, standardise each half over the batch, hop-W_shift
         # patches; written time-major = the transposed TCN input of :660

@@ -12,6 +12,7 @@ Weights are kept on the host as float32 numpy arrays in CANONICAL order (Keras a
    moving_variance and an out kernel of shape (18, 1))
   (FusionMTL: two trunks 'tcn_H/...' and 'tcn_P/...' in place of 'tcn/...', then the fused BatchNorm 'fusion_bn' gamma, beta,
    moving_mean, moving_variance (2*T*32 each); '3C' and the heads read the 2*T*32 fused features)
+  (SingleTaskTCN: the trunk, then 'dense' kernel (T*32, n_classes), bias -- Keras' name for the baseline's only Dense layer)
 and uploaded (re-packed into MFMA operand order by libsmh) whenever they change: the weight store, the Keras weight surface,
 `predict` and the call helpers are host.HostModel's, shared with cnn_models.CnnMTL; the training surface is
 training.TcnTrainingMixin's.
@@ -26,8 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .host import HEADS_CASCADED, HEADS_FUSION, HEADS_MTL, HostModel, f32_cuda, head_spec, ptr, to_f32_cuda, workspace
-from .training import TcnTrainingMixin
+from .host import HEADS_CASCADED, HEADS_FUSION, HEADS_MTL, HEADS_SINGLE, HostModel, f32_cuda, head_spec, ptr, to_f32_cuda, workspace
+from .training import TRAIN_ALL, TcnTrainingMixin
 
 CAT = 18  # cascaded heads: width of concat[Dropout(16) of S or M, R's two outputs]
 
@@ -38,7 +39,8 @@ def weight_spec(n_feat, patch_size, n_classes, nb_filters=32, kernel_size=3, nb_
     block_variant 0: the keras-tcn 2.3.x block; 1: the two-convolution block of keras-tcn >= 2.8 (include/smh.h).
     heads HEADS_CASCADED: S and M carry the concatenation BatchNorm 'cat_bn' (18) and an out kernel (18, 1).
     heads HEADS_FUSION: two trunks 'tcn_H' / 'tcn_P' (n_feat = the per-branch width), the fused BatchNorm 'fusion_bn' over
-    D = 2 * patch_size * nb_filters features, then '3C' and the MTL heads on D inputs."""
+    D = 2 * patch_size * nb_filters features, then '3C' and the MTL heads on D inputs.
+    heads HEADS_SINGLE: the trunk, then 'dense' (D, n_classes) in the place of '3C'; no heads."""
     Cf, D = nb_filters, patch_size * nb_filters
     if heads == HEADS_FUSION:
         if block_variant != 0:
@@ -72,7 +74,8 @@ def weight_spec(n_feat, patch_size, n_classes, nb_filters=32, kernel_size=3, nb_
                 if cin != Cf:
                     spec += [(p + "/matching/kernel", (1, cin, Cf), cin, Cf), (p + "/matching/bias", (Cf,), 0, None)]
                 cin = Cf
-    spec += [("3C/kernel", (D, n_classes), D, n_classes), ("3C/bias", (n_classes,), 0, None)]
+    out = "dense" if heads == HEADS_SINGLE else "3C"
+    spec += [(out + "/kernel", (D, n_classes), D, n_classes), (out + "/bias", (n_classes,), 0, None)]
     for name, odim, _ in head_spec(n_classes, heads):
         spec += [(name + "/dense/kernel", (D, 16), D, 16), (name + "/dense/bias", (16,), 0, None),
                  (name + "/bn/gamma", (16,), 1, None), (name + "/bn/beta", (16,), 0, None),
@@ -149,7 +152,7 @@ class B3MTL(TcnTrainingMixin, HostModel):
             "tcn_block": self.tcn_block}})
 
     def summary(self, print_fn=print):
-        kind = {HEADS_CASCADED: "cascaded MTL", HEADS_FUSION: "intermediate-fusion MTL"}.get(self.HEADS, "MTL")
+        kind = {HEADS_CASCADED: "cascaded MTL", HEADS_FUSION: "intermediate-fusion MTL", HEADS_SINGLE: "no"}.get(self.HEADS, "MTL")
         inputs = "2 x " if self.HEADS == HEADS_FUSION else ""
         self._summary("Model: %s (Lemaire et al. TCN + %s heads), input %s(None, %d, %d)"
                       % (self.CLASS_NAME, kind, inputs, self.patch_size, self.n_feat), print_fn)
@@ -381,3 +384,102 @@ class FusionMTL(B3MTL):
         return super().fit(x, y, batch_size=batch_size, epochs=epochs, verbose=verbose, callbacks=callbacks,
                            validation_data=validation_data, steps_per_epoch=steps_per_epoch, validation_steps=validation_steps,
                            initial_epoch=initial_epoch, **kwargs)
+
+
+class SingleTaskTCN(B3MTL):
+    """`model` object of get_Lemaire_model (lib/baseline_architectures.py:196-300; 5-class twin: 5_class_classification.py:54-145),
+    baseline 3 of Baseline_Results.py: B3_MTL's trunk, then Flatten -> Dense(n_classes) -> softmax -- no Dense(16), no BatchNorm, no
+    head dropout, no l2 term.  One input (N, W, n_feat) time-major (the reference feeds LogMelSpec patches), ONE output 'dense':
+    `predict` returns one (N, n_classes) array, `y` is one one-hot (N, n_classes) array.  n_classes == 2 is compiled with
+    binary_crossentropy on the two softmax outputs (so Keras' 'accuracy' is BINARY accuracy over the N x 2 outputs), 3 / 5 with
+    categorical_crossentropy and categorical accuracy; metrics_names = ['loss', 'accuracy'].  f32 and the keras-tcn 2.3.x block only:
+    the bf16 paths, `forward_from_x0` (the plain front end writes no layer-0 partials) and the single-head sub-model are B3_MTL's."""
+
+    HEADS = HEADS_SINGLE
+    CLASS_NAME = "B3_SingleTask"
+
+    def __init__(self, n_feat=80, patch_size=68, n_classes=2, TR_STEPS=1, loss_weights=None, seed=None, nb_filters=32,
+                 kernel_size=3, nb_stacks=3, n_dilations=8, tcn_block="2.3"):
+        if str(tcn_block) != "2.3":
+            raise ValueError("the single-task model is built for the keras-tcn 2.3.x block (tcn_block='2.3') only")
+        if n_classes not in (2, 3, 5):
+            raise ValueError("n_classes must be 2, 3 or 5, got %r" % (n_classes,))
+        super().__init__(n_feat=n_feat, patch_size=patch_size, n_classes=n_classes, TR_STEPS=TR_STEPS, loss_weights=loss_weights,
+                         seed=seed, nb_filters=nb_filters, kernel_size=kernel_size, nb_stacks=nb_stacks, n_dilations=n_dilations,
+                         tcn_block=tcn_block)
+
+    @property
+    def loss_name(self):
+        return "binary_crossentropy" if self.n_classes == 2 else "categorical_crossentropy"
+
+    @property
+    def output_names(self):
+        return ["dense"]
+
+    @property
+    def metrics_names(self):
+        return ["loss", "accuracy"]
+
+    def split_outputs(self, out):
+        return [out]
+
+    def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
+        """model.predict(x=batchData) -> ONE (N, n_classes) array, as a single-output Keras model returns it."""
+        return super().predict(x, batch_size, verbose, dtype)[0]
+
+    def forward_device(self, x, out=None, trunk=None, dtype="f32"):
+        """x: float32 CUDA tensor (N, W, n_feat) -> (N, n_classes) softmax on the device."""
+        if dtype != "f32":
+            raise ValueError("the single-task model has the f32 forward only, got dtype=%r" % (dtype,))
+        return super().forward_device(x, out, trunk, dtype)
+
+    def forward_from_x0(self, *args, **kwargs):
+        raise ValueError("the single-task model reads one plain featuregram: there are no per-half layer-0 partials to start from; "
+                         "use forward_device or forward_dense")
+
+    # ---- training surface ----
+    def compile(self, loss=None, optimizer=None, metrics=None, loss_weights=None, **kwargs):
+        """`model.compile(loss=..., metrics='accuracy', optimizer=...)` (baseline_architectures.py:292-295).  The loss is fixed by
+        n_classes (`loss_name`): anything else is an error, not a silent change."""
+        if isinstance(loss, dict):
+            loss = loss.get("dense") if set(loss) == {"dense"} else loss
+        if loss is not None and loss != self.loss_name:
+            raise ValueError("compile: the %d-class single-task model is built with %s, not %r" % (self.n_classes, self.loss_name, loss))
+        if metrics is not None:
+            mm = [metrics] if isinstance(metrics, str) else list(metrics.values() if isinstance(metrics, dict) else metrics)
+            if any(v not in ("accuracy", "acc") for v in mm):
+                raise ValueError("compile: the only metric of the single-task model is 'accuracy', got %r" % (metrics,))
+        super().compile(optimizer=optimizer, loss_weights=loss_weights, **kwargs)
+
+    def pack_targets(self, y):
+        """One one-hot (N, n_classes) array (or [array] / {'dense': array}) -> float32 CUDA tensor."""
+        if isinstance(y, dict):
+            y = y["dense"]
+        if isinstance(y, (list, tuple)) and len(y) == 1:
+            y = y[0]
+        y = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        t = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
+        if t.dim() != 2 or t.shape[1] != self.out_dim:
+            raise ValueError("targets must be one-hot (N, %d), got %s" % (self.out_dim, tuple(t.shape)))
+        return t.cuda().contiguous()
+
+    def losses_to_list(self, raw):
+        """Raw device losses [loss, weighted loss, accuracy, 0] of one step (or their mean over steps) -> [loss, accuracy]."""
+        lv = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+        return [float(lv[1] + lv[3]), float(lv[2])]
+
+    def train_on_batch(self, x, y, drop_tcn="auto", drop_heads=None, apply=True, sync=True, _only=None, _mask=TRAIN_ALL):
+        """One optimiser step -> [loss, accuracy].  There is no head dropout: drop_heads is accepted for the shared signature only."""
+        if _only is not None:
+            raise ValueError("single-output sub-models are built for the B3_MTL heads only")
+        return super().train_on_batch(x, y, drop_tcn=drop_tcn, drop_heads=None, apply=apply, sync=sync, _mask=_mask)
+
+    def _l2_penalty(self):
+        return 0.0
+
+    def _device_evaluate_ok(self):
+        return True  # smh_model_eval_losses_f32 holds the two-output bce and the binary accuracy; there is no host restatement
+
+    def _evaluate_device(self, x, y, steps, weight):
+        tot, cnt = super()._evaluate_device(x, y, steps, weight)  # [total | loss | accuracy]
+        return tot[[0, 2]], cnt

@@ -304,9 +304,9 @@ def model_from_json(text, seed=None):
         if rates:
             m.dropout_rate = float(rates[0])
         return m
-    if name in ("B3_MTL", "B3_MTL_Cascaded", "B3_MTL_Intermediate_Fusion"):
-        from .model import B3MTL, CascadedMTL, FusionMTL
-        cls = {"B3_MTL_Cascaded": CascadedMTL, "B3_MTL_Intermediate_Fusion": FusionMTL}.get(name, B3MTL)
+    if name in ("B3_MTL", "B3_MTL_Cascaded", "B3_MTL_Intermediate_Fusion", "B3_SingleTask"):
+        from .model import B3MTL, CascadedMTL, FusionMTL, SingleTaskTCN
+        cls = {"B3_MTL_Cascaded": CascadedMTL, "B3_MTL_Intermediate_Fusion": FusionMTL, "B3_SingleTask": SingleTaskTCN}.get(name, B3MTL)
         m = cls(n_feat=cfg["n_feat"], patch_size=cfg["patch_size"], n_classes=cfg["n_classes"], seed=seed,
                 **{k: cfg[k] for k in ("nb_filters", "kernel_size", "nb_stacks", "n_dilations", "tcn_block") if k in cfg})
         if "dropout_rate" in cfg:  # drawn at build time by the reference (proposed_architectures.py:136): part of the architecture
