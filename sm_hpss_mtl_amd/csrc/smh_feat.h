@@ -42,6 +42,52 @@ int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int
                      float *patches, hipStream_t st, const float *w0 = nullptr, float *x0p = nullptr, void *scratch = nullptr,
                      size_t scratch_bytes = 0);
 
+// ---- device helpers of the finishing kernels (smh_ragged.hip, smh_plain.hip) ------------------------------------------------------
+constexpr float kAmin = 1e-10f;  // librosa.power_to_db amin
+
+// item n of a 1-D grid whose workgroup i runs on XCD i % 8: the list in 8 contiguous ranges, one per XCD (smh_stft.hip has the reasoning)
+__device__ __forceinline__ bool xcd_item(int n_items, unsigned &n) {
+    const unsigned total = (unsigned)n_items, per_xcd = (total + 7u) >> 3;
+    const unsigned j = blockIdx.x >> 3;
+    n = (blockIdx.x & 7u) * per_xcd + j;
+    return j < per_xcd && n < total;
+}
+
+// top-dB floor in the power domain (features_clip_kernel has the derivation):
+//   max(10 log10(max(amin, x^2)), dBmax - 80) = 10 log10(max(x^2, lim)),  lim = max(amin, max(amin, xmax^2) * 1e-8)
+// -- the amin clamp acts on the f32 square
+__device__ __forceinline__ float floor_of_max(int key) {
+    const float xm = __int_as_float(key);
+    return fmaxf(kAmin, fmaxf(kAmin, xm * xm) * 1e-8f);
+}
+__device__ __forceinline__ float final_value(float x, float lim, int log_db) {
+    return log_db ? 3.0102999566398120f * __builtin_amdgcn_logf(fmaxf(x * x, lim)) : x;
+}
+
+// StandardScaler of one row (lib/preprocessing.py:211-214) from one shifted pass: x0 the row's first value, s and q the f64 sums of
+// d = value - x0 and of d^2 over its T frames -> the f64 mean and 1 / scale.  Population variance; constant rows stay unscaled by
+// sklearn's _is_constant_feature / _handle_zeros_in_scale, whose bound grows with the number of samples the scaler was fitted on:
+// n_fit, which the caller decides (T, or the tiled-if-short length).
+__device__ __forceinline__ void scaler_of_sums(double x0, double s, double q, int T, int n_fit, double &mean, double &inv_scale) {
+    const double md = s / (double)T;
+    mean = x0 + md;
+    const double var = fmax(q / (double)T - md * md, 0.0);
+    const double eps = 2.220446049250313e-16;
+    const double nm = (double)n_fit * mean * eps;
+    const bool constant = var <= (double)n_fit * eps * var + nm * nm;
+    double scale = sqrt(var);
+    if (constant || scale == 0.0) scale = 1.0;
+    inv_scale = 1.0 / scale;
+}
+
+// the patches p_lo .. p_hi that hold position u of the tiled featuregram (tools.extract_patches' grid, lib/cython_impl/tools.pyx:21-38:
+// patch p = frames p * shift .. p * shift + W - 1); patch starts are never clamped, so u sits at j = u - p * shift, 0 <= j < W
+__device__ __forceinline__ void patch_range(int u, int W, int shift, int nP, int &p_lo, int &p_hi) {
+    p_hi = u / shift;
+    if (p_hi > nP - 1) p_hi = nP - 1;
+    p_lo = u - W + 1 <= 0 ? 0 : (u - W + shift) / shift;  // ceil((u - W + 1) / shift)
+}
+
 }  // namespace smh_feat
 
 namespace smh_median {

@@ -35,19 +35,22 @@
 
 namespace {
 
+using smh_feat::final_value;
+using smh_feat::floor_of_max;
 using smh_feat::MelTable;
+using smh_feat::xcd_item;
+using smh_rag::align_up;
 using smh_rag::Clip;
+using smh_rag::HostClip;
 using smh_rag::Item;
+using smh_rag::Layout;
 
-constexpr float kAmin = 1e-10f;  // librosa.power_to_db amin
 constexpr int kTile = 64;        // frames per projection workgroup and per finishing chunk: one lane per frame
 constexpr int kProjWaves = 8;
 constexpr int kRowBlock = 32;    // rows per finishing workgroup: 128-byte runs in the time-major patches
 constexpr int kFinWaves = 4;
 constexpr int kRowsPerWave = kRowBlock / kFinWaves;
 constexpr size_t kMaxImageBytes = 150 * 1024;
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // the clips of a launch: a descriptor table (ragged calls) or, with clips == nullptr, B equal clips of T frames laid out densely
 struct Geo {
@@ -73,14 +76,6 @@ __device__ __forceinline__ ClipView clip_view(const Geo &g, int K, int rows, int
         v.T = g.T, v.Ttiled = g.Ttiled, v.nP = g.nP;
     }
     return v;
-}
-
-// item n of a 1-D grid whose workgroup i runs on XCD i % 8: the list in 8 contiguous ranges, one per XCD (smh_stft.hip has the reasoning)
-__device__ __forceinline__ bool xcd_item(int n_items, unsigned &n) {
-    const unsigned total = (unsigned)n_items, per_xcd = (total + 7u) >> 3;
-    const unsigned j = blockIdx.x >> 3;
-    n = (blockIdx.x & 7u) * per_xcd + j;
-    return j < per_xcd && n < total;
 }
 
 __global__ void __launch_bounds__(64 * kProjWaves)
@@ -155,16 +150,6 @@ plain_project_kernel(MelTable mt, const float *__restrict__ S, int K, int rows, 
     }
 }
 
-// top-dB floor in the power domain:  max(10 log10(max(amin, x^2)), dBmax - 80) = 10 log10(max(x^2, lim)),
-// lim = max(amin, max(amin, xmax^2) * 1e-8) -- the amin clamp acts on the f32 square
-__device__ __forceinline__ float floor_of_max(int key) {
-    const float xm = __int_as_float(key);
-    return fmaxf(kAmin, fmaxf(kAmin, xm * xm) * 1e-8f);
-}
-__device__ __forceinline__ float final_value(float x, float lim, int log_db) {
-    return log_db ? 3.0102999566398120f * __builtin_amdgcn_logf(fmaxf(x * x, lim)) : x;
-}
-
 __global__ void __launch_bounds__(64 * kFinWaves)
 plain_finish_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int log_db, int K, int rows, int nrb, int W, int shift,
                     float *__restrict__ patches, Geo g) {
@@ -203,15 +188,9 @@ plain_finish_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int
         for (int q = 0; q < kRowsPerWave; ++q) {
             double a = s[q], b = sq[q];
             for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off), b += __shfl_xor(b, off);
-            const double md = a / (double)T;
-            const double mu = x0[q] + md;
-            const double var = fmax(b / (double)T - md * md, 0.0);
-            const double eps = 2.220446049250313e-16;
-            const double nm = (double)c.Ttiled * mu * eps;
-            const bool constant = var <= (double)c.Ttiled * eps * var + nm * nm;
-            double scale = sqrt(var);
-            if (constant || scale == 0.0) scale = 1.0;
-            mean[q] = mu, inv[q] = (float)(1.0 / scale);
+            double inv_scale;
+            smh_feat::scaler_of_sums(x0[q], a, b, T, c.Ttiled, mean[q], inv_scale);
+            inv[q] = (float)inv_scale;
         }
     }
     if (!want && !log_db) return;  // nothing to finish: fv is final as projected
@@ -237,11 +216,10 @@ plain_finish_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int
         const int nP = c.nP, Tt = c.Ttiled;
         for (int tl = tl0; tl < nt; tl += (64 * kFinWaves) / kRowBlock) {
             for (int u = c0 + tl; u < Tt; u += T) {  // the frame's positions in the tiled featuregram (one unless T < W)
-                int p_hi = u / shift;
-                if (p_hi > nP - 1) p_hi = nP - 1;
-                const int p_lo = u - W + 1 <= 0 ? 0 : (u - W + shift) / shift;  // ceil((u - W + 1) / shift)
+                int p_lo, p_hi;
+                smh_feat::patch_range(u, W, shift, nP, p_lo, p_hi);
                 for (int p = p_lo; p <= p_hi; ++p) {
-                    const int j = u - p * shift;  // 0 <= j < W: patch starts are never clamped
+                    const int j = u - p * shift;
                     if (f < nr) patches[((c.patch_off + (size_t)p) * W + j) * rows + r0 + f] = tile[f * (kTile + 1) + tl];
                 }
             }
@@ -330,27 +308,8 @@ extern "C" int smh_plain_frontend_f32(const smh_ctx *ctx, const float *d_audio, 
     return smh_plain_features_f32(ctx, S, B, T, W, shift, d_fv, d_patches, keys, stream);
 }
 
-// ---- ragged batches: the contract of smh_frontend_ragged_sizes / smh_frontend_ragged_f32 (smh_ragged.hip) -------------------------
+// ---- ragged batches: the contract of smh_frontend_ragged_sizes / smh_frontend_ragged_f32, on the planner of smh_rag.h ----------------
 namespace {
-
-struct PlainPlan {
-    std::vector<int> T, nP;
-    std::vector<long long> fv_off, patch_off;
-};
-
-int plan_plain(const smh_ctx *ctx, const long long *off, const int *len, int B, int W, int shift, bool patches, PlainPlan &p) {
-    p.T.assign(B, 0), p.nP.assign(B, 0), p.fv_off.assign(B + 1, 0), p.patch_off.assign(B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        SMH_REQUIRE(off[b] >= 0 && len[b] >= 0, "plain ragged: clip %d has a negative offset or length", b);
-        const int T = smh_num_frames(len[b], ctx->cfg.n_fft, ctx->cfg.hop);
-        SMH_REQUIRE(T >= 1, "plain ragged: clip %d of %d samples is shorter than n_fft=%d", b, len[b], ctx->cfg.n_fft);
-        p.T[b] = T;
-        p.nP[b] = patches ? smh_num_patches(smh_tiled_frames(T, W), W, shift) : 0;
-        p.fv_off[b + 1] = p.fv_off[b] + (long long)ctx->feat_rows * T;
-        p.patch_off[b + 1] = p.patch_off[b] + p.nP[b];
-    }
-    return SMH_OK;
-}
 
 // device bytes one clip adds to a sub-batch: its descriptor, its max key, its (clip, tile) items of both stages (the STFT's counted
 // at 16 frames, a lower bound of its tile) and its S
@@ -358,54 +317,28 @@ size_t plain_clip_bytes(const smh_ctx *ctx, int T) {
     const size_t items = (size_t)(T + 15) / 16 + (size_t)(T + kTile - 1) / kTile;
     return align_up((size_t)ctx->K * T, 4) * sizeof(float) + items * sizeof(Item) + sizeof(Clip) + sizeof(int);
 }
-constexpr size_t kPlainFixedBytes = 6 * 256;             // alignment slack between the regions of a sub-batch
-constexpr size_t kPlainWorkCap = (size_t)8 << 30;       // what the sizes call asks for at most
+constexpr size_t kPlainFixedBytes = 6 * 256;  // alignment slack between the regions of a sub-batch
 
-struct PlainHostClip {
-    long long audio_off, fv_off, patch_off;
-    int T, Ttiled, nP;
-};
-
-int plain_sub_batch(const smh_ctx *ctx, const float *d_audio, const PlainHostClip *hc, int n, int W, int shift, float *d_fv,
-                    float *d_patches, char *d_work, hipStream_t st) {
-    const int stft_frames = smh_stft::rag_frames(ctx, true);
-    std::vector<Clip> clips(n);
-    std::vector<Item> it_stft, it_proj;
-    size_t spec = 0;
-    for (int b = 0; b < n; ++b) {
-        const PlainHostClip &h = hc[b];
-        Clip &c = clips[b];
-        memset(&c, 0, sizeof(c));
-        c.audio_off = h.audio_off, c.fv_off = h.fv_off, c.patch_off = h.patch_off, c.spec_off = (long long)spec;
-        c.T = h.T, c.Ttiled = h.Ttiled, c.nP = d_patches ? h.nP : 0;
-        spec += align_up((size_t)ctx->K * h.T, 4);
-        for (int t = 0, i = 0; t < h.T; t += stft_frames, ++i) it_stft.push_back({b, i});
-        for (int t = 0, i = 0; t < h.T; t += kTile, ++i) it_proj.push_back({b, i});
-    }
-    // the tables as one blob: [clips][stft items][projection items][max keys = 0]
-    size_t off = 0;
-    auto place = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 16);
-        return o;
-    };
-    const size_t o_clips = place(clips.size() * sizeof(Clip));
-    const size_t o_stft = place(it_stft.size() * sizeof(Item)), o_proj = place(it_proj.size() * sizeof(Item));
-    const size_t o_keys = place((size_t)n * sizeof(int));
-    std::vector<char> blob(off, 0);
-    memcpy(blob.data() + o_clips, clips.data(), clips.size() * sizeof(Clip));
-    memcpy(blob.data() + o_stft, it_stft.data(), it_stft.size() * sizeof(Item));
-    memcpy(blob.data() + o_proj, it_proj.data(), it_proj.size() * sizeof(Item));
-    int rc = smh_rag::upload_tables(ctx, blob.data(), blob.size(), d_work, st);
-    if (rc) return rc;
-    float *d_S = reinterpret_cast<float *>(d_work + align_up(blob.size(), 256));
-    const Clip *d_clips = reinterpret_cast<const Clip *>(d_work + o_clips);
-    rc = smh_stft::launch_rag(ctx, d_audio, d_S, d_clips, reinterpret_cast<const Item *>(d_work + o_stft), (int)it_stft.size(), true, st);
-    if (rc) return rc;
+int plain_sub_batch(const smh_ctx *ctx, const float *d_audio, const HostClip *hc, int n, int W, int shift, float *d_fv,
+                    float *d_patches, char *d_work, size_t work_bytes, hipStream_t st) {
+    std::vector<Clip> clips;
+    const size_t spec = smh_rag::fill_clips(hc, n, ctx->K, d_patches != nullptr, clips);
+    // the tables: [clips][stft items][projection items][max keys = 0]
+    smh_rag::Tables t;
     Geo g;
-    g.clips = d_clips, g.items = reinterpret_cast<const Item *>(d_work + o_proj), g.n_items = (int)it_proj.size();
+    int n_stft;
+    const size_t o_clips = t.add(clips.data(), clips.size() * sizeof(Clip));
+    const size_t o_stft = t.add_items(hc, n, smh_stft::rag_frames(ctx, true), -1, &n_stft);
+    const size_t o_proj = t.add_items(hc, n, kTile, -1, &g.n_items);
+    const size_t o_keys = t.add(nullptr, (size_t)n * sizeof(int));
+    int rc = t.upload(ctx, "smh_plain_frontend_ragged_f32", d_work, work_bytes, spec * sizeof(float), st);
+    if (rc) return rc;
+    float *d_S = reinterpret_cast<float *>(t.behind());
+    g.clips = t.at<const Clip>(o_clips), g.items = t.at<const Item>(o_proj);
+    rc = smh_stft::launch_rag(ctx, d_audio, d_S, g.clips, t.at<const Item>(o_stft), n_stft, true, st);
+    if (rc) return rc;
     g.T = g.Ttiled = g.nP = g.ntiles = 0;
-    return launch_pair(ctx, d_S, d_fv, d_patches, reinterpret_cast<int *>(d_work + o_keys), g, n, W, shift, st);
+    return launch_pair(ctx, d_S, d_fv, d_patches, t.at<int>(o_keys), g, n, W, shift, st);
 }
 
 // the specialised n_fft = 400 STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when
@@ -422,17 +355,10 @@ extern "C" int smh_plain_frontend_ragged_sizes(const smh_ctx *ctx, const long lo
                                                size_t *work_bytes) {
     SMH_REQUIRE(ctx && (B == 0 || (h_offsets && h_lengths)) && B >= 0, "smh_plain_frontend_ragged_sizes: bad argument");
     SMH_REQUIRE(W <= 0 || shift >= 1, "smh_plain_frontend_ragged_sizes: bad patch geometry W=%d shift=%d", W, shift);
-    PlainPlan p;
-    int rc = plan_plain(ctx, h_offsets, h_lengths, B, W, shift, W > 0, p);
+    Layout p;
+    int rc = smh_rag::plan_layout(ctx, "plain ragged", h_offsets, h_lengths, B, W, shift, W > 0, ctx->feat_rows, p);
     if (rc) return rc;
-    for (int b = 0; b <= B; ++b) {
-        if (h_fv_off) h_fv_off[b] = p.fv_off[b];
-        if (h_patch_off) h_patch_off[b] = p.patch_off[b];
-    }
-    for (int b = 0; b < B; ++b) {
-        if (h_T) h_T[b] = p.T[b];
-        if (h_nP) h_nP[b] = p.nP[b];
-    }
+    smh_rag::export_layout(p, B, h_fv_off, h_patch_off, h_T, h_nP);
     if (work_bytes) {
         size_t total = kPlainFixedBytes, single = 0;
         for (int b = 0; b < B; ++b) {
@@ -440,7 +366,7 @@ extern "C" int smh_plain_frontend_ragged_sizes(const smh_ctx *ctx, const long lo
             total += cb;
             single = std::max(single, std::max(cb + kPlainFixedBytes, smh_plain_frontend_workspace_bytes(ctx, 1, h_lengths[b])));
         }
-        *work_bytes = B == 0 ? 0 : align_up(std::max(single, std::min(total, kPlainWorkCap)), 256);
+        *work_bytes = smh_rag::work_size(B, single, total);
     }
     return SMH_OK;
 }
@@ -454,43 +380,22 @@ extern "C" int smh_plain_frontend_ragged_f32(const smh_ctx *ctx, const float *d_
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0, "smh_plain_frontend_ragged_f32: the workspace must start on a 16-byte boundary");
     int rc = check_context(ctx, "smh_plain_frontend_ragged_f32");
     if (rc) return rc;
-    PlainPlan p;
-    rc = plan_plain(ctx, h_offsets, h_lengths, B, W, shift, patches, p);
+    Layout p;
+    rc = smh_rag::plan_layout(ctx, "plain ragged", h_offsets, h_lengths, B, W, shift, patches, ctx->feat_rows, p);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return smh::set_error(SMH_E_INVALID, "the ragged front end uploads its tables from a staging buffer: it cannot be captured in a graph");
-    std::vector<PlainHostClip> hc;
+    auto taken = [&](int b) { return plain_rag_ok(ctx, d_audio, h_offsets[b]); };
+    std::vector<HostClip> hc;
     hc.reserve(B);
-    for (int b = 0; b < B; ++b) {
-        if (!plain_rag_ok(ctx, d_audio, h_offsets[b])) continue;
-        hc.push_back({h_offsets[b], p.fv_off[b], p.patch_off[b], p.T[b], smh_tiled_frames(p.T[b], W > 0 ? W : 1), p.nP[b]});
-    }
-    // as few sub-batches as the workspace allows
-    size_t b0 = 0;
-    while (b0 < hc.size()) {
-        size_t need = kPlainFixedBytes, b1 = b0;
-        while (b1 < hc.size()) {
-            const size_t cb = plain_clip_bytes(ctx, hc[b1].T);
-            if (b1 > b0 && need + cb > work_bytes) break;
-            need += cb;
-            ++b1;
-        }
-        if (need > work_bytes)
-            return smh::set_error(SMH_E_WORKSPACE, "smh_plain_frontend_ragged_f32: workspace %zu < %zu needed by a single clip", work_bytes, need);
-        rc = plain_sub_batch(ctx, d_audio, hc.data() + b0, (int)(b1 - b0), W, shift, d_fv, d_patches, (char *)d_work, st);
-        if (rc) return rc;
-        b0 = b1;
-    }
-    // the clips off an 8-byte boundary, one by one on the same stream (the workspace is free again in stream order)
-    const size_t prow = (size_t)(W > 0 ? W : 0) * ctx->feat_rows;
-    for (int b = 0; b < B; ++b) {
-        if (plain_rag_ok(ctx, d_audio, h_offsets[b])) continue;
-        float *pt = patches && p.nP[b] > 0 ? d_patches + (size_t)p.patch_off[b] * prow : nullptr;
-        rc = smh_plain_frontend_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], pt ? W : 0, pt ? shift : 0, d_fv + p.fv_off[b], pt, d_work,
-                                    work_bytes, nullptr, stream);
-        if (rc < 0) return rc;
-    }
-    return SMH_OK;
+    for (int b = 0; b < B; ++b)
+        if (taken(b)) hc.push_back(smh_rag::host_clip(p, h_offsets, b, W, 0));
+    rc = smh_rag::run_sub_batches(
+        hc.size(), kPlainFixedBytes, work_bytes, st, [&](size_t b) { return plain_clip_bytes(ctx, hc[b].T); }, [&](size_t b0, size_t nb) {
+            return plain_sub_batch(ctx, d_audio, hc.data() + b0, (int)nb, W, shift, d_fv, d_patches, (char *)d_work, work_bytes, st);
+        });
+    if (rc) return rc;
+    // the clips off an 8-byte boundary, through smh_plain_frontend_f32 (the workspace is free again in stream order)
+    return smh_rag::run_alone(p, B, W, shift, ctx->feat_rows, d_fv, d_patches, taken, [&](int b, int w, int sh, float *fv, float *pt) {
+        return smh_plain_frontend_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], w, sh, fv, pt, d_work, work_bytes, nullptr, stream);
+    });
 }

@@ -2,9 +2,12 @@
 // The reference's callers feed one file at a time (Proposed_Work_Results.py:92-95, 131-134, 189-192, 465-474 -> get_featuregram,
 // lib/preprocessing.py:355-457, and get_feature_patches, :137-292); here the files of a batch are one launch per stage: every
 // kernel takes a per-clip descriptor table and a flat (clip, tile) work list built on the host by smh_frontend_ragged_f32
-// (smh_ragged.hip) and uploaded once per call.
+// (smh_ragged.hip) and uploaded once per call.  The host half -- the planner below -- is shared by every front end with a ragged
+// entry ("Ragged batches": what a front end supplies); its implementation lives in smh_ragged.hip.
 #pragma once
 #include <cstdint>
+#include <functional>
+#include <vector>
 
 #include "smh_common.h"
 
@@ -36,9 +39,59 @@ struct Item {
 //   2  the streaming kernels of smh_ragged.hip           3  neither: launch_hp_feat + launch_std_patch on the whole clip
 int feature_route(const smh_ctx *ctx, int T);
 
-// host -> device copy of a call's tables through a pinned slot of the context (smh_ragged.hip: stage_upload), stream-ordered on st;
-// the plain front end's ragged entry (smh_plain.hip) uploads its tables the same way
-int upload_tables(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst, hipStream_t st);
+// ---- the host-side planner of a ragged entry (smh_frontend_ragged_*, smh_plain_frontend_ragged_*) -------------------------------
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// where every clip of a call lies in the caller's buffers: frames, patches, and the floats / patches in front of clip b (B + 1 sums);
+// fv_rows: featuregram rows per clip (2 * feat_rows with the H || P pair); `who` prefixes the error texts
+struct Layout {
+    std::vector<int> T, nP;
+    std::vector<long long> fv_off, patch_off;
+};
+int plan_layout(const smh_ctx *ctx, const char *who, const long long *off, const int *len, int B, int W, int shift, bool patches,
+                int fv_rows, Layout &p);
+// the layout into the arrays of a *_ragged_sizes call (any of them may be null)
+void export_layout(const Layout &p, int B, long long *h_fv_off, long long *h_patch_off, int *h_T, int *h_nP);
+// what a *_ragged_sizes call asks for: every clip at once (total) up to 8 GiB, never less than the largest single clip needs (single)
+size_t work_size(int B, size_t single, size_t total);
+
+struct HostClip {  // one clip a sub-batch takes
+    long long audio_off, fv_off, patch_off;
+    int T, Ttiled, nP;
+    int cls;  // the front end's own class of the clip (smh_ragged.hip: the feature route; unused by smh_plain.hip)
+};
+HostClip host_clip(const Layout &p, const long long *off, int b, int W, int cls);
+// the descriptors of a sub-batch (harm_off and row0 stay 0); returns the floats of S: the sum of K * T, each rounded up to 4
+size_t fill_clips(const HostClip *hc, int n, int K, bool patches, std::vector<Clip> &clips);
+
+// The tables of one sub-batch as ONE blob at the start of the workspace: every add() places its region on the next 16-byte
+// boundary, in the order of the calls, and returns the region's offset -- the handle at<>() turns into a device pointer.
+class Tables {
+  public:
+    size_t add(const void *src, size_t bytes);  // src == nullptr: zeros (the max keys)
+    // the (clip, tile) work list of a stage of `frames` frames per item over the clips of class cls (-1: all of them)
+    size_t add_items(const HostClip *hc, int n, int frames, int cls, int *count);
+    // one copy through a pinned slot of the context, stream-ordered on st; before it, the sub-batch's true extent -- the tables and
+    // `behind` bytes of device regions behind them -- is checked against the workspace (SMH_E_WORKSPACE, `who` in the text)
+    int upload(const smh_ctx *ctx, const char *who, char *d_work, size_t work_bytes, size_t behind, hipStream_t st);
+    template <class T>
+    T *at(size_t off) const { return reinterpret_cast<T *>(d_ + off); }
+    char *behind() const { return d_ + align_up(blob_.size(), 256); }  // the first device region behind the tables
+
+  private:
+    std::vector<char> blob_;
+    char *d_ = nullptr;
+};
+
+// clips [0, n) in as few sub-batches as the workspace allows by the front end's estimate: `fixed` bytes plus bytes(b) per clip;
+// run(first, count) enqueues one.  A clip the estimate finds too large even alone is tried alone: Tables::upload decides by its true
+// extent.  Refuses a capturing stream before anything is enqueued (the tables come from a staging buffer).
+int run_sub_batches(size_t n, size_t fixed, size_t work_bytes, hipStream_t st,
+                    const std::function<size_t(size_t)> &bytes, const std::function<int(size_t, size_t)> &run);
+// the clips no sub-batch took (!taken(b)), one by one through the equal-length entry on the same stream:
+// alone(b, W, shift, fv, patches) with W = shift = 0 and patches = nullptr for a clip without patches
+int run_alone(const Layout &p, int B, int W, int shift, int fv_rows, float *d_fv, float *d_patches,
+              const std::function<bool(int)> &taken, const std::function<int(int, int, int, float *, float *)> &alone);
 
 }  // namespace smh_rag
 

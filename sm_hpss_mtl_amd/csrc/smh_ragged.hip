@@ -55,15 +55,18 @@ void destroy_staging(Staging *s) {
 namespace {
 
 using smh_feat::FeatPlan;
+using smh_feat::final_value;
+using smh_feat::floor_of_max;
+using smh_feat::xcd_item;
+using smh_rag::align_up;
 using smh_rag::Clip;
+using smh_rag::HostClip;
 using smh_rag::Item;
+using smh_rag::Layout;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr float kAmin = 1e-10f;  // librosa.power_to_db amin
 constexpr int kWalkFrames = 128;  // frames per walk item: 64 lanes x a pair of frames
 constexpr int kFinalFrames = 64;  // frames per finalisation item
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // host -> device copy of a call's tables through a pinned slot of the context (ring of four; a slot is reused only after its
 // previous copy has completed, which in practice it long has)
@@ -90,14 +93,6 @@ int stage_upload(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst,
     SMH_CHECK_HIP(hipEventRecord(sl.ev, st));
     sl.in_flight = true;
     return SMH_OK;
-}
-
-// item n of a 1-D grid whose workgroup i runs on XCD i % 8: the list in 8 contiguous ranges, one per XCD (smh_stft.hip has the reasoning)
-__device__ __forceinline__ bool xcd_item(int n_items, unsigned &n) {
-    const unsigned total = (unsigned)n_items, per_xcd = (total + 7u) >> 3;
-    const unsigned j = blockIdx.x >> 3;
-    n = (blockIdx.x & 7u) * per_xcd + j;
-    return j < per_xcd && n < total;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -245,16 +240,6 @@ rag_walk_kernel(FeatPlan fp, const float *__restrict__ S, const float *__restric
     if (lane == 0) atomicMax(&maxkeys[2 * item.clip + half], key);
 }
 
-// top-dB floor in the power domain (features_clip_kernel has the derivation):
-//   max(10 log10(max(amin, x^2)), dBmax - 80) = 10 log10(max(x^2, lim)),  lim = max(amin, max(amin, xmax^2) * 1e-8)
-__device__ __forceinline__ float floor_of_max(int key) {
-    const float xm = __int_as_float(key);
-    return fmaxf(kAmin, fmaxf(kAmin, xm * xm) * 1e-8f);
-}
-__device__ __forceinline__ float final_value(float x, float lim, int log_db) {
-    return log_db ? 3.0102999566398120f * __builtin_amdgcn_logf(fmaxf(x * x, lim)) : x;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // rag_stats_kernel: StandardScaler statistics of one featuregram row per wave (lib/preprocessing.py:211-214, 221-224: per row over
 // the frames, population variance, constant rows left unscaled -- sklearn's _is_constant_feature / _handle_zeros_in_scale), in
@@ -283,16 +268,10 @@ rag_stats_kernel(const float *__restrict__ fv, const int *__restrict__ maxkeys, 
         q += d * d;
     }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off), q += __shfl_xor(q, off);
-    const double md = s / (double)T;
-    const double mean = x0 + md;
-    const double var = fmax(q / (double)T - md * md, 0.0);
-    const double eps = 2.220446049250313e-16;
-    const double nm = (double)T * mean * eps;
-    const bool constant = var <= (double)T * eps * var + nm * nm;
-    double scale = sqrt(var);
-    if (constant || scale == 0.0) scale = 1.0;
+    double mean, inv_scale;
+    smh_feat::scaler_of_sums(x0, s, q, T, T, mean, inv_scale);  // (the constant-row rule counts the clip's own T frames here)
     // the f64 mean as hi + lo floats, 1 / scale as a float: what the LDS-image kernels keep per row as well
-    if (lane == 0) stats[rg] = make_float4((float)mean, (float)(mean - (double)(float)mean), (float)(1.0 / scale), 0.f);
+    if (lane == 0) stats[rg] = make_float4((float)mean, (float)(mean - (double)(float)mean), (float)inv_scale, 0.f);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -345,11 +324,10 @@ rag_final_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int lo
     const int nP = c.nP, Tt = c.Ttiled;
     for (int tl = wave; tl < nt; tl += nw) {
         for (int v = t0 + tl; v < Tt; v += T) {  // the frame's positions in the tiled featuregram (one unless T < W)
-            int p_hi = v / shift;
-            if (p_hi > nP - 1) p_hi = nP - 1;
-            int p_lo = v - W + 1 <= 0 ? 0 : (v - W + shift) / shift;  // ceil((v - W + 1) / shift)
+            int p_lo, p_hi;
+            smh_feat::patch_range(v, W, shift, nP, p_lo, p_hi);
             for (int p = p_lo; p <= p_hi; ++p) {
-                const int j = v - p * shift;  // 0 <= j < W: patch starts are never clamped (their centres end W/2 before the last frame)
+                const int j = v - p * shift;
                 float *o = patches + (((size_t)c.patch_off + p) * W + j) * R2;
                 for (int f = lane; f < R2; f += 64) o[f] = tile[f * ld + tl];
             }
@@ -358,12 +336,7 @@ rag_final_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int lo
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-struct HostClip {
-    long long audio_off, fv_off, patch_off;
-    int T, Ttiled, nP;
-    int cls;  // 0: LDS image, even T; 1: LDS image, odd T; 2: streaming kernels
-};
-
+// (HostClip::cls here: 0: LDS image, even T; 1: LDS image, odd T; 2: streaming kernels)
 struct RagGeom {
     int K, rows, stft_frames, med_frames;
 };
@@ -398,108 +371,80 @@ bool rag_clip_ok(const smh_ctx *ctx, int T) {
 
 // one sub-batch: tables -> one upload -> one launch per stage
 int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, const HostClip *hc, int n, int W, int shift, float *d_fv,
-                  float *d_patches, char *d_work, bool stft_aligned8, hipStream_t st) {
-    std::vector<Clip> clips(n);
-    std::vector<Item> it_stft, it_med, it_walk, it_final;
+                  float *d_patches, char *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st) {
+    std::vector<Clip> clips;
+    const size_t spec = smh_rag::fill_clips(hc, n, g.K, d_patches != nullptr, clips);
     std::vector<int> list[3];
-    size_t spec = 0, harm = 0;
+    size_t harm = 0;
     int max_T[2] = {0, 0};
     for (int b = 0; b < n; ++b) {
         const HostClip &h = hc[b];
-        Clip &c = clips[b];
-        memset(&c, 0, sizeof(c));
-        c.audio_off = h.audio_off, c.fv_off = h.fv_off, c.patch_off = h.patch_off;
-        c.spec_off = (long long)spec, c.harm_off = (long long)harm;
-        c.T = h.T, c.Ttiled = h.Ttiled, c.nP = d_patches ? h.nP : 0;
-        c.row0 = h.cls == 2 ? (int)list[2].size() * 2 * g.rows : 0;
-        spec += align_up((size_t)g.K * h.T, 4);
+        clips[b].harm_off = (long long)harm;
+        clips[b].row0 = h.cls == 2 ? (int)list[2].size() * 2 * g.rows : 0;
         harm += (size_t)((h.T + 15) / 16) * 16 * g.K;
-        for (int t = 0, i = 0; t < h.T; t += g.stft_frames, ++i) it_stft.push_back({b, i});
-        for (int t = 0, i = 0; t < h.T; t += g.med_frames, ++i) it_med.push_back({b, i});
-        if (h.cls == 2) {
-            for (int t = 0, i = 0; t < h.T; t += kWalkFrames, ++i) it_walk.push_back({b, i});
-            for (int t = 0, i = 0; t < h.T; t += kFinalFrames, ++i) it_final.push_back({b, i});
-        } else {
-            max_T[h.cls] = std::max(max_T[h.cls], h.T);
-        }
+        if (h.cls != 2) max_T[h.cls] = std::max(max_T[h.cls], h.T);
         list[h.cls].push_back(b);
     }
-    // the tables as one blob: [clips][stft items][median items][walk items][final items][lists 0, 1, 2][max keys = 0]
-    size_t off = 0;
-    auto place = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 16);
-        return o;
-    };
-    const size_t o_clips = place(clips.size() * sizeof(Clip));
-    const size_t o_stft = place(it_stft.size() * sizeof(Item)), o_med = place(it_med.size() * sizeof(Item));
-    const size_t o_walk = place(it_walk.size() * sizeof(Item)), o_final = place(it_final.size() * sizeof(Item));
-    const size_t o_l0 = place(list[0].size() * sizeof(int)), o_l1 = place(list[1].size() * sizeof(int)),
-                 o_l2 = place(list[2].size() * sizeof(int));
-    const size_t o_keys = place((size_t)2 * n * sizeof(int));
-    std::vector<char> blob(off, 0);
-    auto put = [&](size_t o, const void *p, size_t bytes) {
-        if (bytes) memcpy(blob.data() + o, p, bytes);
-    };
-    put(o_clips, clips.data(), clips.size() * sizeof(Clip));
-    put(o_stft, it_stft.data(), it_stft.size() * sizeof(Item));
-    put(o_med, it_med.data(), it_med.size() * sizeof(Item));
-    put(o_walk, it_walk.data(), it_walk.size() * sizeof(Item));
-    put(o_final, it_final.data(), it_final.size() * sizeof(Item));
-    put(o_l0, list[0].data(), list[0].size() * sizeof(int));
-    put(o_l1, list[1].data(), list[1].size() * sizeof(int));
-    put(o_l2, list[2].data(), list[2].size() * sizeof(int));
-    int rc = stage_upload(ctx, blob.data(), blob.size(), d_work, st);
+    // the tables: [clips][stft items][median items][walk items][final items][lists 0, 1, 2][max keys = 0]
+    smh_rag::Tables t;
+    int n_stft, n_med, n_walk, n_final;
+    const size_t o_clips = t.add(clips.data(), clips.size() * sizeof(Clip));
+    const size_t o_stft = t.add_items(hc, n, g.stft_frames, -1, &n_stft), o_med = t.add_items(hc, n, g.med_frames, -1, &n_med);
+    const size_t o_walk = t.add_items(hc, n, kWalkFrames, 2, &n_walk), o_final = t.add_items(hc, n, kFinalFrames, 2, &n_final);
+    size_t o_list[3];
+    for (int k = 0; k < 3; ++k) o_list[k] = t.add(list[k].data(), list[k].size() * sizeof(int));
+    const size_t o_keys = t.add(nullptr, (size_t)2 * n * sizeof(int));
+    // device regions behind the tables, each on a 256-byte boundary: stats, S, perc, harm
+    const size_t stats_bytes = list[2].size() * (size_t)2 * g.rows * sizeof(float4);
+    const size_t behind = align_up(stats_bytes, 256) + 2 * align_up(spec * sizeof(float), 256) + harm * sizeof(float);
+    int rc = t.upload(ctx, "ragged front end", d_work, work_bytes, behind, st);
     if (rc) return rc;
-    // device regions behind the tables
-    size_t w = align_up(blob.size(), 256);
-    float4 *d_stats = reinterpret_cast<float4 *>(d_work + w);
-    w = align_up(w + list[2].size() * (size_t)2 * g.rows * sizeof(float4), 256);
-    float *d_S = reinterpret_cast<float *>(d_work + w);
-    w = align_up(w + spec * sizeof(float), 256);
-    float *d_perc = reinterpret_cast<float *>(d_work + w);
-    w = align_up(w + spec * sizeof(float), 256);
-    float *d_harm = reinterpret_cast<float *>(d_work + w);
-    const Clip *d_clips = reinterpret_cast<const Clip *>(d_work + o_clips);
-    auto items_at = [&](size_t o) { return reinterpret_cast<const Item *>(d_work + o); };
-    auto list_at = [&](size_t o) { return reinterpret_cast<const int *>(d_work + o); };
-    int *d_keys = reinterpret_cast<int *>(d_work + o_keys);
-
-    rc = smh_stft::launch_rag(ctx, d_audio, d_S, d_clips, items_at(o_stft), (int)it_stft.size(), stft_aligned8, st);
+    char *w = t.behind();
+    auto region = [&](size_t bytes) {
+        char *r = w;
+        w += align_up(bytes, 256);
+        return r;
+    };
+    float4 *d_stats = reinterpret_cast<float4 *>(region(stats_bytes));
+    float *d_S = reinterpret_cast<float *>(region(spec * sizeof(float)));
+    float *d_perc = reinterpret_cast<float *>(region(spec * sizeof(float)));
+    float *d_harm = reinterpret_cast<float *>(w);
+    const Clip *d_clips = t.at<const Clip>(o_clips);
+    int *d_keys = t.at<int>(o_keys);
+    rc = smh_stft::launch_rag(ctx, d_audio, d_S, d_clips, t.at<const Item>(o_stft), n_stft, stft_aligned8, st);
     if (rc) return rc;
-    rc = smh_median::launch_rag(d_S, d_harm, d_perc, g.K, ctx->cfg.l_harm, ctx->cfg.l_perc, d_clips, items_at(o_med), (int)it_med.size(), st);
+    rc = smh_median::launch_rag(d_S, d_harm, d_perc, g.K, ctx->cfg.l_harm, ctx->cfg.l_perc, d_clips, t.at<const Item>(o_med), n_med, st);
     if (rc) return rc;
     // (The LDS-image clips' small grids were tried on a side stream beside the streaming kernels: the fork / join events cost the host
     // 0.4 ms per call and the call got slower, 0.74 -> 1.10 ms per 256 files; everything stays on the caller's stream.)
-    rc = smh_feat::launch_features_rag(ctx, d_S, d_harm, d_perc, d_clips, list_at(o_l0), (int)list[0].size(), max_T[0], 1, W > 0 ? W : 1,
-                                       shift > 0 ? shift : 1, d_fv, d_patches, st);
-    if (rc) return rc;
-    rc = smh_feat::launch_features_rag(ctx, d_S, d_harm, d_perc, d_clips, list_at(o_l1), (int)list[1].size(), max_T[1], 0, W > 0 ? W : 1,
-                                       shift > 0 ? shift : 1, d_fv, d_patches, st);
-    if (rc) return rc;
+    for (int k = 0; k < 2; ++k) {  // list 0: even T, list 1: odd T
+        rc = smh_feat::launch_features_rag(ctx, d_S, d_harm, d_perc, d_clips, t.at<const int>(o_list[k]), (int)list[k].size(), max_T[k],
+                                           k == 0, W > 0 ? W : 1, shift > 0 ? shift : 1, d_fv, d_patches, st);
+        if (rc) return rc;
+    }
     if (!list[2].empty()) {
         const FeatPlan fp = smh_feat::feat_plan(ctx, 1);
-        const unsigned gw = (unsigned)(8 * ((2 * (long long)it_walk.size() + 7) / 8));
+        const unsigned gw = (unsigned)(8 * ((2 * (long long)n_walk + 7) / 8));
         if (fp.pend <= 2)
             hipLaunchKernelGGL(rag_walk_kernel<2>, dim3(gw), dim3(64 * fp.nseg), 0, st, fp, d_S, d_harm, d_perc, g.K, g.rows, d_fv, d_keys,
-                               d_clips, items_at(o_walk), (int)it_walk.size());
+                               d_clips, t.at<const Item>(o_walk), n_walk);
         else
             hipLaunchKernelGGL(rag_walk_kernel<4>, dim3(gw), dim3(64 * fp.nseg), 0, st, fp, d_S, d_harm, d_perc, g.K, g.rows, d_fv, d_keys,
-                               d_clips, items_at(o_walk), (int)it_walk.size());
+                               d_clips, t.at<const Item>(o_walk), n_walk);
         rc = smh::launch_status("rag_walk_kernel");
         if (rc) return rc;
         if (d_patches) {
             const int n_rows = (int)list[2].size() * 2 * g.rows;
             hipLaunchKernelGGL(rag_stats_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, st, (const float *)d_fv, (const int *)d_keys,
-                               ctx->cfg.log_db, g.rows, d_clips, list_at(o_l2), n_rows, d_stats);
+                               ctx->cfg.log_db, g.rows, d_clips, t.at<const int>(o_list[2]), n_rows, d_stats);
             rc = smh::launch_status("rag_stats_kernel");
             if (rc) return rc;
         }
         const size_t lds = sizeof(float) * (size_t)2 * g.rows * (kFinalFrames + 1);
         SMH_CHECK_HIP(hipFuncSetAttribute((const void *)rag_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const unsigned gf = (unsigned)(8 * (((long long)it_final.size() + 7) / 8));
+        const unsigned gf = (unsigned)(8 * (((long long)n_final + 7) / 8));
         hipLaunchKernelGGL(rag_final_kernel, dim3(gf), dim3(512), lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows, W > 0 ? W : 1,
-                           shift > 0 ? shift : 1, d_patches, (const float4 *)d_stats, d_clips, items_at(o_final), (int)it_final.size());
+                           shift > 0 ? shift : 1, d_patches, (const float4 *)d_stats, d_clips, t.at<const Item>(o_final), n_final);
         rc = smh::launch_status("rag_final_kernel");
         if (rc) return rc;
     }
@@ -510,37 +455,130 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
 int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip> &hc, int W, int shift, float *d_fv, float *d_patches,
             void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st) {
     if (hc.empty()) return SMH_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return smh::set_error(SMH_E_INVALID, "the ragged front end uploads its tables from a staging buffer: it cannot be captured in a graph");
     RagGeom g;
     g.K = ctx->K, g.rows = ctx->feat_rows;
     g.stft_frames = smh_stft::rag_frames(ctx, stft_aligned8);
     g.med_frames = smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, nullptr);
     SMH_REQUIRE(g.med_frames > 0, "ragged front end: no median kernel for this context");
+    return smh_rag::run_sub_batches(
+        hc.size(), kFixedBytes, work_bytes, st, [&](size_t b) { return clip_bytes(g, hc[b]); }, [&](size_t b0, size_t nb) {
+            return run_sub_batch(ctx, g, d_audio, hc.data() + b0, (int)nb, W, shift, d_fv, d_patches, (char *)d_work, work_bytes,
+                                 stft_aligned8, st);
+        });
+}
+
+}  // namespace
+
+namespace smh_rag {
+
+// ---- the planner (smh_rag.h) ------------------------------------------------------------------------------------------------
+int plan_layout(const smh_ctx *ctx, const char *who, const long long *off, const int *len, int B, int W, int shift, bool patches,
+                int fv_rows, Layout &p) {
+    p.T.assign(B, 0), p.nP.assign(B, 0), p.fv_off.assign(B + 1, 0), p.patch_off.assign(B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        SMH_REQUIRE(off[b] >= 0 && len[b] >= 0, "%s: clip %d has a negative offset or length", who, b);
+        const int T = smh_num_frames(len[b], ctx->cfg.n_fft, ctx->cfg.hop);
+        SMH_REQUIRE(T >= 1, "%s: clip %d of %d samples is shorter than n_fft=%d", who, b, len[b], ctx->cfg.n_fft);
+        p.T[b] = T;
+        p.nP[b] = patches ? smh_num_patches(smh_tiled_frames(T, W), W, shift) : 0;
+        p.fv_off[b + 1] = p.fv_off[b] + (long long)fv_rows * T;
+        p.patch_off[b + 1] = p.patch_off[b] + p.nP[b];
+    }
+    return SMH_OK;
+}
+
+void export_layout(const Layout &p, int B, long long *h_fv_off, long long *h_patch_off, int *h_T, int *h_nP) {
+    for (int b = 0; b <= B; ++b) {
+        if (h_fv_off) h_fv_off[b] = p.fv_off[b];
+        if (h_patch_off) h_patch_off[b] = p.patch_off[b];
+    }
+    for (int b = 0; b < B; ++b) {
+        if (h_T) h_T[b] = p.T[b];
+        if (h_nP) h_nP[b] = p.nP[b];
+    }
+}
+
+size_t work_size(int B, size_t single, size_t total) {
+    constexpr size_t kWorkCap = (size_t)8 << 30;
+    return B == 0 ? 0 : align_up(std::max(single, std::min(total, kWorkCap)), 256);
+}
+
+HostClip host_clip(const Layout &p, const long long *off, int b, int W, int cls) {
+    return {off[b], p.fv_off[b], p.patch_off[b], p.T[b], smh_tiled_frames(p.T[b], W > 0 ? W : 1), p.nP[b], cls};
+}
+
+size_t fill_clips(const HostClip *hc, int n, int K, bool patches, std::vector<Clip> &clips) {
+    clips.assign(n, Clip{});
+    size_t spec = 0;
+    for (int b = 0; b < n; ++b) {
+        const HostClip &h = hc[b];
+        Clip &c = clips[b];
+        c.audio_off = h.audio_off, c.fv_off = h.fv_off, c.patch_off = h.patch_off, c.spec_off = (long long)spec;
+        c.T = h.T, c.Ttiled = h.Ttiled, c.nP = patches ? h.nP : 0;
+        spec += align_up((size_t)K * h.T, 4);
+    }
+    return spec;
+}
+
+size_t Tables::add(const void *src, size_t bytes) {
+    const size_t o = blob_.size();
+    blob_.resize(align_up(o + bytes, 16), 0);
+    if (src && bytes) memcpy(blob_.data() + o, src, bytes);
+    return o;
+}
+
+size_t Tables::add_items(const HostClip *hc, int n, int frames, int cls, int *count) {
+    size_t k = 0;
+    for (int b = 0; b < n; ++b)
+        if (cls < 0 || hc[b].cls == cls) k += (size_t)(hc[b].T + frames - 1) / frames;
+    const size_t o = add(nullptr, k * sizeof(Item));
+    Item *it = reinterpret_cast<Item *>(blob_.data() + o);
+    for (int b = 0; b < n; ++b)
+        if (cls < 0 || hc[b].cls == cls)
+            for (int t = 0, i = 0; t < hc[b].T; t += frames, ++i) *it++ = {b, i};
+    *count = (int)k;
+    return o;
+}
+
+int Tables::upload(const smh_ctx *ctx, const char *who, char *d_work, size_t work_bytes, size_t behind, hipStream_t st) {
+    d_ = d_work;
+    const size_t need = align_up(blob_.size(), 256) + behind;
+    if (need > work_bytes) return smh::set_error(SMH_E_WORKSPACE, "%s: workspace %zu < %zu needed by a single clip", who, work_bytes, need);
+    return stage_upload(ctx, blob_.data(), blob_.size(), d_work, st);
+}
+
+int run_sub_batches(size_t n, size_t fixed, size_t work_bytes, hipStream_t st,
+                    const std::function<size_t(size_t)> &bytes, const std::function<int(size_t, size_t)> &run) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return smh::set_error(SMH_E_INVALID, "the ragged front end uploads its tables from a staging buffer: it cannot be captured in a graph");
     size_t b0 = 0;
-    while (b0 < hc.size()) {
-        size_t need = kFixedBytes, b1 = b0;
-        while (b1 < hc.size()) {
-            const size_t cb = clip_bytes(g, hc[b1]);
+    while (b0 < n) {
+        size_t need = fixed, b1 = b0;
+        while (b1 < n) {
+            const size_t cb = bytes(b1);
             if (b1 > b0 && need + cb > work_bytes) break;
             need += cb;
             ++b1;
         }
-        if (need > work_bytes)
-            return smh::set_error(SMH_E_WORKSPACE, "ragged front end: workspace %zu < %zu needed by a single clip", work_bytes, need);
-        int rc = run_sub_batch(ctx, g, d_audio, hc.data() + b0, (int)(b1 - b0), W, shift, d_fv, d_patches, (char *)d_work, stft_aligned8, st);
+        int rc = run(b0, b1 - b0);
         if (rc) return rc;
         b0 = b1;
     }
     return SMH_OK;
 }
 
-constexpr size_t kRagWorkCap = (size_t)8 << 30;  // what smh_frontend_ragged_sizes asks for at most (a larger batch runs in sub-batches)
-
-}  // namespace
-
-namespace smh_rag {
+int run_alone(const Layout &p, int B, int W, int shift, int fv_rows, float *d_fv, float *d_patches, const std::function<bool(int)> &taken,
+              const std::function<int(int, int, int, float *, float *)> &alone) {
+    const size_t prow = (size_t)(W > 0 ? W : 0) * fv_rows;
+    for (int b = 0; b < B; ++b) {
+        if (taken(b)) continue;
+        float *pt = d_patches && p.nP[b] > 0 ? d_patches + (size_t)p.patch_off[b] * prow : nullptr;
+        int rc = alone(b, pt ? W : 0, pt ? shift : 0, d_fv + p.fv_off[b], pt);
+        if (rc < 0) return rc;
+    }
+    return SMH_OK;
+}
 
 // smh_frontend_f32's route for B equal clips beyond the LDS image: the streaming kernels above (returns 1 if it ran, 0 if this
 // context or shape has no ragged kernels, < 0 on error)
@@ -567,10 +605,6 @@ int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, in
     return rc ? rc : 1;
 }
 
-int upload_tables(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst, hipStream_t st) {
-    return stage_upload(ctx, src, bytes, d_dst, st);
-}
-
 int feature_route(const smh_ctx *ctx, int T) {
     if (smh_features_blocked_ok(ctx, T, 0)) {
         if (!smh_median::blocked_harm_ok(ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc)) return 3;
@@ -589,26 +623,8 @@ extern "C" int smh_internal_frontend_route(const smh_ctx *ctx, int T) {
 
 // ---- the C ABI -------------------------------------------------------------------------------------------------------------
 namespace {
-struct RaggedPlan {
-    std::vector<int> T, nP;
-    std::vector<long long> fv_off, patch_off;  // floats / patches in front of clip b
-};
-int plan_ragged(const smh_ctx *ctx, const long long *off, const int *len, int B, int W, int shift, bool patches, RaggedPlan &p) {
-    p.T.assign(B, 0), p.nP.assign(B, 0), p.fv_off.assign(B + 1, 0), p.patch_off.assign(B + 1, 0);
-    const int rows2 = 2 * ctx->feat_rows;
-    for (int b = 0; b < B; ++b) {
-        SMH_REQUIRE(off[b] >= 0 && len[b] >= 0, "ragged: clip %d has a negative offset or length", b);
-        const int T = smh_num_frames(len[b], ctx->cfg.n_fft, ctx->cfg.hop);
-        SMH_REQUIRE(T >= 1, "ragged: clip %d of %d samples is shorter than n_fft=%d", b, len[b], ctx->cfg.n_fft);
-        p.T[b] = T;
-        p.nP[b] = patches ? smh_num_patches(smh_tiled_frames(T, W), W, shift) : 0;
-        p.fv_off[b + 1] = p.fv_off[b] + (long long)rows2 * T;
-        p.patch_off[b + 1] = p.patch_off[b] + p.nP[b];
-    }
-    return SMH_OK;
-}
 // which clips the ragged kernels take (cls 0 / 1 / 2) and which go through smh_frontend_f32 alone (-1)
-void classify(const smh_ctx *ctx, const float *d_audio, const long long *off, const RaggedPlan &p, int B, std::vector<int> &cls) {
+void classify(const smh_ctx *ctx, const float *d_audio, const long long *off, const Layout &p, int B, std::vector<int> &cls) {
     cls.assign(B, -1);
     if (!rag_context_ok(ctx)) return;
     // the specialised STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when it is
@@ -629,20 +645,13 @@ extern "C" int smh_frontend_ragged_sizes(const smh_ctx *ctx, const long long *h_
                                          size_t *work_bytes) {
     SMH_REQUIRE(ctx && (B == 0 || (h_offsets && h_lengths)) && B >= 0, "smh_frontend_ragged_sizes: bad argument");
     SMH_REQUIRE(W <= 0 || shift >= 1, "smh_frontend_ragged_sizes: bad patch geometry W=%d shift=%d", W, shift);
-    RaggedPlan p;
-    int rc = plan_ragged(ctx, h_offsets, h_lengths, B, W, shift, W > 0, p);
+    Layout p;
+    int rc = smh_rag::plan_layout(ctx, "ragged", h_offsets, h_lengths, B, W, shift, W > 0, 2 * ctx->feat_rows, p);
     if (rc) return rc;
-    for (int b = 0; b <= B; ++b) {
-        if (h_fv_off) h_fv_off[b] = p.fv_off[b];
-        if (h_patch_off) h_patch_off[b] = p.patch_off[b];
-    }
-    for (int b = 0; b < B; ++b) {
-        if (h_T) h_T[b] = p.T[b];
-        if (h_nP) h_nP[b] = p.nP[b];
-    }
+    smh_rag::export_layout(p, B, h_fv_off, h_patch_off, h_T, h_nP);
     if (work_bytes) {
-        // every clip the ragged kernels take, at once -- up to kRagWorkCap, beyond that the call runs in sub-batches -- and never less
-        // than the largest single clip needs (alone in a sub-batch, or through smh_frontend_f32)
+        // every clip the ragged kernels take at once, and never less than the largest single clip needs (alone in a sub-batch, or
+        // through smh_frontend_f32): smh_rag::work_size
         std::vector<int> cls;
         classify(ctx, nullptr, h_offsets, p, B, cls);  // (alignment is the call's business: sized as if every clip qualified)
         RagGeom g;
@@ -658,7 +667,7 @@ extern "C" int smh_frontend_ragged_sizes(const smh_ctx *ctx, const long long *h_
             total += cb;
             single = std::max(single, cb + kFixedBytes);
         }
-        *work_bytes = B == 0 ? 0 : align_up(std::max(single, std::min(total, kRagWorkCap)), 256);
+        *work_bytes = smh_rag::work_size(B, single, total);
     }
     return SMH_OK;
 }
@@ -670,31 +679,22 @@ extern "C" int smh_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio,
     const bool patches = d_patches != nullptr;
     SMH_REQUIRE(!patches || (W >= 1 && shift >= 1), "smh_frontend_ragged_f32: bad patch geometry W=%d shift=%d", W, shift);
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0, "smh_frontend_ragged_f32: the workspace must start on a 16-byte boundary");
-    RaggedPlan p;
-    int rc = plan_ragged(ctx, h_offsets, h_lengths, B, W, shift, patches, p);
+    Layout p;
+    int rc = smh_rag::plan_layout(ctx, "ragged", h_offsets, h_lengths, B, W, shift, patches, 2 * ctx->feat_rows, p);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     std::vector<int> cls;
     classify(ctx, d_audio, h_offsets, p, B, cls);
     std::vector<HostClip> hc;
     hc.reserve(B);
-    for (int b = 0; b < B; ++b) {
-        if (cls[b] < 0) continue;
-        HostClip h;
-        h.audio_off = h_offsets[b], h.fv_off = p.fv_off[b], h.patch_off = p.patch_off[b];
-        h.T = p.T[b], h.Ttiled = smh_tiled_frames(p.T[b], W > 0 ? W : 1), h.nP = p.nP[b], h.cls = cls[b];
-        hc.push_back(h);
-    }
+    for (int b = 0; b < B; ++b)
+        if (cls[b] >= 0) hc.push_back(smh_rag::host_clip(p, h_offsets, b, W, cls[b]));
     rc = run_rag(ctx, d_audio, hc, W, shift, d_fv, d_patches, d_work, work_bytes, true, st);
     if (rc) return rc;
     // the clips no ragged kernel covers, one by one on the same stream (the workspace is free again in stream order)
-    const size_t prow = (size_t)(W > 0 ? W : 0) * 2 * ctx->feat_rows;
-    for (int b = 0; b < B; ++b) {
-        if (cls[b] >= 0) continue;
-        float *pt = patches && p.nP[b] > 0 ? d_patches + (size_t)p.patch_off[b] * prow : nullptr;
-        rc = smh_frontend_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], pt ? W : 0, pt ? shift : 0, d_fv + p.fv_off[b], pt, d_work,
-                              work_bytes, nullptr, nullptr, nullptr, stream);
-        if (rc < 0) return rc;
-    }
-    return SMH_OK;
+    return smh_rag::run_alone(p, B, W, shift, 2 * ctx->feat_rows, d_fv, d_patches, [&](int b) { return cls[b] >= 0; },
+                              [&](int b, int w, int sh, float *fv, float *pt) {
+                                  return smh_frontend_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], w, sh, fv, pt, d_work, work_bytes,
+                                                          nullptr, nullptr, nullptr, stream);
+                              });
 }

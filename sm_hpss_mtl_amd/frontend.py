@@ -116,6 +116,17 @@ def _out(out, key, shape, dtype, dev):
     return t
 
 
+def _maxkeys(out, n, what, dev):
+    """The int32 max-key scratch of a features call: out['maxkeys'] if the caller keeps one (at least n entries; `what` names n in
+    the error text), else a fresh tensor."""
+    keys = (out or {}).get("maxkeys")
+    if keys is None:
+        return torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    if not (keys.is_cuda and keys.dtype == torch.int32 and keys.numel() >= n and keys.is_contiguous()):
+        raise ValueError("out['maxkeys'] must be a contiguous int32 device tensor with at least %s = %d entries" % (what, n))
+    return keys
+
+
 def _f32c(t, name):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise TypeError("%s must be a CUDA/HIP torch tensor" % name)
@@ -257,11 +268,7 @@ class Frontend:
         if W is not None:
             nP = self.num_patches(T, W, shift)
             patches = _out(out, "patches", (B * nP, W, 2 * self.rows), torch.float32, dev)
-        keys = (out or {}).get("maxkeys")
-        if keys is None:
-            keys = torch.empty(2 * max(B, 1), dtype=torch.int32, device=dev)
-        elif not (keys.is_cuda and keys.dtype == torch.int32 and keys.numel() >= 2 * B and keys.is_contiguous()):
-            raise ValueError("out['maxkeys'] must be a contiguous int32 device tensor with at least 2*B = %d entries" % (2 * B))
+        keys = _maxkeys(out, 2 * B, "2*B", dev)
         got = _lib.check(self.lib.smh_features_f32(self._h, _ptr(S), _ptr(harm), _ptr(perc), B, T, W or 0, shift or 0,
                                                    _ptr(fv), _ptr(patches) if nP else None, _ptr(keys), _stream()),
                          "smh_features_f32")
@@ -288,11 +295,7 @@ class Frontend:
         fv = _out(out, "fv", (B, 2 * self.rows, T), torch.float32, dev)
         x0p = _out(out, "x0p", (B * nP, 2, W, 32), torch.float32, dev)
         pt = _out(out, "patches", (B * nP, W, 2 * self.rows), torch.float32, dev) if patches else None
-        keys = (out or {}).get("maxkeys")
-        if keys is None:
-            keys = torch.empty(2 * max(B, 1), dtype=torch.int32, device=dev)
-        elif not (keys.is_cuda and keys.dtype == torch.int32 and keys.numel() >= 2 * B and keys.is_contiguous()):
-            raise ValueError("out['maxkeys'] must be a contiguous int32 device tensor with at least 2*B = %d entries" % (2 * B))
+        keys = _maxkeys(out, 2 * B, "2*B", dev)
         got = _lib.check(self.lib.smh_features_l0_f32(
             self._h, _ptr(S), _ptr(harm), _ptr(perc), int(harm_layout), B, T, W, shift, _ptr(fv), _ptr(pt),
             C.c_void_p(w0), _ptr(x0p), _ptr(keys), _stream()), "smh_features_l0_f32")
@@ -315,11 +318,7 @@ class Frontend:
         if W is not None:
             nP = self.num_patches(T, W, shift)
             patches = _out(out, "patches", (B * nP, W, self.rows), torch.float32, dev)
-        keys = (out or {}).get("maxkeys")
-        if keys is None:
-            keys = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
-        elif not (keys.is_cuda and keys.dtype == torch.int32 and keys.numel() >= B and keys.is_contiguous()):
-            raise ValueError("out['maxkeys'] must be a contiguous int32 device tensor with at least B = %d entries" % B)
+        keys = _maxkeys(out, B, "B", dev)
         got = _lib.check(self.lib.smh_plain_features_f32(self._h, _ptr(S), B, T, W or 0, shift or 0, _ptr(fv),
                                                          _ptr(patches) if nP else None, _ptr(keys), _stream()),
                          "smh_plain_features_f32")
@@ -331,8 +330,14 @@ class Frontend:
         """audio (B, n_samples) -> dict(fv=(B, 2*rows, T)[, patches=(B*nP, W, 2*rows)][, S, harm, perc]).
         `out` may carry preallocated 'fv' / 'patches' tensors (steady-state loops allocate nothing).
         A plain configuration (hpss=False) gives fv=(B, rows, T) and patches=(B*nP, W, rows); its only tap is S."""
-        if not self.cfg.hpss:
-            return self._run_plain(audio, W, shift, taps, out)
+        # what differs between the two front ends: the featuregram's rows, the workspace / entry pair and the taps
+        if self.cfg.hpss:
+            F, names = 2 * self.rows, ("S", "harm", "perc")
+            work_bytes, entry, label = self.lib.smh_frontend_workspace_bytes, self.lib.smh_frontend_f32, "smh_frontend_f32"
+        else:
+            F, names = self.rows, ("S",)
+            work_bytes, entry, label = (self.lib.smh_plain_frontend_workspace_bytes, self.lib.smh_plain_frontend_f32,
+                                        "smh_plain_frontend_f32")
         audio = _f32c(audio, "audio")
         B, N = audio.shape
         T = self.num_frames(N)
@@ -341,62 +346,25 @@ class Frontend:
         dev = audio.device
         out = {} if out is None else out
         fv = out.get("fv")
-        if fv is None or fv.shape != (B, 2 * self.rows, T):
-            fv = torch.empty((B, 2 * self.rows, T), dtype=torch.float32, device=dev)
+        if fv is None or fv.shape != (B, F, T):
+            fv = torch.empty((B, F, T), dtype=torch.float32, device=dev)
         patches, nP = None, 0
         if W is not None:
             nP = self.num_patches(T, W, shift)
             patches = out.get("patches")
-            if patches is None or patches.shape != (B * nP, W, 2 * self.rows):
-                patches = torch.empty((B * nP, W, 2 * self.rows), dtype=torch.float32, device=dev)
-        need = self.lib.smh_frontend_workspace_bytes(self._h, B, N)
+            if patches is None or patches.shape != (B * nP, W, F):
+                patches = torch.empty((B * nP, W, F), dtype=torch.float32, device=dev)
+        need = work_bytes(self._h, B, N)
         if self._work is None or self._work.numel() < need or self._work.device != dev:
-            self._work = torch.empty(need, dtype=torch.uint8, device=dev)
-        S = harm = perc = None
-        if taps:
-            S = torch.empty((B, self.K, T), dtype=torch.float32, device=dev)
-            harm, perc = torch.empty_like(S), torch.empty_like(S)
-        got = _lib.check(self.lib.smh_frontend_f32(
-            self._h, _ptr(audio), B, N, W or 0, shift or 0, _ptr(fv), _ptr(patches) if nP else None,
-            _ptr(self._work), self._work.numel(), _ptr(S), _ptr(harm), _ptr(perc), _stream()), "smh_frontend_f32")
+            self._work = torch.empty(need if self.cfg.hpss else max(need, 1), dtype=torch.uint8, device=dev)
+        tap = {k: torch.empty((B, self.K, T), dtype=torch.float32, device=dev) for k in names} if taps else {}
+        got = _lib.check(entry(self._h, _ptr(audio), B, N, W or 0, shift or 0, _ptr(fv), _ptr(patches) if nP else None,
+                               _ptr(self._work), self._work.numel(), *(_ptr(tap.get(k)) for k in names), _stream()), label)
         assert got == nP, (got, nP)
         res = {"fv": fv, "n_patches": nP}
         if W is not None:
             res["patches"] = patches
-        if taps:
-            res.update(S=S, harm=harm, perc=perc)
-        return res
-
-    def _run_plain(self, audio, W, shift, taps, out):
-        audio = _f32c(audio, "audio")
-        B, N = audio.shape
-        T = self.num_frames(N)
-        if T < 1:
-            raise ValueError("clip of %d samples is shorter than n_fft=%d" % (N, self.cfg.n_fft))
-        dev = audio.device
-        out = {} if out is None else out
-        fv = out.get("fv")
-        if fv is None or fv.shape != (B, self.rows, T):
-            fv = torch.empty((B, self.rows, T), dtype=torch.float32, device=dev)
-        patches, nP = None, 0
-        if W is not None:
-            nP = self.num_patches(T, W, shift)
-            patches = out.get("patches")
-            if patches is None or patches.shape != (B * nP, W, self.rows):
-                patches = torch.empty((B * nP, W, self.rows), dtype=torch.float32, device=dev)
-        need = self.lib.smh_plain_frontend_workspace_bytes(self._h, B, N)
-        if self._work is None or self._work.numel() < need or self._work.device != dev:
-            self._work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        S = torch.empty((B, self.K, T), dtype=torch.float32, device=dev) if taps else None
-        got = _lib.check(self.lib.smh_plain_frontend_f32(
-            self._h, _ptr(audio), B, N, W or 0, shift or 0, _ptr(fv), _ptr(patches) if nP else None,
-            _ptr(self._work), self._work.numel(), _ptr(S), _stream()), "smh_plain_frontend_f32")
-        assert got == nP, (got, nP)
-        res = {"fv": fv, "n_patches": nP}
-        if W is not None:
-            res["patches"] = patches
-        if taps:
-            res["S"] = S
+        res.update(tap)
         return res
 
     # ---- ragged batches ----
@@ -436,10 +404,9 @@ class Frontend:
         hT, hnP = (C.c_int * B)(), (C.c_int * B)()
         work = C.c_size_t()
         # a plain configuration (hpss=False) takes the plain pair of entries: same contract, (rows, T_b) and (nP_b, W, rows) per clip
-        sizes, ragged = ((self.lib.smh_frontend_ragged_sizes, self.lib.smh_frontend_ragged_f32) if self.cfg.hpss else
-                         (self.lib.smh_plain_frontend_ragged_sizes, self.lib.smh_plain_frontend_ragged_f32))
-        _lib.check(sizes(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP, C.byref(work)),
-                   "smh_frontend_ragged_sizes")
+        stem = "smh_frontend_ragged" if self.cfg.hpss else "smh_plain_frontend_ragged"
+        sizes, ragged = getattr(self.lib, stem + "_sizes"), getattr(self.lib, stem + "_f32")
+        _lib.check(sizes(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP, C.byref(work)), stem + "_sizes")
         F = (2 if self.cfg.hpss else 1) * self.rows
         fv = torch.empty(max(int(fv_off[B]), 1), dtype=torch.float32, device=dev)
         patches = torch.empty((max(int(p_off[B]), 1), W or 1, F), dtype=torch.float32, device=dev) if W else None
@@ -447,7 +414,7 @@ class Frontend:
             self._work = torch.empty(max(work.value, 1), dtype=torch.uint8, device=dev)
         _lib.check(ragged(self._h, _ptr(audio), h_off, h_len, B, W or 0, shift or 0, _ptr(fv),
                           _ptr(patches) if (W and int(p_off[B]) > 0) else None, _ptr(self._work), self._work.numel(), _stream()),
-                   "smh_frontend_ragged_f32")
+                   stem + "_f32")
         res = {"fv": [fv[int(fv_off[b]):int(fv_off[b + 1])].view(F, int(hT[b])) for b in range(B)],
                "T": [int(hT[b]) for b in range(B)], "n_patches": [int(hnP[b]) for b in range(B)]}
         if W:
