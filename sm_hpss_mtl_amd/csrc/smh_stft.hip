@@ -556,7 +556,19 @@ void generic_args(const smh_ctx *ctx, StftArgs &a) {
     }
 }
 constexpr int kRagFramesGeneric = 16;
+// The kernel an equal-length call runs: 2 the f64 one, 1 the specialised 8 x 25 one, 0 the generic one.
+// n_fft = 400 with 8-byte aligned frames takes the specialised kernel (SMH_STFT_GENERIC=1 forces the generic one); an odd clip
+// length only matters for where the NEXT clip starts, so a single clip keeps it.
+int stft_route(const smh_ctx *ctx, const float *d_audio, int B, int n_samples) {
+    if (ctx->stft_f64) return 2;
+    return stft400_ok(ctx) && ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0 ? 1 : 0;
+}
 }  // namespace
+
+// tests: the route smh_stft_mag_f32 takes for this call (stft_route above), -1 for a null context
+extern "C" int smh_internal_stft_route(const smh_ctx *ctx, const float *d_audio, int B, int n_samples) {
+    return ctx ? stft_route(ctx, d_audio, B, n_samples) : -1;
+}
 
 namespace smh_stft {
 int rag_frames(const smh_ctx *ctx, bool aligned8) {
@@ -600,10 +612,9 @@ extern "C" int smh_stft_mag_f32(const smh_ctx *ctx, const float *d_audio, int B,
     const int T = smh_num_frames(n_samples, ctx->cfg.n_fft, ctx->cfg.hop);
     SMH_REQUIRE(T >= 1, "smh_stft_mag_f32: clip of %d samples is shorter than n_fft=%d", n_samples, ctx->cfg.n_fft);
     if (B == 0) return SMH_OK;
-    if (ctx->stft_f64) return smh_stft::launch_f64(ctx, d_audio, B, n_samples, T, d_S, (hipStream_t)stream);
-    // n_fft = 400 with 8-byte aligned frames: the specialised 8 x 25 kernel (SMH_STFT_GENERIC=1 forces the generic one)
-    // (an odd clip length only matters for where the NEXT clip starts: a single clip keeps the specialised kernel)
-    if (stft400_ok(ctx) && ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0) {
+    const int route = stft_route(ctx, d_audio, B, n_samples);
+    if (route == 2) return smh_stft::launch_f64(ctx, d_audio, B, n_samples, T, d_S, (hipStream_t)stream);
+    if (route == 1) {
         // frames per workgroup: <= 20 (37 KB of LDS, 128 VGPRs: FOUR 256-thread workgroups per CU), splitting T evenly (98 -> 5 x 20,
         // the last with 18).  25 frames (45 KB: three per CU) measured 69-71 us, 20 frames 64.6; 16 and fewer leave half of phase
         // 2's threads idle (8 items per frame) and are slower again.  tools/gpu/r2_stft_tune.sh sweeps it.
