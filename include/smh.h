@@ -370,7 +370,10 @@ int smh_model_eval_losses_f32(const smh_model *m, const float *d_out, const floa
  * d_out (nP, out_dim) as smh_model_forward_f32 writes it, to the same f32 tolerance.  Nothing of size nP x W x n_feat is built: the
  * first layer (a 1x1 convolution) is evaluated once per FRAME into d_work ((2, Tc, 32) float32 =
  * smh_model_dense_workspace_bytes) and every patch is read as a window of it.  Needs Tc >= W (shorter batches are tiled by
- * get_feature_patches: build the patches and call smh_model_forward_f32), n_feat a multiple of 8, block_variant 0. */
+ * get_feature_patches: build the patches and call smh_model_forward_f32), n_feat a multiple of 8, block_variant 0.
+ * On return (once the stream has run) d_work holds the per-frame layer-0 partials (2, Tc, 32) float32, laid out
+ * [half][frame][channel]: half h is the product of rows [h * n_feat / 2, + n_feat / 2) of d_fv with the same rows of the layer-0
+ * kernel, WITHOUT the layer-0 bias.  Both dense entries leave the same bits there. */
 size_t smh_model_dense_workspace_bytes(const smh_model *m, int Tc);
 int smh_model_forward_dense_f32(const smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes,
                                 float *d_out, void *stream);
@@ -388,6 +391,14 @@ int smh_model_forward_bf16_ex(smh_model *m, const float *d_x, int N, float *d_ou
 /* The same from the layer-0 partials of smh_features_l0_f32 (the bench fast path; layer 0 is then exact f32): d_x0p
  * (N, 2, patch_size, 32) float32 as for smh_model_forward_x0_f32. */
 int smh_model_forward_x0_bf16(smh_model *m, const float *d_x0p, int N, float *d_out, int split, void *stream);
+/* Dense file-level inference on split bf16 operands (always split = 1; the B3_MTL heads and block_variant 0 only, as
+ * smh_model_forward_bf16): the arguments, the return value (the number of patches >= 0, or an error), the checks and the workspace
+ * (smh_model_dense_workspace_bytes) of smh_model_forward_dense_f32.  Layer 0 stays exact f32: the same per-frame pass writes the
+ * same partials (2, Tc, 32), [half][frame][channel] without the layer-0 bias, into d_work, and the split-operand network reads
+ * every patch as a window of them -- bit for bit what smh_model_forward_x0_bf16 computes on the same windows gathered into
+ * (nP, 2, patch_size, 32).  The split operand cache follows the weight version as in smh_model_forward_bf16. */
+int smh_model_forward_dense_bf16(smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes, float *d_out,
+                                 void *stream);
 int smh_model_get_weights(const smh_model *m, float *h_flat, size_t n, void *stream);
 
 /* ---- a13: Conv2D MTL baselines, inference forward (lib/proposed_architectures.py:425-511 Doukhan, :516-588

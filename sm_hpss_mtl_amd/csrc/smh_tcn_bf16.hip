@@ -699,17 +699,23 @@ b3mtl_forward_bf16s_kernel(TcnArgs a, PackInfo pi, Offsets off, const float *__r
     // ---- initial Conv1D(32, 1): into the residual registers and the split images of buffer 0 --------------------------------------
     if (a.from_x0) {
         // layer 0 was computed by the feature kernel in exact f32 (smh_features_l0_f32): X holds its two per-half partials
-        // (N, 2, T, 32); sum them, add the bias (the f32 kernel's prologue, smh_tcn.hip)
+        // (N, 2, T, 32); sum them, add the bias (the f32 kernel's prologue, smh_tcn.hip).  Dense form (a.x0_shift > 0,
+        // smh_model_forward_dense_bf16; inference only): X is (2, x0_T, 32), the partials of every frame of a featuregram, and patch n
+        // the window of T frames starting at min(n * x0_shift, x0_T - T) -- rows of 128 bytes, so every window is 16-byte aligned
         const float *bias0 = flat + off.w0_b;
         const f32x4 bl = *reinterpret_cast<const f32x4 *>(bias0 + 4 * q), bh = *reinterpret_cast<const f32x4 *>(bias0 + 16 + 4 * q);
+        const bool win = !TRAIN && a.x0_shift > 0;
+        const size_t half = (size_t)(win ? a.x0_T : T) * C;  // floats between the two halves of a frame
         f32x4 pa[kMaxTilesS][4];
 #pragma unroll
         for (int i = 0; i < kMaxTilesS; ++i) {  // all loads first
-            const float *p0 = X + ((((size_t)(n0 + ti.g[i]) * 2) * T + ti.t[i]) * C + 4 * q);
+            const int n = n0 + ti.g[i];
+            const size_t first = win ? (size_t)min(n * a.x0_shift, a.x0_T - T) : (size_t)n * 2 * T;  // the patch's first frame row
+            const float *p0 = X + ((first + ti.t[i]) * C + 4 * q);
             const bool on = i < ti.n;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                pa[i][e] = on ? *reinterpret_cast<const f32x4 *>(p0 + (size_t)(e >> 1) * T * C + 16 * (e & 1)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                pa[i][e] = on ? *reinterpret_cast<const f32x4 *>(p0 + (size_t)(e >> 1) * half + 16 * (e & 1)) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int i = 0; i < kMaxTilesS; ++i) {
@@ -948,10 +954,15 @@ static int plan_bf16(const smh_model *m, const PackInfo &pi, int N, int split, i
     return SMH_OK;
 }
 
+// x0_shift > 0 (from_x0, split operands, inference): d_x holds the per-frame partials (2, x0_T, 32) and patch n is the window of
+// patch_size frames starting at min(n * x0_shift, x0_T - patch_size) (TcnArgs::x0_shift; smh_model_forward_dense_bf16)
 static int forward_bf16(smh_model *m, const float *d_x, int N, float *d_out, int split, int from_x0, void *stream,
-                        const TrainIO *tio = nullptr) {
+                        const TrainIO *tio = nullptr, int x0_shift = 0, int x0_T = 0) {
     SMH_REQUIRE(m && d_x && (d_out || tio), "smh_model_forward_bf16: null argument");
     SMH_REQUIRE(!tio || split, "smh_model_forward_bf16: the training forward exists for split operands only");
+    SMH_REQUIRE(x0_shift == 0 || (from_x0 && split && !tio && x0_shift > 0 && x0_T >= m->cfg.patch_size),
+                "smh_model_forward_bf16: windows of per-frame partials (x0_shift=%d, x0_T=%d) are read by the split-operand inference "
+                "forward from layer-0 partials only, never by the training forward", x0_shift, x0_T);
     SMH_REQUIRE(N >= 0, "smh_model_forward_bf16: N=%d", N);
     int rc = model_bf16_ok(m);
     if (rc) return rc;
@@ -962,6 +973,7 @@ static int forward_bf16(smh_model *m, const float *d_x, int N, float *d_out, int
     SplitPlan sp{};
     rc = plan_bf16(m, pi, N, split, from_x0, &a, &lds, &sp);
     if (rc) return rc;
+    a.x0_shift = x0_shift, a.x0_T = x0_T;
     hipStream_t st = (hipStream_t)stream;
     const Offsets off = offsets(m);
     if (!m->d_bf16) SMH_CHECK_HIP(hipMalloc(&m->d_bf16, 2 * pi.total * 16));  // hi operands, then lo operands
@@ -1034,4 +1046,36 @@ extern "C" int smh_model_forward_bf16(smh_model *m, const float *d_x, int N, flo
 
 extern "C" int smh_model_forward_x0_bf16(smh_model *m, const float *d_x0p, int N, float *d_out, int split, void *stream) {
     return forward_bf16(m, d_x0p, N, d_out, split, 1, stream);
+}
+
+// Dense file-level inference on split bf16 operands: smh_model_forward_dense_f32's checks and its l0_frames_kernel pass (layer 0
+// stays exact f32, once per frame, into d_work), then the split-operand kernel reads every patch as a window of d_work.
+extern "C" int smh_model_forward_dense_bf16(smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes,
+                                            float *d_out, void *stream) {
+    SMH_REQUIRE(m && d_fv && d_work && d_out, "smh_model_forward_dense_bf16: null argument");
+    int rc = model_bf16_ok(m);
+    if (rc) return rc;
+    SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_fv) % 16) == 0 &&
+                    (reinterpret_cast<uintptr_t>(d_out) % 4) == 0,
+                "smh_model_forward_dense_bf16: d_fv and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries");
+    const int W = m->cfg.patch_size, F = m->cfg.n_feat;
+    SMH_REQUIRE(F % 8 == 0, "smh_model_forward_dense_bf16: n_feat=%d must be a multiple of 8 (two halves of whole k steps)", F);
+    SMH_REQUIRE(shift >= 1 && Tc >= W, "smh_model_forward_dense_bf16: needs shift >= 1 and at least patch_size=%d frames (Tc=%d, shift=%d); "
+                "shorter chunks are tiled by get_feature_patches and take smh_model_forward_bf16", W, Tc, shift);
+    SMH_REQUIRE(work_bytes >= smh_model_dense_workspace_bytes(m, Tc), "smh_model_forward_dense_bf16: workspace of %zu bytes, need %zu",
+                work_bytes, smh_model_dense_workspace_bytes(m, Tc));
+    const int nP = smh_num_patches(Tc, W, shift);
+    if (nP <= 0) return 0;
+    {  // the plan's refusals before anything is launched
+        TcnArgs a;
+        size_t lds;
+        SplitPlan sp{};
+        rc = plan_bf16(m, pack_info(m), nP, 1, 1, &a, &lds, &sp);
+        if (rc) return rc;
+    }
+    float *x0 = static_cast<float *>(d_work);
+    rc = launch_l0_frames(d_fv, smh_model_w0_ptr(m), x0, F / 2, Tc, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = forward_bf16(m, x0, nP, d_out, 1, 1, stream, nullptr, shift, Tc);
+    return rc ? rc : nP;
 }

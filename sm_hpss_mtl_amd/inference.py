@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from .frontend import Frontend, FrontendConfig, _ptr, _stream
 from .host import HEADS_SINGLE
+from .persistence import HeadModel
 
 _fe = None
 
@@ -91,12 +92,31 @@ def smooth_labels(Predictions, PtdLabels, win_size, smooth_type="prediction"):
     return sm, lab
 
 
-def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000):
+def patch_probabilities(fv, model, W, W_shift=1, output=None, batch_frames=10000, dtype="f32"):
     """fv (2R, nFrames) HarmPerc featuregram of one file -> 1-D float32 numpy track of the chosen head's
     probability, one value per patch, batches concatenated (DAFx12...:612-676).  model: B3MTL, cascaded, or FusionMTL (per-branch
     n_feat = R; the file-wise predict of Intermediate_Fusion_Results.py:441-590).  A late_fusion.LateFusion ensemble (per-model n_feat
     = R) has the one output '3C' and returns its blended (nP, n_classes) track instead of a 1-D one.  So does a model.SingleTaskTCN
-    (output 'dense'), whose fv is ONE (n_feat, nFrames) featuregram such as LogMelSpec: no halves, the rows are standardised once."""
+    (output 'dense'), whose fv is ONE (n_feat, nFrames) featuregram such as LogMelSpec: no halves, the rows are standardised once.
+    output: the head's name; None = 'M'.  model may also be the driver's single-output sub-model (persistence.HeadModel, what
+    `Train_Params['model']` holds at predict time, :518-523): the model it was cut from runs and that head's column comes back --
+    the same track as (full model, output=name); output then defaults to the sub-model's own name and may name no other.
+    dtype: "f32", or "bf16" = the network on split bf16 operands (B3MTL with the keras-tcn 2.3.x block only; layer 0 of the dense
+    branch stays exact f32) -- `forward_dense(..., dtype=dtype)` / `forward_device(x, dtype=dtype)`."""
+    if isinstance(model, HeadModel):
+        if output not in (None, model.name):
+            raise ValueError("output %r is not the output %r of this single-output sub-model" % (output, model.name))
+        model, output = model.model, model.name
+    elif output is None:
+        output = "M"
+    if dtype not in ("f32", "bf16"):
+        raise ValueError("dtype must be 'f32' or 'bf16' (split bf16 operands), got %r" % (dtype,))
+    if dtype == "bf16":  # refused here, before the featuregram is touched
+        if not hasattr(model, "_dense_entry"):
+            raise ValueError("dtype='bf16': B3_MTL with the keras-tcn 2.3.x block is the only model with a bf16 path; %s has the f32 "
+                             "forward only" % type(model).__name__)
+        model._dense_entry(dtype)
+    kw = {} if dtype == "f32" else {"dtype": dtype}
     fe = _frontend()
     d = _dev(fv)
     single = getattr(model, "HEADS", 0) == HEADS_SINGLE  # one plain featuregram in, one output
@@ -130,16 +150,16 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
         e = min(s + batch_frames, T)
         chunk = d[:, s:e].contiguous()
         if dense and e - s > W:
-            # the same patches without building them (smh_model_forward_dense_f32): each half standardised over the batch as
+            # the same patches without building them (smh_model_forward_dense_f32 / _bf16): each half standardised over the batch as
             # get_feature_patches does (:647), layer 0 once per frame, every hop-W_shift patch a window of it
-            o = model.forward_dense(fe.standardize_rows(chunk), W_shift)
+            o = model.forward_dense(fe.standardize_rows(chunk), W_shift, **kw)
             if o.shape[0]:
                 preds.append(o[:, sel])
             continue
         if single:  # one input: the whole batch standardised row by row, hop-W_shift patches, time-major
             x = fe.extract_patches(fe.standardize_rows(chunk)[None], W, W_shift, time_major=True)
             if x.shape[0]:
-                preds.append(model.forward_device(x))
+                preds.append(model.forward_device(x, **kw))
             continue
         # get_feature_patches on the batch (:647): tile if short, standardise each half over the batch, hop-W_shift
         # patches; written time-major = the transposed TCN input of :660
@@ -148,7 +168,7 @@ def patch_probabilities(fv, model, W, W_shift=1, output="M", batch_frames=10000)
         if h.shape[0] == 0:
             continue
         x = [h, p] if fusion else torch.cat([h, p], dim=2)  # (the fusion model takes the halves as they are: no copy)
-        preds.append(model.forward_device(x)[:, sel])
+        preds.append(model.forward_device(x, **kw)[:, sel])
     if not preds:
         return np.zeros((0, model.out_dim) if late else (0,), np.float32)
     out = torch.cat(preds)

@@ -150,10 +150,16 @@ class LateFusion:
                       out, labels, heads)
         return out
 
-    def forward_dense(self, fv, shift=1, out=None, labels=None, heads=None):
+    def forward_dense(self, fv, shift=1, out=None, labels=None, heads=None, dtype="f32"):
         """Every hop-`shift` patch of a standardised H||P featuregram fv (2 * n_feat, Tc) through both models and the blend without
         building the patches (smh_late_fusion_forward_dense_f32): layer 0 of both models once per frame, every patch a window of it.
-        Returns (nP, n_classes), nP = tools.extract_patches' count for Tc frames.  Needs Tc >= patch_size and n_feat % 4 == 0."""
+        Returns (nP, n_classes), nP = tools.extract_patches' count for Tc frames.  Needs Tc >= patch_size and n_feat % 4 == 0.
+        dtype: "f32" only (B3_MTL is the only model with a bf16 path)."""
+        if dtype == "bf16":
+            raise ValueError("dtype='bf16': B3_MTL with the keras-tcn 2.3.x block is the only model with a bf16 path; the late-fusion "
+                             "ensemble has the f32 forward only")
+        if dtype != "f32":
+            raise ValueError("dtype must be 'f32' or 'bf16' (split bf16 operands), got %r" % (dtype,))
         fv = f32_cuda(fv, "forward_dense")
         if fv.dim() != 2 or fv.shape[0] != 2 * self.n_feat:
             raise ValueError("expected the H||P featuregram (%d, Tc), got %s" % (2 * self.n_feat, tuple(fv.shape)))

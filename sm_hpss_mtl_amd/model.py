@@ -113,6 +113,7 @@ class B3MTL(TcnTrainingMixin, HostModel):
 
     CLASS_NAME = "B3_MTL"
     _DENSE_ENTRY, _DENSE_WORKSPACE = "smh_model_forward_dense_f32", "smh_model_dense_workspace_bytes"
+    _DENSE_ENTRY_BF16 = "smh_model_forward_dense_bf16"  # B3_MTL alone: every other model refuses dtype="bf16" (`_dense_entry`)
 
     def __init__(self, n_feat=240, patch_size=68, n_classes=3, TR_STEPS=1, loss_weights=None, seed=None,
                  nb_filters=32, kernel_size=3, nb_stacks=3, n_dilations=8, tcn_block="2.3"):
@@ -221,11 +222,26 @@ class B3MTL(TcnTrainingMixin, HostModel):
     def _dense_workspace_args(self, Tc, shift):
         return (Tc,)
 
-    def forward_dense(self, fv, shift=1, out=None):
+    def _dense_entry(self, dtype):
+        """The C entry of forward_dense for `dtype`; the refusals that need no launch: an unknown dtype (`_forward`'s wording), and
+        "bf16" on anything but a B3_MTL with the keras-tcn 2.3.x block."""
+        if dtype == "f32":
+            return self._DENSE_ENTRY
+        if dtype != "bf16":
+            raise ValueError("dtype must be 'f32' or 'bf16' (split bf16 operands), got %r" % (dtype,))
+        if self.HEADS != HEADS_MTL or self.block_variant != 0:
+            raise ValueError("dtype='bf16': B3_MTL with the keras-tcn 2.3.x block is the only model with a bf16 path; %s%s has the f32 "
+                             "forward only" % (self.CLASS_NAME, "" if self.block_variant == 0 else " with the 2.8 block"))
+        return self._DENSE_ENTRY_BF16
+
+    def forward_dense(self, fv, shift=1, out=None, dtype="f32"):
         """Every hop-`shift` patch of a standardised featuregram batch fv (n_feat, Tc) through the network (dense file-level
         inference, DAFx12_Speech_Music_Detection_B3_MTL_v2.py:634-665) WITHOUT building the (nP, W, n_feat) patches: layer 0 once
         per frame, every patch a window of it (`smh_model_forward_dense_f32`).  Returns (nP, out_dim); nP = tools.extract_patches'
-        count for Tc frames.  Needs Tc >= patch_size; shorter batches are tiled by get_feature_patches and go through forward_device."""
+        count for Tc frames.  Needs Tc >= patch_size; shorter batches are tiled by get_feature_patches and go through forward_device.
+        dtype="bf16" (B3_MTL only): the network on split bf16 operands as in `forward_device` (`smh_model_forward_dense_bf16`);
+        layer 0 stays the exact-f32 per-frame pass."""
+        entry = self._dense_entry(dtype)
         fv = f32_cuda(fv, "forward_dense")
         rows, what = self._dense_rows()
         if fv.dim() != 2 or fv.shape[0] != rows:
@@ -242,9 +258,9 @@ class B3MTL(TcnTrainingMixin, HostModel):
             return out
         nbytes = getattr(self.lib, self._DENSE_WORKSPACE)(self._h, *self._dense_workspace_args(Tc, shift))
         work = workspace(nbytes, fv.device)
-        got = self._call(self._DENSE_ENTRY, self._h, ptr(fv), Tc, shift, ptr(work), nbytes, ptr(out))
+        got = self._call(entry, self._h, ptr(fv), Tc, shift, ptr(work), nbytes, ptr(out))
         if got != nP:
-            raise RuntimeError("%s produced %d patches, expected %d" % (self._DENSE_ENTRY, got, nP))
+            raise RuntimeError("%s produced %d patches, expected %d" % (entry, got, nP))
         return out
 
     def check_status(self):
@@ -355,12 +371,13 @@ class FusionMTL(B3MTL):
     def _dense_workspace_args(self, Tc, shift):
         return (Tc, shift)
 
-    def forward_dense(self, fv, shift=1, out=None):
+    def forward_dense(self, fv, shift=1, out=None, dtype="f32"):
         """Every hop-`shift` patch of a standardised featuregram batch fv (2 * n_feat, Tc) -- the H||P featuregram exactly as
         B3MTL.forward_dense takes it: H rows, then P rows -- through the network without building the patches or their halves
         (smh_fusion_forward_dense_f32): layer 0 of both trunks once per frame, every patch a window of it.  Returns (nP, out_dim), nP
-        = tools.extract_patches' count for Tc frames.  Needs Tc >= patch_size and n_feat % 4 == 0."""
-        return super().forward_dense(fv, shift, out)
+        = tools.extract_patches' count for Tc frames.  Needs Tc >= patch_size and n_feat % 4 == 0.  dtype: "f32" only (B3_MTL is the
+        only model with a bf16 path)."""
+        return super().forward_dense(fv, shift, out, dtype)
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_data=None,
             steps_per_epoch=None, validation_steps=None, initial_epoch=0, **kwargs):
