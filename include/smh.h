@@ -157,6 +157,27 @@ int smh_features_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, 
 int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc, int harm_layout,
                         int B, int T, int W, int shift, float *d_fv, float *d_patches, int32_t *d_maxkeys, void *stream);
 
+/* ---- patch layout of the harmonic-percussive front end (patch_layout), numbered like smh_extract_patches_f32's `layout`:
+ *   0 = image (B*nP, 2*rows, W), frame index fastest, harmonic rows first: what get_feature_patches returns
+ *       (np.append(patches_H, patches_P, axis=1), lib/preprocessing.py:201-234) -- the Conv2D models' input before
+ *       np.expand_dims(.., axis=3);
+ *   1 = time-major (B*nP, W, 2*rows): the TCN's input after the Lemaire-only transpose (Proposed_Work_Results.py:235-236).
+ * A patch value is the same f32 number in either layout; only its address differs, and the featuregram is the same bits.  The
+ * finishing kernels write the asked-for layout directly (no transpose pass).  smh_features_layout_f32, smh_frontend_layout_f32 and
+ * smh_frontend_ragged_layout_f32 are smh_features_ex_f32, smh_frontend_f32 and smh_frontend_ragged_f32 with that one argument
+ * more; the old entries call them with 1.  Any other value returns SMH_E_INVALID (text in smh_last_error) before any launch.
+ * smh_frontend_ragged_sizes serves both: h_patch_off counts patches, and a patch is W * 2*rows floats in either layout.
+ * (The layer-0 entry smh_features_l0_f32 and the smh_plain_* entries write time-major patches only.)                          */
+int smh_features_layout_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc, int harm_layout,
+                            int B, int T, int W, int shift, int patch_layout, float *d_fv, float *d_patches,
+                            int32_t *d_maxkeys, void *stream);
+int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int W, int shift, int patch_layout,
+                            float *d_fv, float *d_patches, void *d_work, size_t work_bytes, float *d_S, float *d_harm,
+                            float *d_perc, void *stream);
+int smh_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets, const int *h_lengths,
+                                   int B, int W, int shift, int patch_layout, float *d_fv, float *d_patches /* or NULL */,
+                                   void *d_work, size_t work_bytes, void *stream);
+
 /* ---- fused fast path: get_featuregram (from Xin) + get_feature_patches for a batch of clips ---
  * d_audio (B, n_samples) -> d_fv (B, 2*rows, T)  [the featuregram, = get_featuregram's return]
  *                        -> d_patches (B*nP, W, 2*rows) time-major, standardised  [may be NULL]

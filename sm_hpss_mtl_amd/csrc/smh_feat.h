@@ -7,6 +7,10 @@ namespace smh_feat {
 constexpr int kMaxMels = 256;     // filters held in LDS by the fused feature kernel
 constexpr int kMaxMelNnz = 2048;  // taps held in LDS
 
+// patch layouts of the finishing kernels, numbered as smh_extract_patches_f32 numbers its `layout` argument (include/smh.h)
+constexpr int kLayoutImage = 0;      // (nP, 2*rows, W): the Conv2D models' images, harmonic rows first
+constexpr int kLayoutTimeMajor = 1;  // (nP, W, 2*rows): the TCN's input
+
 struct MelTable {
     int n_mels, nnz;
     const int *start, *count, *off;
@@ -30,17 +34,18 @@ FeatPlan feat_plan(const smh_ctx *c, int which /* 0: four segments, 1: eight */)
 // harm_tmajor != 0: harm is (B, T, K) as written by smh_median::launch_hpss(want_tmajor = 1)
 int launch_hp_feat(const smh_ctx *c, const float *S, const float *harm, const float *perc, int harm_tmajor, int B, int T,
                    float *fv, int *maxkeys, hipStream_t st);
-// top_db clip (in place) + StandardScaler + time-major patches
+// top_db clip (in place) + StandardScaler + patches (launch_std_patch below)
 // everything after the medians in one kernel per clip; harmb = harm in layout 2 (B, ceil(T/16), K, 16).
 // Returns 1 if it ran, 0 if the shape does not qualify (the caller must then not have asked for layout 2), < 0 on error
 int launch_features_clip(const smh_ctx *c, const float *S, const float *harmb, const float *perc, int B, int T, int W,
-                         int shift, int nP, float *fv, float *patches, const float *w0, float *x0p, hipStream_t st);
+                         int shift, int nP, float *fv, float *patches, const float *w0, float *x0p, hipStream_t st,
+                         int layout = kLayoutTimeMajor);
 // w0 / x0p non-null: also emit this half's share of the network's first Conv1D (see smh_features_l0_f32)
 // scratch (scratch_bytes): device memory the long-clip path may use for its standardised copy of the featuregram (2 * B * rows * T
 // floats) instead of a stream-ordered allocation per call -- smh_frontend_f32 hands it the S / perc part of its workspace, dead by then
 int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int T, int W, int shift, int nP,
                      float *patches, hipStream_t st, const float *w0 = nullptr, float *x0p = nullptr, void *scratch = nullptr,
-                     size_t scratch_bytes = 0);
+                     size_t scratch_bytes = 0, int layout = kLayoutTimeMajor);
 
 // ---- device helpers of the finishing kernels (smh_ragged.hip, smh_plain.hip) ------------------------------------------------------
 constexpr float kAmin = 1e-10f;  // librosa.power_to_db amin

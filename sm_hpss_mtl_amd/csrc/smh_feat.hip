@@ -417,11 +417,35 @@ hp_feat_walk_kernel(FeatPlan fp, int log_db, const float *__restrict__ S, const 
 
 // ---------------------------------------------------------------------------------------------------
 // fused fast path, kernel 2: one workgroup per (clip, half): top_db clip (written back: the final
-// featuregram) -> StandardScaler per row -> time-major patches (B*nP, W, 2*rows) for the TCN.
+// featuregram) -> StandardScaler per row -> time-major patches (B*nP, W, 2*rows) for the TCN, or, IMAGE, the Conv2D models'
+// images (B*nP, 2*rows, W): what tools.extract_patches returns before the Lemaire-only transpose (lib/preprocessing.py:201-206),
+// harmonic rows first (np.append(patches_H, patches_P, axis=1)).  The same f32 values at other addresses; the layout is a
+// template parameter, so no instantiation carries the other one's store loop.
 // ---------------------------------------------------------------------------------------------------
 constexpr int kPatchThreads = 1024;
 
-template <bool L0>
+// Image-layout store of one workgroup's share of a clip's patches: `nrows` consecutive featuregram rows whose LDS image starts at
+// `img` (row stride ld) with their statistics at s_mean / s_lo / s_inv.  In a patch (2*rows, W) those rows are ONE contiguous block
+// of nrows * W floats starting at float o_first of patch 0 (patch stride pstride): consecutive threads write consecutive floats
+// (f = idx / W, j = idx % W) and read consecutive words of an LDS row.
+__device__ __forceinline__ void store_image_patches(const float *img, int ld, const float *s_mean, const float *s_lo, const float *s_inv,
+                                                    int nrows, int T, int W, int shift, int nP, float *o_first, size_t pstride) {
+    const int n = nrows * W;
+    for (int p = 0; p < nP; ++p) {
+        const int s = p * shift;  // (smh_num_patches leaves no patch to pull back: p * shift + W <= Ttiled)
+        float *o = o_first + (size_t)p * pstride;
+        for (int idx = threadIdx.x; idx < n; idx += blockDim.x) {
+            const int f = idx / W, j = idx - f * W;
+            int tt = s + j;
+            tt -= (tt / T) * T;
+            // (x - mean) rounded to f32 as sklearn does (mean carried as hi + lo), then * 1/scale: the time-major loop's arithmetic
+            const float c = (float)((double)img[f * ld + tt] - ((double)s_mean[f] + (double)s_lo[f]));
+            o[idx] = c * s_inv[f];
+        }
+    }
+}
+
+template <bool L0, bool IMAGE = false>
 __global__ void __launch_bounds__(kPatchThreads)
 std_patch_kernel(int log_db, float *__restrict__ fv, const int *__restrict__ maxkeys, int rows, int T, int Ttiled, int W,
                  int shift, int nP, float *__restrict__ patches, const float *__restrict__ w0, float *__restrict__ x0p) {
@@ -522,6 +546,11 @@ std_patch_kernel(int log_db, float *__restrict__ fv, const int *__restrict__ max
         }
     }
     if (!patches) return;
+    if constexpr (IMAGE) {
+        store_image_patches(tile, ld, s_mean, s_lo, s_inv, rows, T, W, shift, nP,
+                            patches + (size_t)b * nP * F * W + (size_t)half * rows * W, (size_t)F * W);
+        return;
+    }
     for (int p = 0; p < nP; ++p) {
         int s = p * shift;
         const int e = min(s + W, Ttiled);
@@ -561,7 +590,8 @@ __global__ void clip_fv_kernel(float *__restrict__ fv, const int *__restrict__ m
 // ---------------------------------------------------------------------------------------------------
 // RAG (smh_rag.h): workgroup i takes clip list[i] of a ragged call -- T, the tiled length, the patch count and every buffer offset
 // come from that clip's descriptor; the arithmetic is the equal-length instantiation's, so a clip gets the same bits in both.
-template <bool RAG>
+// IMAGE: the patches leave in the Conv2D models' layout (nP, 2*rows, W) -- std_patch_kernel has the store.
+template <bool RAG, bool IMAGE = false>
 __global__ void __launch_bounds__(1024)
 features_clip_kernel(FeatPlan fp, int log_db, int stop_after /* tuning: phase probe */, const float *__restrict__ S, const float *__restrict__ harmb,
                      const float *__restrict__ perc, int K, int T, int rows, int Ttiled, int W, int shift, int nP,
@@ -775,6 +805,10 @@ features_clip_kernel(FeatPlan fp, int log_db, int stop_after /* tuning: phase pr
         }
     }
     if (!patches) return;
+    if constexpr (IMAGE) {  // a patch is the whole image's rows: one contiguous block of R2 * W floats
+        store_image_patches(img, ld, s_mean, s_lo, s_inv, R2, T, W, shift, nP, patches + pb * R2 * W, (size_t)R2 * W);
+        return;
+    }
     for (int p = 0; p < nP; ++p) {
         int s0 = p * shift;
         const int e = min(s0 + W, Ttiled);
@@ -822,7 +856,9 @@ __global__ void fill_int_kernel(int *p, int n, int v) {
 // PROBE: tools/perc_in_walk_bound.py only (SMH_FEAT_PROBE_PERC): a separate instantiation, the plain kernel's registers stay as they are
 // RAG (smh_rag.h): the B entries of `list` are clips of a ragged call (all of even T); T, the tiled length, the patch count and every
 // buffer offset come from the clip's descriptor; the arithmetic is the equal-length instantiation's, so a clip gets the same bits.
-template <int NP, bool TRACE = false, bool PROBE = false, bool RAG = false>
+// IMAGE: the patches leave in the Conv2D models' layout (nP, 2*rows, W), this half's rows as one contiguous block per patch
+// (std_patch_kernel has the store); a separate instantiation, the time-major kernels keep their registers.
+template <int NP, bool TRACE = false, bool PROBE = false, bool RAG = false, bool IMAGE = false>
 __global__ void __launch_bounds__(512, (TRACE ? 6 : 1))
 features_half_kernel(FeatPlan fp, int log_db, int stop_after, const float *__restrict__ S, const float *__restrict__ harmb,
                      const float *__restrict__ perc, int B, int K, int T, int rows, int Ttiled, int W, int shift, int nP,
@@ -1143,6 +1179,11 @@ features_half_kernel(FeatPlan fp, int log_db, int stop_after, const float *__res
     }
     stamp(5);  // layer 0
     if (!patches) return;
+    if constexpr (IMAGE) {
+        store_image_patches(img, ld, s_mean, s_lo, s_inv, rows, T, W, shift, nP, patches + pb * R2 * W + (size_t)half * rows * W,
+                            (size_t)R2 * W);
+        return;
+    }
     for (int p = 0; p < nP; ++p) {
         int s0 = p * shift;
         const int e = min(s0 + W, Ttiled);
@@ -1247,8 +1288,9 @@ int launch_hp_feat(const smh_ctx *c, const float *S, const float *harm, const fl
 
 // single-kernel path (harm in layout 2): returns 1 if it ran, 0 if the shape does not qualify, < 0 on error
 int launch_features_clip(const smh_ctx *c, const float *S, const float *harmb, const float *perc, int B, int T, int W,
-                         int shift, int nP, float *fv, float *patches, const float *w0, float *x0p, hipStream_t st) {
+                         int shift, int nP, float *fv, float *patches, const float *w0, float *x0p, hipStream_t st, int layout) {
     const int K = c->K, rows = c->feat_rows;
+    const bool image = layout == kLayoutImage && patches != nullptr;  // (no patches: the time-major instantiations, which store none)
     if (!c->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS")) return 0;
     if (x0p && (rows % 4 != 0 || rows > 128)) return 0;
     size_t lds = sizeof(float) * ((size_t)2 * rows * (T | 1) + 3 * (size_t)2 * rows) + 128;
@@ -1291,7 +1333,10 @@ int launch_features_clip(const smh_ctx *c, const float *S, const float *harmb, c
         hipLaunchKernelGGL((features_half_kernel<NPV, TR, ##__VA_ARGS__>), dim3(grid), dim3(512), ldh, st, fp, c->cfg.log_db, probe, S, \
                            harmb, perc, B, K, T, rows, smh_tiled_frames(T, W), W, shift, nP, fv, patches, w0, x0p, nullptr, nullptr); \
     } while (0)
-        if (probe >> 8) {  // SMH_FEAT_PROBE_PERC: the instantiation with the probe compiled in (outputs invalid)
+        if (image) {  // (the tools' trace / probe instantiations are time-major only)
+            if (fp.pend <= 2) SMH_LAUNCH_HALF(2, false, false, false, true);
+            else SMH_LAUNCH_HALF(4, false, false, false, true);
+        } else if (probe >> 8) {  // SMH_FEAT_PROBE_PERC: the instantiation with the probe compiled in (outputs invalid)
             SMH_LAUNCH_HALF(2, false, true);
         } else if (fp.trace) {
             if (fp.pend <= 2) SMH_LAUNCH_HALF(2, true);
@@ -1304,46 +1349,65 @@ int launch_features_clip(const smh_ctx *c, const float *S, const float *harmb, c
         int rch = smh::launch_status("features_half_kernel");
         return rch ? rch : 1;
     }
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(features_clip_kernel<false>, dim3(B), dim3(1024), lds, st, fp, c->cfg.log_db, stop & 15, S, harmb, perc, K, T, rows,
-                       smh_tiled_frames(T, W), W, shift, nP, fv, patches, w0, x0p, nullptr, nullptr);
+    if (image) {
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((features_clip_kernel<false, true>), dim3(B), dim3(1024), lds, st, fp, c->cfg.log_db, stop & 15, S, harmb, perc, K, T,
+                           rows, smh_tiled_frames(T, W), W, shift, nP, fv, patches, w0, x0p, nullptr, nullptr);
+    } else {
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(features_clip_kernel<false>, dim3(B), dim3(1024), lds, st, fp, c->cfg.log_db, stop & 15, S, harmb, perc, K, T, rows,
+                           smh_tiled_frames(T, W), W, shift, nP, fv, patches, w0, x0p, nullptr, nullptr);
+    }
     int rc = smh::launch_status("features_clip_kernel");
     return rc ? rc : 1;
 }
 
 // Clips of different lengths that each fit the LDS image (smh_rag.h): the same two kernels, one workgroup (pair) per list entry.
 int launch_features_rag(const smh_ctx *c, const float *S, const float *harmb, const float *perc, const smh_rag::Clip *d_clips,
-                        const int *d_list, int n, int max_T, int even_T, int W, int shift, float *fv, float *patches, hipStream_t st) {
+                        const int *d_list, int n, int max_T, int even_T, int W, int shift, float *fv, float *patches, hipStream_t st,
+                        int layout) {
     if (n <= 0) return SMH_OK;
     const int K = c->K, rows = c->feat_rows;
     const FeatPlan fp = feat_plan(c, 1);
+    const bool image = layout == kLayoutImage && patches != nullptr;
     if (even_T) {
         const size_t ldh = sizeof(float) * ((size_t)rows * (max_T | 1) + 3 * (size_t)rows) + 64;
         const unsigned grid = 16u * (unsigned)((n + 7) / 8);
         const int probe = 16;  // (layer-0 weights are not used here)
+#define SMH_LAUNCH_HALF_RAG(NPV, IMG)                                                                                                \
+    do {                                                                                                                           \
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_half_kernel<NPV, false, false, true, IMG>,                        \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh));                                 \
+        hipLaunchKernelGGL((features_half_kernel<NPV, false, false, true, IMG>), dim3(grid), dim3(512), ldh, st, fp, c->cfg.log_db, \
+                           probe, S, harmb, perc, n, K, 0, rows, 0, W, shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);   \
+    } while (0)
         if (fp.pend <= 2) {
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_half_kernel<2, false, false, true>,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh));
-            hipLaunchKernelGGL((features_half_kernel<2, false, false, true>), dim3(grid), dim3(512), ldh, st, fp, c->cfg.log_db, probe, S,
-                               harmb, perc, n, K, 0, rows, 0, W, shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);
+            if (image) SMH_LAUNCH_HALF_RAG(2, true);
+            else SMH_LAUNCH_HALF_RAG(2, false);
         } else {
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_half_kernel<4, false, false, true>,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh));
-            hipLaunchKernelGGL((features_half_kernel<4, false, false, true>), dim3(grid), dim3(512), ldh, st, fp, c->cfg.log_db, probe, S,
-                               harmb, perc, n, K, 0, rows, 0, W, shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);
+            if (image) SMH_LAUNCH_HALF_RAG(4, true);
+            else SMH_LAUNCH_HALF_RAG(4, false);
         }
+#undef SMH_LAUNCH_HALF_RAG
         return smh::launch_status("features_half_kernel (ragged)");
     }
     const size_t lds = sizeof(float) * ((size_t)2 * rows * (max_T | 1) + 3 * (size_t)2 * rows) + 128;
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(features_clip_kernel<true>, dim3(n), dim3(1024), lds, st, fp, c->cfg.log_db, 0, S, harmb, perc, K, 0, rows, 0, W,
-                       shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);
+    if (image) {
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((features_clip_kernel<true, true>), dim3(n), dim3(1024), lds, st, fp, c->cfg.log_db, 0, S, harmb, perc, K, 0, rows, 0,
+                           W, shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);
+    } else {
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(features_clip_kernel<true>, dim3(n), dim3(1024), lds, st, fp, c->cfg.log_db, 0, S, harmb, perc, K, 0, rows, 0, W,
+                           shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);
+    }
     return smh::launch_status("features_clip_kernel (ragged)");
 }
 
 int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int T, int W, int shift, int nP,
-                     float *patches, hipStream_t st, const float *w0, float *x0p, void *scratch, size_t scratch_bytes) {
+                     float *patches, hipStream_t st, const float *w0, float *x0p, void *scratch, size_t scratch_bytes, int layout) {
     const int rows = c->feat_rows;
+    if (x0p && layout != kLayoutTimeMajor) return smh::set_error(SMH_E_INVALID, "the layer-0 feature path writes time-major patches only");
     const size_t lds = sizeof(float) * ((size_t)rows * (T | 1) + 3 * (size_t)rows);
     if (x0p && (lds > 150 * 1024 || rows % 4 != 0 || rows > 128))
         return smh::set_error(SMH_E_INVALID, "smh_features_l0_f32: needs a featuregram half that fits one LDS tile "
@@ -1371,7 +1435,7 @@ int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int
         size_t nb = (per_clip + 255) / 256;
         if (nb > 4096) nb = 4096;
         hipLaunchKernelGGL(extract_patches_kernel, dim3((unsigned)nb, B), dim3(256), 0, st, (const float *)tmp, 2 * rows, T,
-                           smh_tiled_frames(T, W), W, shift, nP, 1, patches);
+                           smh_tiled_frames(T, W), W, shift, nP, layout, patches);
         int rc = smh::launch_status("long-clip standardise / patch kernels");
         if (own) SMH_CHECK_HIP(hipFreeAsync(tmp, st));
         return rc;
@@ -1381,6 +1445,12 @@ int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int
         hipLaunchKernelGGL(std_patch_kernel<true>, dim3(2, B), dim3(kPatchThreads), lds, st, c->cfg.log_db, fv, maxkeys, rows,
                            T, smh_tiled_frames(T, W), W, shift, nP, patches, w0, x0p);
         return smh::launch_status("std_patch_kernel<l0>");
+    }
+    if (layout == kLayoutImage && patches) {
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)std_patch_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((std_patch_kernel<false, true>), dim3(2, B), dim3(kPatchThreads), lds, st, c->cfg.log_db, fv, maxkeys, rows, T,
+                           smh_tiled_frames(T, W), W, shift, nP, patches, w0, x0p);
+        return smh::launch_status("std_patch_kernel<image>");
     }
     SMH_CHECK_HIP(hipFuncSetAttribute((const void *)std_patch_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(std_patch_kernel<false>, dim3(2, B), dim3(kPatchThreads), lds, st, c->cfg.log_db, fv, maxkeys, rows, T,

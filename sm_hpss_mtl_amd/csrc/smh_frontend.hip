@@ -18,13 +18,18 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 namespace smh_rag {  // smh_ragged.hip: the streaming kernels that serve clips beyond the LDS image (feature_route: smh_rag.h)
 size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T);
 int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, int W, int shift, int nP, float *d_fv,
-              float *d_patches, void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st);
+              float *d_patches, void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout);
 }  // namespace smh_rag
 
-extern "C" int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc,
-                                   int harm_layout, int B, int T, int W, int shift, float *d_fv, float *d_patches,
-                                   int32_t *d_maxkeys, void *stream) {
+namespace {
+inline bool layout_ok(int patch_layout) { return patch_layout == smh_feat::kLayoutImage || patch_layout == smh_feat::kLayoutTimeMajor; }
+}  // namespace
+
+extern "C" int smh_features_layout_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc,
+                                       int harm_layout, int B, int T, int W, int shift, int patch_layout, float *d_fv,
+                                       float *d_patches, int32_t *d_maxkeys, void *stream) {
     SMH_REQUIRE(ctx && d_S && d_harm && d_perc && d_fv && d_maxkeys, "smh_features_f32: null argument");
+    SMH_REQUIRE(layout_ok(patch_layout), "smh_features_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d", patch_layout);
     SMH_REQUIRE(B >= 0 && B <= 65535 && T >= 1, "smh_features_f32: bad shape B=%d T=%d", B, T);
     SMH_REQUIRE(harm_layout >= 0 && harm_layout <= 2, "smh_features_f32: harm_layout must be 0, 1 or 2");
     int nP = 0;
@@ -36,7 +41,7 @@ extern "C" int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const f
     hipStream_t st = (hipStream_t)stream;
     if (harm_layout == 2) {
         int rc2 = smh_feat::launch_features_clip(ctx, d_S, d_harm, d_perc, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP, d_fv,
-                                                 nP > 0 ? d_patches : nullptr, nullptr, nullptr, st);
+                                                 nP > 0 ? d_patches : nullptr, nullptr, nullptr, st, patch_layout);
         if (rc2 < 0) return rc2;
         SMH_REQUIRE(rc2 == 1, "smh_features_ex_f32: harm_layout 2 needs smh_features_blocked_ok(ctx, T=%d, 0)", T);
         return nP;
@@ -45,9 +50,16 @@ extern "C" int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const f
     if (rc) return rc;
     // always run: it applies the top_db clip that completes the featuregram
     rc = smh_feat::launch_std_patch(ctx, d_fv, (const int *)d_maxkeys, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP,
-                                    nP > 0 ? d_patches : nullptr, st);
+                                    nP > 0 ? d_patches : nullptr, st, nullptr, nullptr, nullptr, 0, patch_layout);
     if (rc) return rc;
     return nP;
+}
+
+extern "C" int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc,
+                                   int harm_layout, int B, int T, int W, int shift, float *d_fv, float *d_patches,
+                                   int32_t *d_maxkeys, void *stream) {
+    return smh_features_layout_f32(ctx, d_S, d_harm, d_perc, harm_layout, B, T, W, shift, smh_feat::kLayoutTimeMajor, d_fv, d_patches,
+                                   d_maxkeys, stream);
 }
 
 extern "C" int smh_features_blocked_ok(const smh_ctx *ctx, int T, int with_l0) {
@@ -110,7 +122,15 @@ extern "C" size_t smh_frontend_workspace_bytes(const smh_ctx *ctx, int B, int n_
 extern "C" int smh_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int W, int shift,
                                 float *d_fv, float *d_patches, void *d_work, size_t work_bytes, float *d_S,
                                 float *d_harm, float *d_perc, void *stream) {
+    return smh_frontend_layout_f32(ctx, d_audio, B, n_samples, W, shift, smh_feat::kLayoutTimeMajor, d_fv, d_patches, d_work, work_bytes,
+                                   d_S, d_harm, d_perc, stream);
+}
+
+extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int W, int shift,
+                                       int patch_layout, float *d_fv, float *d_patches, void *d_work, size_t work_bytes,
+                                       float *d_S, float *d_harm, float *d_perc, void *stream) {
     SMH_REQUIRE(ctx && d_audio && d_fv && d_work, "smh_frontend_f32: null argument");
+    SMH_REQUIRE(layout_ok(patch_layout), "smh_frontend_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d", patch_layout);
     SMH_REQUIRE(B >= 0 && B <= 65535, "smh_frontend_f32: B=%d out of range", B);
     const int T = smh_num_frames(n_samples, ctx->cfg.n_fft, ctx->cfg.hop);
     SMH_REQUIRE(T >= 1, "smh_frontend_f32: clip of %d samples is shorter than n_fft=%d", n_samples, ctx->cfg.n_fft);
@@ -139,7 +159,8 @@ extern "C" int smh_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B,
         // the one smh_stft_mag_f32 would pick for this batch: the generic one when a clip starts off an 8-byte boundary (odd n_samples
         // and B > 1), whose S differs in the last bits from the specialised kernel's that a lone aligned clip gets.
         const bool aligned8 = ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0;
-        rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, W, shift, nP, d_fv, nP > 0 ? d_patches : nullptr, d_work, work_bytes, aligned8, st);
+        rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, W, shift, nP, d_fv, nP > 0 ? d_patches : nullptr, d_work, work_bytes, aligned8, st,
+                                patch_layout);
         if (rc < 0) return rc;
         if (rc == 1) return nP;
     }
@@ -155,7 +176,7 @@ extern "C" int smh_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B,
         return smh::set_error(SMH_E_INVALID, "smh_frontend_f32: the medians of T=%d wrote harm layout %d, the feature route needs 2", T, tm);
     if (tm == 2) {
         rc = smh_feat::launch_features_clip(ctx, S, harm, perc, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP, d_fv,
-                                            nP > 0 ? d_patches : nullptr, nullptr, nullptr, st);
+                                            nP > 0 ? d_patches : nullptr, nullptr, nullptr, st, patch_layout);
         if (rc < 0) return rc;
         if (rc == 1) return nP;
         return smh::set_error(SMH_E_INVALID, "smh_frontend_f32: internal layout mismatch");
@@ -165,7 +186,8 @@ extern "C" int smh_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B,
     // (the workspace's S and perc parts -- 2 * spec bytes at its start, also when the caller took the taps into buffers of its own --
     // are dead behind the feature kernel: the long-clip patch path standardises into them instead of allocating per call)
     rc = smh_feat::launch_std_patch(ctx, d_fv, (const int *)maxkeys, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP,
-                                    nP > 0 ? d_patches : nullptr, st, nullptr, nullptr, (d_S || d_perc) ? nullptr : w, 2 * spec);
+                                    nP > 0 ? d_patches : nullptr, st, nullptr, nullptr, (d_S || d_perc) ? nullptr : w, 2 * spec,
+                                    patch_layout);
     if (rc) return rc;
     return nP;
 }

@@ -125,5 +125,6 @@ namespace smh_feat {
 // clips whose featuregram fits an LDS image (smh_features_blocked_ok): the kernels of the equal-length path with per-clip shapes.
 // list: n clip indices, all of even T (even_T != 0: features_half_kernel) or all of odd T (features_clip_kernel); max_T over them.
 int launch_features_rag(const smh_ctx *c, const float *S, const float *harmb, const float *perc, const smh_rag::Clip *d_clips,
-                        const int *d_list, int n, int max_T, int even_T, int W, int shift, float *fv, float *patches, hipStream_t st);
+                        const int *d_list, int n, int max_T, int even_T, int W, int shift, float *fv, float *patches, hipStream_t st,
+                        int layout /* smh_feat::kLayoutImage / kLayoutTimeMajor */);
 }  // namespace smh_feat

@@ -281,7 +281,14 @@ rag_stats_kernel(const float *__restrict__ fv, const int *__restrict__ maxkeys, 
 // frame's column leaves the tile as one contiguous (2*rows)-float row of every patch that holds the frame -- tools.extract_patches'
 // grid (lib/cython_impl/tools.pyx:21-38: patch p = frames p*shift .. p*shift + W - 1 of the tiled featuregram, frame index modulo T
 // for clips shorter than a patch, lib/preprocessing.py:139-142), transposed to time-major (Proposed_Work_Results.py:235-236).
+// IMAGE: the Conv2D models' layout (nP, 2*rows, W) instead (what extract_patches returns, lib/preprocessing.py:201-206).  Phase 2 then
+// keeps phase 1's shape, a wave per row, lanes = the chunk's frames: lane tl holds frame v = t0 + tl, and for every patch p that holds
+// v the wave stores tile[f][tl] at ((patch_off + p) * R2 + f) * W + (v - p * shift) -- consecutive lanes, consecutive floats of row f
+// of the same patch (a patch boundary inside the chunk splits the run in two), read from consecutive words of one LDS row.  The
+// patches a frame lies in are found once per lane, outside the loop over the rows.  Same tile, no LDS added; a separate
+// instantiation, the time-major kernel keeps its registers.
 // ---------------------------------------------------------------------------------------------------------------------------
+template <bool IMAGE>
 __global__ void __launch_bounds__(512)
 rag_final_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int log_db, int rows, int W, int shift,
                  float *__restrict__ patches, const float4 *__restrict__ stats, const Clip *__restrict__ clips,
@@ -322,6 +329,19 @@ rag_final_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int lo
     if (!want) return;
     __syncthreads();
     const int nP = c.nP, Tt = c.Ttiled;
+    if constexpr (IMAGE) {
+        if (lane >= nt) return;
+        const size_t psz = (size_t)R2 * W;
+        for (int v = t0 + lane; v < Tt; v += T) {  // the frame's positions in the tiled featuregram (one unless T < W)
+            int p_lo, p_hi;
+            smh_feat::patch_range(v, W, shift, nP, p_lo, p_hi);
+            for (int p = p_lo; p <= p_hi; ++p) {
+                float *o = patches + ((size_t)c.patch_off + p) * psz + (v - p * shift);
+                for (int f = wave; f < R2; f += nw) o[(size_t)f * W] = tile[f * ld + lane];
+            }
+        }
+        return;
+    }
     for (int tl = wave; tl < nt; tl += nw) {
         for (int v = t0 + tl; v < Tt; v += T) {  // the frame's positions in the tiled featuregram (one unless T < W)
             int p_lo, p_hi;
@@ -371,7 +391,7 @@ bool rag_clip_ok(const smh_ctx *ctx, int T) {
 
 // one sub-batch: tables -> one upload -> one launch per stage
 int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, const HostClip *hc, int n, int W, int shift, float *d_fv,
-                  float *d_patches, char *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st) {
+                  float *d_patches, char *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout) {
     std::vector<Clip> clips;
     const size_t spec = smh_rag::fill_clips(hc, n, g.K, d_patches != nullptr, clips);
     std::vector<int> list[3];
@@ -419,7 +439,7 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
     // 0.4 ms per call and the call got slower, 0.74 -> 1.10 ms per 256 files; everything stays on the caller's stream.)
     for (int k = 0; k < 2; ++k) {  // list 0: even T, list 1: odd T
         rc = smh_feat::launch_features_rag(ctx, d_S, d_harm, d_perc, d_clips, t.at<const int>(o_list[k]), (int)list[k].size(), max_T[k],
-                                           k == 0, W > 0 ? W : 1, shift > 0 ? shift : 1, d_fv, d_patches, st);
+                                           k == 0, W > 0 ? W : 1, shift > 0 ? shift : 1, d_fv, d_patches, st, layout);
         if (rc) return rc;
     }
     if (!list[2].empty()) {
@@ -441,10 +461,18 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
             if (rc) return rc;
         }
         const size_t lds = sizeof(float) * (size_t)2 * g.rows * (kFinalFrames + 1);
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)rag_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const unsigned gf = (unsigned)(8 * (((long long)n_final + 7) / 8));
-        hipLaunchKernelGGL(rag_final_kernel, dim3(gf), dim3(512), lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows, W > 0 ? W : 1,
-                           shift > 0 ? shift : 1, d_patches, (const float4 *)d_stats, d_clips, t.at<const Item>(o_final), n_final);
+        if (layout == smh_feat::kLayoutImage && d_patches) {
+            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)rag_final_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(rag_final_kernel<true>, dim3(gf), dim3(512), lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows,
+                               W > 0 ? W : 1, shift > 0 ? shift : 1, d_patches, (const float4 *)d_stats, d_clips, t.at<const Item>(o_final),
+                               n_final);
+        } else {
+            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)rag_final_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(rag_final_kernel<false>, dim3(gf), dim3(512), lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows,
+                               W > 0 ? W : 1, shift > 0 ? shift : 1, d_patches, (const float4 *)d_stats, d_clips, t.at<const Item>(o_final),
+                               n_final);
+        }
         rc = smh::launch_status("rag_final_kernel");
         if (rc) return rc;
     }
@@ -453,7 +481,7 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
 
 // all clips of `hc` through the ragged kernels, in as few sub-batches as the workspace allows
 int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip> &hc, int W, int shift, float *d_fv, float *d_patches,
-            void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st) {
+            void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout) {
     if (hc.empty()) return SMH_OK;
     RagGeom g;
     g.K = ctx->K, g.rows = ctx->feat_rows;
@@ -463,7 +491,7 @@ int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip
     return smh_rag::run_sub_batches(
         hc.size(), kFixedBytes, work_bytes, st, [&](size_t b) { return clip_bytes(g, hc[b]); }, [&](size_t b0, size_t nb) {
             return run_sub_batch(ctx, g, d_audio, hc.data() + b0, (int)nb, W, shift, d_fv, d_patches, (char *)d_work, work_bytes,
-                                 stft_aligned8, st);
+                                 stft_aligned8, st, layout);
         });
 }
 
@@ -593,7 +621,7 @@ size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T) {
 }
 
 int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, int W, int shift, int nP, float *d_fv,
-              float *d_patches, void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st) {
+              float *d_patches, void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout) {
     if (!rag_context_ok(ctx) || !rag_clip_ok(ctx, T) || (reinterpret_cast<uintptr_t>(d_work) % 16) != 0) return 0;
     const int rows2 = 2 * ctx->feat_rows;
     std::vector<HostClip> hc(B);
@@ -601,7 +629,7 @@ int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, in
         hc[b].audio_off = (long long)b * n_samples, hc[b].fv_off = (long long)b * rows2 * T, hc[b].patch_off = (long long)b * nP;
         hc[b].T = T, hc[b].Ttiled = smh_tiled_frames(T, W > 0 ? W : 1), hc[b].nP = nP, hc[b].cls = 2;
     }
-    int rc = run_rag(ctx, d_audio, hc, W, shift, d_fv, d_patches, d_work, work_bytes, stft_aligned8, st);
+    int rc = run_rag(ctx, d_audio, hc, W, shift, d_fv, d_patches, d_work, work_bytes, stft_aligned8, st, layout);
     return rc ? rc : 1;
 }
 
@@ -672,10 +700,12 @@ extern "C" int smh_frontend_ragged_sizes(const smh_ctx *ctx, const long long *h_
     return SMH_OK;
 }
 
-extern "C" int smh_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets,
-                                       const int *h_lengths, int B, int W, int shift, float *d_fv, float *d_patches,
-                                       void *d_work, size_t work_bytes, void *stream) {
+extern "C" int smh_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets,
+                                              const int *h_lengths, int B, int W, int shift, int patch_layout, float *d_fv,
+                                              float *d_patches, void *d_work, size_t work_bytes, void *stream) {
     SMH_REQUIRE(ctx && d_audio && d_fv && d_work && h_offsets && h_lengths && B >= 0, "smh_frontend_ragged_f32: bad argument");
+    SMH_REQUIRE(patch_layout == smh_feat::kLayoutImage || patch_layout == smh_feat::kLayoutTimeMajor,
+                "smh_frontend_ragged_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d", patch_layout);
     const bool patches = d_patches != nullptr;
     SMH_REQUIRE(!patches || (W >= 1 && shift >= 1), "smh_frontend_ragged_f32: bad patch geometry W=%d shift=%d", W, shift);
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0, "smh_frontend_ragged_f32: the workspace must start on a 16-byte boundary");
@@ -689,12 +719,19 @@ extern "C" int smh_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio,
     hc.reserve(B);
     for (int b = 0; b < B; ++b)
         if (cls[b] >= 0) hc.push_back(smh_rag::host_clip(p, h_offsets, b, W, cls[b]));
-    rc = run_rag(ctx, d_audio, hc, W, shift, d_fv, d_patches, d_work, work_bytes, true, st);
+    rc = run_rag(ctx, d_audio, hc, W, shift, d_fv, d_patches, d_work, work_bytes, true, st, patch_layout);
     if (rc) return rc;
     // the clips no ragged kernel covers, one by one on the same stream (the workspace is free again in stream order)
     return smh_rag::run_alone(p, B, W, shift, 2 * ctx->feat_rows, d_fv, d_patches, [&](int b) { return cls[b] >= 0; },
                               [&](int b, int w, int sh, float *fv, float *pt) {
-                                  return smh_frontend_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], w, sh, fv, pt, d_work, work_bytes,
-                                                          nullptr, nullptr, nullptr, stream);
+                                  return smh_frontend_layout_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], w, sh, patch_layout, fv, pt,
+                                                                 d_work, work_bytes, nullptr, nullptr, nullptr, stream);
                               });
+}
+
+extern "C" int smh_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets,
+                                       const int *h_lengths, int B, int W, int shift, float *d_fv, float *d_patches,
+                                       void *d_work, size_t work_bytes, void *stream) {
+    return smh_frontend_ragged_layout_f32(ctx, d_audio, h_offsets, h_lengths, B, W, shift, smh_feat::kLayoutTimeMajor, d_fv, d_patches,
+                                          d_work, work_bytes, stream);
 }

@@ -32,6 +32,9 @@ PLAIN_FEATS = {
     "MelSpec": (True, False),
     "LogMelSpec": (True, True),
 }
+# Frontend's `layout` argument -> the C ABI's patch_layout (include/smh.h): "image" (nP, 2*rows, W), what get_feature_patches returns
+# and the Conv2D models read; "time_major" (nP, W, 2*rows), the TCN's input
+LAYOUTS = {"image": 0, "time_major": 1}
 # FrontendConfig.stft_precision -> the C ABI's stft_precision (include/smh.h: SMH_STFT_F32 / SMH_STFT_F64)
 STFT_PRECISIONS = {"f32": _lib.SMH_STFT_F32, "f64": _lib.SMH_STFT_F64}
 
@@ -96,6 +99,16 @@ class FrontendConfig:
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _layout(layout):
+    if layout not in LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (sorted(LAYOUTS), layout))
+    return LAYOUTS[layout]
+
+
+def _patch_shape(n, W, F, layout):
+    return (n, F, W) if layout == "image" else (n, W, F)
 
 
 def _stream():
@@ -257,9 +270,11 @@ class Frontend:
         assert got == nP
         return out
 
-    def features(self, S, harm, perc, W=None, shift=None, out=None):
-        """(S, harm, perc) -> dict(fv[, patches]): masks + mel + dB, then standardise + time-major patches."""
+    def features(self, S, harm, perc, W=None, shift=None, out=None, layout="time_major"):
+        """(S, harm, perc) -> dict(fv[, patches]): masks + mel + dB, then standardise + patches: (B*nP, W, 2*rows) time-major, or
+        (B*nP, 2*rows, W) with layout="image"."""
         self._need_hpss("features")
+        lay = _layout(layout)
         S, harm, perc = _f32c(S, "S"), _f32c(harm, "harm"), _f32c(perc, "perc")
         B, K, T = S.shape
         dev = S.device
@@ -267,11 +282,11 @@ class Frontend:
         nP, patches = 0, None
         if W is not None:
             nP = self.num_patches(T, W, shift)
-            patches = _out(out, "patches", (B * nP, W, 2 * self.rows), torch.float32, dev)
+            patches = _out(out, "patches", _patch_shape(B * nP, W, 2 * self.rows, layout), torch.float32, dev)
         keys = _maxkeys(out, 2 * B, "2*B", dev)
-        got = _lib.check(self.lib.smh_features_f32(self._h, _ptr(S), _ptr(harm), _ptr(perc), B, T, W or 0, shift or 0,
-                                                   _ptr(fv), _ptr(patches) if nP else None, _ptr(keys), _stream()),
-                         "smh_features_f32")
+        got = _lib.check(self.lib.smh_features_layout_f32(self._h, _ptr(S), _ptr(harm), _ptr(perc), 0, B, T, W or 0, shift or 0, lay,
+                                                          _ptr(fv), _ptr(patches) if nP else None, _ptr(keys), _stream()),
+                         "smh_features_layout_f32")
         assert got == nP
         return {"fv": fv, "patches": patches, "n_patches": nP, "maxkeys": keys}
 
@@ -326,14 +341,24 @@ class Frontend:
         return {"fv": fv, "patches": patches, "n_patches": nP, "maxkeys": keys}
 
     # ---- fused fast path ----
-    def run(self, audio, W=None, shift=None, taps=False, out=None):
+    def _plain_layout(self, layout):
+        lay = _layout(layout)
+        if not self.cfg.hpss and layout != "time_major":
+            raise ValueError("the plain front end (hpss=False) writes time-major patches only; layout=%r needs a harmonic-percussive "
+                             "configuration" % (layout,))
+        return lay
+
+    def run(self, audio, W=None, shift=None, taps=False, out=None, layout="time_major"):
         """audio (B, n_samples) -> dict(fv=(B, 2*rows, T)[, patches=(B*nP, W, 2*rows)][, S, harm, perc]).
+        layout="image": patches=(B*nP, 2*rows, W), the Conv2D models' images, written by the same kernels (no transpose pass).
         `out` may carry preallocated 'fv' / 'patches' tensors (steady-state loops allocate nothing).
-        A plain configuration (hpss=False) gives fv=(B, rows, T) and patches=(B*nP, W, rows); its only tap is S."""
+        A plain configuration (hpss=False) gives fv=(B, rows, T) and patches=(B*nP, W, rows), time-major only; its only tap is S."""
+        lay = self._plain_layout(layout)
         # what differs between the two front ends: the featuregram's rows, the workspace / entry pair and the taps
         if self.cfg.hpss:
             F, names = 2 * self.rows, ("S", "harm", "perc")
-            work_bytes, entry, label = self.lib.smh_frontend_workspace_bytes, self.lib.smh_frontend_f32, "smh_frontend_f32"
+            work_bytes, label = self.lib.smh_frontend_workspace_bytes, "smh_frontend_layout_f32"
+            entry = lambda h, a, B_, N_, W_, sh, *rest: self.lib.smh_frontend_layout_f32(h, a, B_, N_, W_, sh, lay, *rest)
         else:
             F, names = self.rows, ("S",)
             work_bytes, entry, label = (self.lib.smh_plain_frontend_workspace_bytes, self.lib.smh_plain_frontend_f32,
@@ -352,8 +377,8 @@ class Frontend:
         if W is not None:
             nP = self.num_patches(T, W, shift)
             patches = out.get("patches")
-            if patches is None or patches.shape != (B * nP, W, F):
-                patches = torch.empty((B * nP, W, F), dtype=torch.float32, device=dev)
+            if patches is None or patches.shape != _patch_shape(B * nP, W, F, layout):
+                patches = torch.empty(_patch_shape(B * nP, W, F, layout), dtype=torch.float32, device=dev)
         need = work_bytes(self._h, B, N)
         if self._work is None or self._work.numel() < need or self._work.device != dev:
             self._work = torch.empty(need if self.cfg.hpss else max(need, 1), dtype=torch.uint8, device=dev)
@@ -368,13 +393,14 @@ class Frontend:
         return res
 
     # ---- ragged batches ----
-    def run_ragged(self, clips, W=None, shift=None):
-        """Clips of DIFFERENT lengths in one call (`smh_frontend_ragged_f32`).  clips: list of 1-D float32 arrays / tensors.
-        Returns dict(fv=[(2*rows, T_b) tensors], patches=[(nP_b, W, 2*rows) tensors] (views of one buffer each),
-        n_patches=[...], T=[...]).  Every clip gets bit for bit what `run` gives it alone or in an equal-length batch:
+    def run_ragged(self, clips, W=None, shift=None, layout="time_major"):
+        """Clips of DIFFERENT lengths in one call (`smh_frontend_ragged_layout_f32`).  clips: list of 1-D float32 arrays / tensors.
+        Returns dict(fv=[(2*rows, T_b) tensors], patches=[(nP_b, W, 2*rows) tensors] (views of one buffer each; (nP_b, 2*rows, W)
+        with layout="image"), n_patches=[...], T=[...]).  Every clip gets bit for bit what `run` gives it alone or in an equal-length batch:
         the clips are laid out at 16-byte aligned offsets, so each takes the same kernels as there.  (Not an equal-length
         batch of an odd number of samples: its clips start off 8-byte boundaries and take the generic STFT kernel, whose S
         differs from the specialised kernel's in the last bits.)"""
+        lay = self._plain_layout(layout)
         B = len(clips)
         if B == 0:
             return {"fv": [], "patches": [], "n_patches": [], "T": []}
@@ -406,10 +432,12 @@ class Frontend:
         # a plain configuration (hpss=False) takes the plain pair of entries: same contract, (rows, T_b) and (nP_b, W, rows) per clip
         stem = "smh_frontend_ragged" if self.cfg.hpss else "smh_plain_frontend_ragged"
         sizes, ragged = getattr(self.lib, stem + "_sizes"), getattr(self.lib, stem + "_f32")
+        if self.cfg.hpss:
+            ragged = lambda h, a, o_, l_, B_, W_, sh, *rest: self.lib.smh_frontend_ragged_layout_f32(h, a, o_, l_, B_, W_, sh, lay, *rest)
         _lib.check(sizes(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP, C.byref(work)), stem + "_sizes")
         F = (2 if self.cfg.hpss else 1) * self.rows
         fv = torch.empty(max(int(fv_off[B]), 1), dtype=torch.float32, device=dev)
-        patches = torch.empty((max(int(p_off[B]), 1), W or 1, F), dtype=torch.float32, device=dev) if W else None
+        patches = torch.empty(_patch_shape(max(int(p_off[B]), 1), W or 1, F, layout), dtype=torch.float32, device=dev) if W else None
         if self._work is None or self._work.numel() < work.value or self._work.device != dev:
             self._work = torch.empty(max(work.value, 1), dtype=torch.uint8, device=dev)
         _lib.check(ragged(self._h, _ptr(audio), h_off, h_len, B, W or 0, shift or 0, _ptr(fv),
@@ -421,11 +449,13 @@ class Frontend:
             res["patches"] = [patches[int(p_off[b]):int(p_off[b + 1])] for b in range(B)]
         return res
 
-    def patches_from_featuregram(self, fv, W, shift):
-        """get_feature_patches for the TCN models on the device: featuregram (2*rows, T) [rows 0..F/2-1 harmonic] ->
-        standardised time-major patches (nP, W, 2*rows) (tile-if-short, StandardScaler per half, extract_patches, transpose)."""
+    def patches_from_featuregram(self, fv, W, shift, layout="time_major"):
+        """get_feature_patches on the device: featuregram (2*rows, T) [rows 0..F/2-1 harmonic] -> standardised patches
+        (tile-if-short, StandardScaler per half, extract_patches): time-major (nP, W, 2*rows) for the TCN models (the transpose
+        included), or layout="image": (nP, 2*rows, W) as get_feature_patches returns them, for the Conv2D models."""
+        _layout(layout)
         fv = _f32c(fv, "fv")
         if fv.dim() != 2:
             raise ValueError("FV should be of the shape (nFeatures, nFrames)")
         x = self.standardize_rows(fv)  # per row over the frames: the per-half scaler is row-wise, so halves need no split
-        return self.extract_patches(x[None], W, shift, time_major=True)
+        return self.extract_patches(x[None], W, shift, time_major=layout == "time_major")

@@ -9,7 +9,8 @@ happens: the reference computes one file at a time on the CPU and grows its buff
 batch needs are decided first -- the number of patches a file yields is an integer contract of its length
 (`smh_num_frames` / `smh_tiled_frames` / `smh_num_patches`), and silence removal keeps the length -- and then go through
 the HIP front end together as ONE ragged device batch (`Frontend.run_ragged`); patches stay on the device as float32
-tensors in the network's (N, W, 2F) layout.  Per-file results do not depend on what else is in the batch, so the yielded
+tensors in the network's layout, written that way by the front end's kernels: (N, W, 2F) time-major for the Lemaire TCN models,
+(N, 2F, W, 1) images for the Conv2D ones (PARAMS['Model'] decides, as it does in the reference's loop).  Per-file results do not depend on what else is in the batch, so the yielded
 batches are the ones the sequential loop would yield.
 
 Data parallel (SURVEY 8e "class-balanced batch composition must be preserved globally, not per rank"): `generator(...,
@@ -176,12 +177,16 @@ def _cached_featuregram(path, fresh=None):
 def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
     """specs: list of (classname, sp_path, mu_path, target_dB).  Loads / conditions / mixes the signals (the 'next' row in
     front of the path: lib.preprocessing.load_and_preprocess_signal, mix_signals), then ONE ragged pass of the front end.
-    Returns a list of (nP_i, W, 2F) float32 device tensors ((nP_i, W, F) for the feature names without an H / P pair)."""
+    Returns a list of float32 device tensors in the layout PARAMS['Model'] reads: (nP_i, W, 2F) for a Lemaire_et_al variant
+    ((nP_i, W, F) for the feature names without an H / P pair); (nP_i, 2F, W, 1) for any other -- the Conv2D models' images,
+    get_feature_patches' np.expand_dims(patches, axis=3), Proposed_Work_Results.py:483-484 (a view: no copy)."""
     import torch
     from . import frontend as _fe
     from .lib import preprocessing as pp
-    if 'Lemaire_et_al' not in PARAMS['Model']:
-        raise ValueError("the device generator yields the TCN layout (N, W, F): Model must be a Lemaire_et_al variant")
+    layout = "time_major" if 'Lemaire_et_al' in PARAMS['Model'] else "image"
+    if layout == "image" and featName in _fe.PLAIN_FEATS:
+        raise ValueError("the plain front end (featName %r) writes the TCN layout (N, W, F) only: the device generator serves the "
+                         "Conv2D models from the '*HarmPercSpec' feature names" % (featName,))
     clips = []
     for classname, sp, mu, db in specs:
         cache = pp.feature_cache_path(PARAMS['feature_opDir'], classname, sp, mu, db)
@@ -202,7 +207,7 @@ def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
     out = [None] * len(clips)
     audio_idx = [i for i, c in enumerate(clips) if c[0] == "audio"]
     if audio_idx:
-        res = fe.run_ragged([clips[i][1] for i in audio_idx], W=W, shift=shift)
+        res = fe.run_ragged([clips[i][1] for i in audio_idx], W=W, shift=shift, layout=layout)
         for k, i in enumerate(audio_idx):
             out[i] = res["patches"][k]
             if PARAMS.get('save_features', True):  # get_featuregram(save_feat=True): the reference's .npy cache
@@ -213,8 +218,8 @@ def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
                 _cached_featuregram(clips[i][2], fresh=res["fv"][k])  # ... and stays on the device for the epochs to come
     for i, c in enumerate(clips):
         if c[0] == "fv":  # cached featuregram (device copy after its first use): standardise + patches only
-            out[i] = fe.patches_from_featuregram(_cached_featuregram(c[1]), W, shift)
-    return out
+            out[i] = fe.patches_from_featuregram(_cached_featuregram(c[1]), W, shift, layout=layout)
+    return [t.unsqueeze(3) for t in out] if layout == "image" else out
 
 
 def _n_patches_of_file(PARAMS, path, n_fft, W, shift, lengths_cache):
@@ -309,7 +314,7 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
     the patches of a list of files as one batch) -- defaults: the integer contracts of libsmh and ONE ragged front-end pass.
 
     batchData: [batchSize music | batchSize speech | batchSize speech+music] patches, (3*batchSize, W, 2F) for the TCN
-    models ((.., 2F, W, 1) for the Conv2D ones when the per-file callables are injected); labels: {'R', 'S', 'M', '3C'} for
+    models, (.., 2F, W, 1) for the Conv2D ones (device path and injected per-file callables alike); labels: {'R', 'S', 'M', '3C'} for
     the MTL models (the S = M = 0 rule for mixtures included, Proposed_Work_Results.py:249-260), else the one-hot matrix."""
     batch_count = 0
     np.random.shuffle(file_list['speech'])
@@ -437,7 +442,7 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
                     batchData = batching.noise_augmentation(full, rng)[mine]
         else:
             import torch
-            batchData = torch.cat(parts, dim=0)  # device patches are already (N, W, F)
+            batchData = torch.cat(parts, dim=0)  # device patches are already in the model's layout: (N, W, F) or (N, F, W, 1)
             if PARAMS['data_augmentation_with_noise']:  # the scale from numpy (same on all ranks), the noise from torch's generator
                 batchData = batching.noise_augmentation(batchData, rng)
         if three:
@@ -496,8 +501,8 @@ def fusion_generator(PARAMS, folder, file_list, batchSize, **kwargs):
 
 def test_file_wise_generator(PARAMS, file_name_sp, file_name_mu, target_dB, featuregram_fn=None, patches_fn=None):
     """All patches of ONE test file + their one-hot labels (Proposed_Work_Results.py:459-496).  The patch shift is the
-    reference's hard-coded 68, not PARAMS['W_shift'].  Device path: float32 tensor (nP, W, 2F); with the per-file callables
-    injected: what they return, transposed to (nP, W, F) for the TCN models."""
+    reference's hard-coded 68, not PARAMS['W_shift'].  Device path: float32 tensor (nP, W, 2F) for the TCN models, (nP, 2F, W, 1)
+    for the Conv2D ones; with the per-file callables injected: what they return, transposed to (nP, W, F) for the TCN models."""
     n_fft = PARAMS['n_fft'][PARAMS['Model']]
     n_mels = PARAMS['n_mels'][PARAMS['Model']]
     featName = PARAMS['featName'][PARAMS['Model']]
