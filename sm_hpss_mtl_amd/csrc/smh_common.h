@@ -33,6 +33,16 @@ inline int launch_status(const char *what) {
     return SMH_OK;
 }
 
+// One launch of a kernel with dynamic LDS beyond the 64 KB default: raise the kernel's limit to attr_lds (on every call -- the
+// attribute belongs to the kernel, the value to the shape), launch with `lds` bytes, report the status under `what`.
+template <class... Params, class... Args>
+inline int launch_lds(void (*kernel)(Params...), const char *what, dim3 grid, dim3 block, size_t lds, size_t attr_lds, hipStream_t st,
+                      Args... args) {
+    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_lds));
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<Params>(args)...);
+    return launch_status(what);
+}
+
 // Timing probes and experiment switches that make a launch's OUTPUTS INVALID (a phase skipped, a store or load left out):
 // read only when SMH_ENABLE_PROBES=1 is set, and every affected launch says so on stderr.  Without that switch the variable is
 // ignored (one notice per variable).  Selectors that keep results valid (kernel A/B choices such as SMH_TCN_SKEW) use getenv.

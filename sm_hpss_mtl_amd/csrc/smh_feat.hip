@@ -1221,15 +1221,44 @@ extern "C" int smh_internal_feat_trace(int enable, unsigned long long *host, siz
     return 0;
 }
 
+// ---- the kernel table: every instantiation of the LDS-image kernels the library holds, chosen from run-time values ------------------
+// (a flag like IMAGE is added here, not at the launch sites)
+namespace {
+enum HalfTool { kNoTool, kTrace, kProbe };  // tools/trace_features.py's stamps; SMH_FEAT_PROBE_PERC (outputs invalid)
+using HalfKernel = decltype(&features_half_kernel<2>);
+using ClipKernel = decltype(&features_clip_kernel<false>);
+using StdPatchKernel = decltype(&std_patch_kernel<false>);
+
+HalfKernel pick_half_kernel(bool pend2, bool rag, bool image, HalfTool tool) {
+    if (rag) {
+        if (image) return pend2 ? features_half_kernel<2, false, false, true, true> : features_half_kernel<4, false, false, true, true>;
+        return pend2 ? features_half_kernel<2, false, false, true, false> : features_half_kernel<4, false, false, true, false>;
+    }
+    // (the tools' trace / probe instantiations are time-major, equal-length only; the probe has its two-accumulator form only)
+    if (image) return pend2 ? features_half_kernel<2, false, false, false, true> : features_half_kernel<4, false, false, false, true>;
+    if (tool == kProbe) return features_half_kernel<2, false, true>;
+    if (tool == kTrace) return pend2 ? features_half_kernel<2, true> : features_half_kernel<4, true>;
+    return pend2 ? features_half_kernel<2, false> : features_half_kernel<4, false>;
+}
+ClipKernel pick_clip_kernel(bool rag, bool image) {
+    if (rag) return image ? features_clip_kernel<true, true> : features_clip_kernel<true>;
+    return image ? features_clip_kernel<false, true> : features_clip_kernel<false>;
+}
+StdPatchKernel pick_std_patch_kernel(bool l0, bool image) {  // (layer 0 reads time-major patches: no <true, true>)
+    if (l0) return std_patch_kernel<true>;
+    return image ? std_patch_kernel<false, true> : std_patch_kernel<false>;
+}
+}  // namespace
+
 // Residency of the bench path's feature kernel (tests/test_bench_path_gpu.py): workgroups of features_half_kernel<2> per CU
 // for a clip of T frames and `rows` mel rows per half with the layer-0 weights read from L2.  Three is what the measured
 // 113-118 us rest on (78 VGPRs, 49 KB of LDS); a build that needs more than 80 VGPRs silently drops to two and ~130 us.
 extern "C" int smh_internal_feat_residency(int rows, int T) {
-    const size_t ldh = sizeof(float) * ((size_t)rows * (T | 1) + 3 * (size_t)rows) + 64;
-    if (hipFuncSetAttribute((const void *)features_half_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh) != hipSuccess)
-        return -1;
+    const size_t ldh = smh_feat::half_image_bytes(rows, T, false);
+    const void *k = (const void *)pick_half_kernel(true, false, false, kNoTool);
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh) != hipSuccess) return -1;
     int nb = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)features_half_kernel<2, false>, 512, ldh) != hipSuccess) return -1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 512, ldh) != hipSuccess) return -1;
     return nb;
 }
 
@@ -1270,149 +1299,95 @@ int launch_hp_feat(const smh_ctx *c, const float *S, const float *harm, const fl
     if (c->feat_walk_ok && lds_walk <= 150 * 1024 && walk_waves >= 1 && !smh::lab_env("SMH_FEAT_TAPS")) {
         const FeatPlan fp = feat_plan(c, 0);
         const int nwaves = std::min(16, walk_waves);
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)hp_feat_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_walk));
-        hipLaunchKernelGGL(hp_feat_walk_kernel, dim3(B), dim3(64 * nwaves), lds_walk, st, fp, c->cfg.log_db, S, harm, perc,
-                           harm_tmajor, K, T, rows, fv, maxkeys);
-        return smh::launch_status("hp_feat_walk_kernel");
+        return smh::launch_lds(hp_feat_walk_kernel, "hp_feat_walk_kernel", dim3(B), dim3(64 * nwaves), lds_walk, lds_walk, st, fp,
+                               c->cfg.log_db, S, harm, perc, harm_tmajor, K, T, rows, fv, maxkeys);
     }
     // frame slabs: split T evenly into pieces of <= 64 frames (T=98 -> 2 x 49)
     const int nslab = (T + 63) / 64;
     const int TS = (T + nslab - 1) / nslab;
     const size_t lds = harm_tmajor ? sizeof(float) * (size_t)TS * (K | 1) : 0;
     if (lds > 150 * 1024) return smh::set_error(SMH_E_INVALID, "K=%d too large for the feature kernel", K);
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)hp_feat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(hp_feat_kernel, dim3((T + TS - 1) / TS, B), dim3(kFeatThreads), lds, st, mel_table(c), c->cfg.log_db, S,
-                       harm, perc, harm_tmajor, K, T, TS, rows, fv, maxkeys);
-    return smh::launch_status("hp_feat_kernel");
+    return smh::launch_lds(hp_feat_kernel, "hp_feat_kernel", dim3((T + TS - 1) / TS, B), dim3(kFeatThreads), lds, lds, st, mel_table(c),
+                           c->cfg.log_db, S, harm, perc, harm_tmajor, K, T, TS, rows, fv, maxkeys);
 }
 
-// single-kernel path (harm in layout 2): returns 1 if it ran, 0 if the shape does not qualify, < 0 on error
-int launch_features_clip(const smh_ctx *c, const float *S, const float *harmb, const float *perc, int B, int T, int W,
-                         int shift, int nP, float *fv, float *patches, const float *w0, float *x0p, hipStream_t st, int layout) {
-    const int K = c->K, rows = c->feat_rows;
-    const bool image = layout == kLayoutImage && patches != nullptr;  // (no patches: the time-major instantiations, which store none)
-    if (!c->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS")) return 0;
-    if (x0p && (rows % 4 != 0 || rows > 128)) return 0;
-    size_t lds = sizeof(float) * ((size_t)2 * rows * (T | 1) + 3 * (size_t)2 * rows) + 128;
-    if (x0p) lds += sizeof(float) * 2 * rows * 32;  // the layer's weights
-    if (lds > 158 * 1024) return 0;
+bool features_image_ok(const smh_ctx *c, int T, bool with_l0) {
+    const int rows = c->feat_rows;
+    if (!c->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS")) return false;
+    if (with_l0 && (rows % 4 != 0 || rows > 128)) return false;
+    return clip_image_bytes(rows, T, with_l0) <= kClipImageLimit;
+}
+
+// single-kernel path (harm in layout 2): returns 1 if it ran, 0 if the shape does not qualify, < 0 on error.
+// Clips of different lengths that each fit the LDS image (smh_rag.h) take the same two kernels, one workgroup (pair) per list entry.
+int launch_features_image(const smh_ctx *c, const float *S, const float *harmb, const float *perc, const ImageClips &clips,
+                          const PatchOut &po, float *fv, const float *w0, float *x0p, hipStream_t st) {
+    const bool rag = clips.d_clips != nullptr;
+    const int K = c->K, rows = c->feat_rows, n = clips.n, T = clips.T;
+    if (rag && n <= 0) return 1;
+    // (a list's clips were routed here by the same predicate: smh_rag::feature_route)
+    if (!rag && !features_image_ok(c, T, x0p != nullptr)) return 0;
+    const bool image = po.layout == kLayoutImage && po.patches != nullptr;  // (no patches: the time-major instantiations, which store none)
     // even T: one workgroup per (clip, half), lane = frame pair (features_half_kernel); odd T: one workgroup per clip, lane = frame
-    const int pair = (T % 2 == 0 && !getenv("SMH_FEAT_NOPAIR")) ? 1 : 0;
+    const bool pair = rag ? clips.even_T != 0 : (T % 2 == 0 && !getenv("SMH_FEAT_NOPAIR"));
     FeatPlan fp = feat_plan(c, 1);
-    fp.trace = g_feat_trace;
-    const char *stop_ev = smh::probe_env("SMH_FEAT_STOP");  // timing probe: the kernel returns early
-    int stop = stop_ev ? atoi(stop_ev) & 15 : 0;
-    if (const char *pe = smh::probe_env("SMH_FEAT_PROBE_PERC")) stop |= (std::max(0, std::min(atoi(pe), 255)) << 8);  // see the kernel
+    int stop = 0;
+    bool w0_l2 = true;
+    if (!rag) {  // the tools' switches act on the equal-length launch only
+        fp.trace = g_feat_trace;
+        const char *stop_ev = smh::probe_env("SMH_FEAT_STOP");  // timing probe: the kernel returns early
+        stop = stop_ev ? atoi(stop_ev) & 15 : 0;
+        if (const char *pe = smh::probe_env("SMH_FEAT_PROBE_PERC")) stop |= (std::max(0, std::min(atoi(pe), 255)) << 8);  // see the kernel
+    }
+    // the kernels read a list's shapes from d_clips: T, the tiled length and nP go as 0
+    const int kT = rag ? 0 : T, Ttiled = rag ? 0 : smh_tiled_frames(T, po.W), nP = rag ? 0 : po.nP;
     if (pair) {
         // half the LDS per workgroup: two share a CU.  The 8 waves take the 8-segment plan, one segment each: every segment
         // boundary costs a re-read of the bins its filters straddle (8 segments: 280 bin reads for 201 bins; 16 segments,
         // two per wave: 340 and 5 % slower).  Tried and dropped: disjoint bin ranges with the straddling filters' partial sums
         // combined by ds_add_f32 in a zeroed image (every bin read once, but 1.7x slower: LDS float atomics); software
         // pipelining of the walk's half-batches (slower: the loads already overlap across the two workgroups of a CU).
-        size_t ldh = sizeof(float) * ((size_t)rows * (T | 1) + 3 * (size_t)rows) + 64;
         // the layer-0 weights come straight from L2 (15 KB per half, shared by every workgroup): without an LDS copy a workgroup
         // needs 49 KB and THREE share a CU (77 VGPRs: 6 waves per SIMD) -- 127-130 -> 113-115 us; SMH_FEAT_W0LDS=1: the copy
-        const bool w0_l2 = smh::lab_env("SMH_FEAT_W0LDS") == nullptr;
-        if (x0p && !w0_l2) ldh += sizeof(float) * rows * 32;
+        if (!rag) w0_l2 = smh::lab_env("SMH_FEAT_W0LDS") == nullptr;
+        const size_t ldh = half_image_bytes(rows, T, x0p && !w0_l2);
+        if (ldh > kHalfImageLimit) return smh::set_error(SMH_E_INVALID, "features_half_kernel: image of %zu bytes for T=%d", ldh, T);
         const int probe = (stop & ~16) | (w0_l2 ? 16 : 0);
         // (the two halves of a clip back to back in their XCD's dispatch order: consecutive workgroups land on the same CU and the
         // second finds the first one's S / harm / perc lines in that CU's vector cache -- n halves apart the kernel takes 134 us
         // instead of 111, profiles/r03_store_policies.txt)
-        const unsigned grid = 16u * (unsigned)((B + 7) / 8);
-        if (getenv("SMH_FEAT_OCC")) {  // tools only: what the runtime says about residency
+        const unsigned grid = 16u * (unsigned)((n + 7) / 8);
+        if (!rag && getenv("SMH_FEAT_OCC")) {  // tools only: what the runtime says about residency
+            const void *k2 = (const void *)pick_half_kernel(true, false, false, kNoTool);
             int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)features_half_kernel<2, false>, 512, ldh);
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k2, 512, ldh);
             hipFuncAttributes fa;
-            (void)hipFuncGetAttributes(&fa, (const void *)features_half_kernel<2, false>);
+            (void)hipFuncGetAttributes(&fa, k2);
             fprintf(stderr, "features_half_kernel<2>: dynamic LDS %zu B, regs %d, occupancy %d workgroups per CU\n", ldh, fa.numRegs, nb);
         }
-#define SMH_LAUNCH_HALF(NPV, TR, ...)                                                                                     \
-    do {                                                                                                                \
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_half_kernel<NPV, TR, ##__VA_ARGS__>,                   \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh));                      \
-        hipLaunchKernelGGL((features_half_kernel<NPV, TR, ##__VA_ARGS__>), dim3(grid), dim3(512), ldh, st, fp, c->cfg.log_db, probe, S, \
-                           harmb, perc, B, K, T, rows, smh_tiled_frames(T, W), W, shift, nP, fv, patches, w0, x0p, nullptr, nullptr); \
-    } while (0)
-        if (image) {  // (the tools' trace / probe instantiations are time-major only)
-            if (fp.pend <= 2) SMH_LAUNCH_HALF(2, false, false, false, true);
-            else SMH_LAUNCH_HALF(4, false, false, false, true);
-        } else if (probe >> 8) {  // SMH_FEAT_PROBE_PERC: the instantiation with the probe compiled in (outputs invalid)
-            SMH_LAUNCH_HALF(2, false, true);
-        } else if (fp.trace) {
-            if (fp.pend <= 2) SMH_LAUNCH_HALF(2, true);
-            else SMH_LAUNCH_HALF(4, true);
-        } else {
-            if (fp.pend <= 2) SMH_LAUNCH_HALF(2, false);
-            else SMH_LAUNCH_HALF(4, false);
-        }
-#undef SMH_LAUNCH_HALF
-        int rch = smh::launch_status("features_half_kernel");
+        const HalfTool tool = (probe >> 8) ? kProbe : fp.trace ? kTrace : kNoTool;
+        int rch = smh::launch_lds(pick_half_kernel(fp.pend <= 2, rag, image, tool), rag ? "features_half_kernel (ragged)" : "features_half_kernel",
+                                  dim3(grid), dim3(512), ldh, ldh, st, fp, c->cfg.log_db, probe, S, harmb, perc, n, K, kT, rows, Ttiled, po.W,
+                                  po.shift, nP, fv, po.patches, w0, x0p, clips.d_clips, clips.d_list);
         return rch ? rch : 1;
     }
-    if (image) {
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((features_clip_kernel<false, true>), dim3(B), dim3(1024), lds, st, fp, c->cfg.log_db, stop & 15, S, harmb, perc, K, T,
-                           rows, smh_tiled_frames(T, W), W, shift, nP, fv, patches, w0, x0p, nullptr, nullptr);
-    } else {
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(features_clip_kernel<false>, dim3(B), dim3(1024), lds, st, fp, c->cfg.log_db, stop & 15, S, harmb, perc, K, T, rows,
-                           smh_tiled_frames(T, W), W, shift, nP, fv, patches, w0, x0p, nullptr, nullptr);
-    }
-    int rc = smh::launch_status("features_clip_kernel");
+    const size_t lds = clip_image_bytes(rows, T, x0p != nullptr);
+    int rc = smh::launch_lds(pick_clip_kernel(rag, image), rag ? "features_clip_kernel (ragged)" : "features_clip_kernel", dim3(n), dim3(1024),
+                             lds, lds, st, fp, c->cfg.log_db, stop & 15, S, harmb, perc, K, kT, rows, Ttiled, po.W, po.shift, nP, fv,
+                             po.patches, w0, x0p, clips.d_clips, clips.d_list);
     return rc ? rc : 1;
 }
 
-// Clips of different lengths that each fit the LDS image (smh_rag.h): the same two kernels, one workgroup (pair) per list entry.
-int launch_features_rag(const smh_ctx *c, const float *S, const float *harmb, const float *perc, const smh_rag::Clip *d_clips,
-                        const int *d_list, int n, int max_T, int even_T, int W, int shift, float *fv, float *patches, hipStream_t st,
-                        int layout) {
-    if (n <= 0) return SMH_OK;
-    const int K = c->K, rows = c->feat_rows;
-    const FeatPlan fp = feat_plan(c, 1);
-    const bool image = layout == kLayoutImage && patches != nullptr;
-    if (even_T) {
-        const size_t ldh = sizeof(float) * ((size_t)rows * (max_T | 1) + 3 * (size_t)rows) + 64;
-        const unsigned grid = 16u * (unsigned)((n + 7) / 8);
-        const int probe = 16;  // (layer-0 weights are not used here)
-#define SMH_LAUNCH_HALF_RAG(NPV, IMG)                                                                                                \
-    do {                                                                                                                           \
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_half_kernel<NPV, false, false, true, IMG>,                        \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldh));                                 \
-        hipLaunchKernelGGL((features_half_kernel<NPV, false, false, true, IMG>), dim3(grid), dim3(512), ldh, st, fp, c->cfg.log_db, \
-                           probe, S, harmb, perc, n, K, 0, rows, 0, W, shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);   \
-    } while (0)
-        if (fp.pend <= 2) {
-            if (image) SMH_LAUNCH_HALF_RAG(2, true);
-            else SMH_LAUNCH_HALF_RAG(2, false);
-        } else {
-            if (image) SMH_LAUNCH_HALF_RAG(4, true);
-            else SMH_LAUNCH_HALF_RAG(4, false);
-        }
-#undef SMH_LAUNCH_HALF_RAG
-        return smh::launch_status("features_half_kernel (ragged)");
-    }
-    const size_t lds = sizeof(float) * ((size_t)2 * rows * (max_T | 1) + 3 * (size_t)2 * rows) + 128;
-    if (image) {
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((features_clip_kernel<true, true>), dim3(n), dim3(1024), lds, st, fp, c->cfg.log_db, 0, S, harmb, perc, K, 0, rows, 0,
-                           W, shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);
-    } else {
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)features_clip_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(features_clip_kernel<true>, dim3(n), dim3(1024), lds, st, fp, c->cfg.log_db, 0, S, harmb, perc, K, 0, rows, 0, W,
-                           shift, 0, fv, patches, nullptr, nullptr, d_clips, d_list);
-    }
-    return smh::launch_status("features_clip_kernel (ragged)");
-}
-
-int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int T, int W, int shift, int nP,
-                     float *patches, hipStream_t st, const float *w0, float *x0p, void *scratch, size_t scratch_bytes, int layout) {
-    const int rows = c->feat_rows;
+int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int T, const PatchOut &po, hipStream_t st, const float *w0,
+                     float *x0p, void *scratch, size_t scratch_bytes) {
+    const int rows = c->feat_rows, W = po.W, shift = po.shift, nP = po.nP, layout = po.layout;
+    float *patches = po.patches;
     if (x0p && layout != kLayoutTimeMajor) return smh::set_error(SMH_E_INVALID, "the layer-0 feature path writes time-major patches only");
-    const size_t lds = sizeof(float) * ((size_t)rows * (T | 1) + 3 * (size_t)rows);
-    if (x0p && (lds > 150 * 1024 || rows % 4 != 0 || rows > 128))
+    const size_t lds = std_patch_tile_bytes(rows, T);
+    if (x0p && (lds > kStdPatchLimit || rows % 4 != 0 || rows > 128))
         return smh::set_error(SMH_E_INVALID, "smh_features_l0_f32: needs a featuregram half that fits one LDS tile "
                               "(T=%d) and a row count divisible by 4, at most 128 (rows=%d)", T, rows);
-    if (lds > 150 * 1024) {
+    if (lds > kStdPatchLimit) {
         // long clips: the same three steps as separate streaming kernels over a stream-ordered scratch copy
         if (B > 32767) return smh::set_error(SMH_E_INVALID, "B=%d too large for the long-clip path; split the batch", B);
         const size_t half = (size_t)rows * T;
@@ -1440,22 +1415,10 @@ int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int
         if (own) SMH_CHECK_HIP(hipFreeAsync(tmp, st));
         return rc;
     }
-    if (x0p) {
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)std_patch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(std_patch_kernel<true>, dim3(2, B), dim3(kPatchThreads), lds, st, c->cfg.log_db, fv, maxkeys, rows,
-                           T, smh_tiled_frames(T, W), W, shift, nP, patches, w0, x0p);
-        return smh::launch_status("std_patch_kernel<l0>");
-    }
-    if (layout == kLayoutImage && patches) {
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)std_patch_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((std_patch_kernel<false, true>), dim3(2, B), dim3(kPatchThreads), lds, st, c->cfg.log_db, fv, maxkeys, rows, T,
-                           smh_tiled_frames(T, W), W, shift, nP, patches, w0, x0p);
-        return smh::launch_status("std_patch_kernel<image>");
-    }
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)std_patch_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(std_patch_kernel<false>, dim3(2, B), dim3(kPatchThreads), lds, st, c->cfg.log_db, fv, maxkeys, rows, T,
-                       smh_tiled_frames(T, W), W, shift, nP, patches, w0, x0p);
-    return smh::launch_status("std_patch_kernel");
+    const bool image = layout == kLayoutImage && patches;
+    return smh::launch_lds(pick_std_patch_kernel(x0p != nullptr, image), x0p ? "std_patch_kernel<l0>" : image ? "std_patch_kernel<image>" : "std_patch_kernel",
+                           dim3(2, B), dim3(kPatchThreads), lds, lds, st, c->cfg.log_db, fv, maxkeys, rows, T, smh_tiled_frames(T, W), W, shift,
+                           nP, patches, w0, x0p);
 }
 
 }  // namespace smh_feat

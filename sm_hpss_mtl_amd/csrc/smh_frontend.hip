@@ -12,17 +12,36 @@
 #include "smh_rag.h"
 
 namespace {
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-}  // namespace
-
-namespace smh_rag {  // smh_ragged.hip: the streaming kernels that serve clips beyond the LDS image (feature_route: smh_rag.h)
-size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T);
-int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, int W, int shift, int nP, float *d_fv,
-              float *d_patches, void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout);
-}  // namespace smh_rag
-
-namespace {
+using smh_feat::PatchOut;
+using smh_rag::align_up;
 inline bool layout_ok(int patch_layout) { return patch_layout == smh_feat::kLayoutImage || patch_layout == smh_feat::kLayoutTimeMajor; }
+
+// smh_features_layout_f32 and smh_features_l0_f32 behind their null checks.  `who` is the name their error texts carry; w0 / x0p
+// non-null: layer 0 with it, whose patch geometry counts without a patch buffer and which has nothing to do without patches
+int features_body(const char *who, const char *who_blocked, const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc,
+                  int harm_layout, int B, int T, int W, int shift, int patch_layout, float *d_fv, float *d_patches, const float *d_w0,
+                  float *d_x0p, int32_t *d_maxkeys, void *stream) {
+    const bool l0 = d_x0p != nullptr;
+    SMH_REQUIRE(B >= 0 && B <= 65535 && T >= 1, "%s: bad shape B=%d T=%d", who, B, T);
+    SMH_REQUIRE(harm_layout >= 0 && harm_layout <= 2, "%s: harm_layout must be 0, 1 or 2", who);
+    PatchOut po;
+    int rc = smh_feat::patch_out(who, d_patches, l0, T, W, shift, patch_layout, po);
+    if (rc) return rc;
+    if (B == 0 || (l0 && po.nP <= 0)) return po.nP;
+    hipStream_t st = (hipStream_t)stream;
+    if (harm_layout == 2) {
+        int rc2 = smh_feat::launch_features_image(ctx, d_S, d_harm, d_perc, {B, T, nullptr, nullptr, 0}, po, d_fv, d_w0, d_x0p, st);
+        if (rc2 < 0) return rc2;
+        SMH_REQUIRE(rc2 == 1, "%s: harm_layout 2 needs smh_features_blocked_ok(ctx, T=%d, %d)", who_blocked, T, l0 ? 1 : 0);
+        return po.nP;
+    }
+    rc = smh_feat::launch_hp_feat(ctx, d_S, d_harm, d_perc, harm_layout, B, T, d_fv, (int *)d_maxkeys, st);
+    if (rc) return rc;
+    // always run: it applies the top_db clip that completes the featuregram
+    rc = smh_feat::launch_std_patch(ctx, d_fv, (const int *)d_maxkeys, B, T, po, st, d_w0, d_x0p, nullptr, 0);
+    if (rc) return rc;
+    return po.nP;
+}
 }  // namespace
 
 extern "C" int smh_features_layout_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc,
@@ -30,29 +49,8 @@ extern "C" int smh_features_layout_f32(const smh_ctx *ctx, const float *d_S, con
                                        float *d_patches, int32_t *d_maxkeys, void *stream) {
     SMH_REQUIRE(ctx && d_S && d_harm && d_perc && d_fv && d_maxkeys, "smh_features_f32: null argument");
     SMH_REQUIRE(layout_ok(patch_layout), "smh_features_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d", patch_layout);
-    SMH_REQUIRE(B >= 0 && B <= 65535 && T >= 1, "smh_features_f32: bad shape B=%d T=%d", B, T);
-    SMH_REQUIRE(harm_layout >= 0 && harm_layout <= 2, "smh_features_f32: harm_layout must be 0, 1 or 2");
-    int nP = 0;
-    if (d_patches) {
-        SMH_REQUIRE(W >= 1 && shift >= 1, "smh_features_f32: bad patch geometry W=%d shift=%d", W, shift);
-        nP = smh_num_patches(smh_tiled_frames(T, W), W, shift);
-    }
-    if (B == 0) return nP;
-    hipStream_t st = (hipStream_t)stream;
-    if (harm_layout == 2) {
-        int rc2 = smh_feat::launch_features_clip(ctx, d_S, d_harm, d_perc, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP, d_fv,
-                                                 nP > 0 ? d_patches : nullptr, nullptr, nullptr, st, patch_layout);
-        if (rc2 < 0) return rc2;
-        SMH_REQUIRE(rc2 == 1, "smh_features_ex_f32: harm_layout 2 needs smh_features_blocked_ok(ctx, T=%d, 0)", T);
-        return nP;
-    }
-    int rc = smh_feat::launch_hp_feat(ctx, d_S, d_harm, d_perc, harm_layout, B, T, d_fv, (int *)d_maxkeys, st);
-    if (rc) return rc;
-    // always run: it applies the top_db clip that completes the featuregram
-    rc = smh_feat::launch_std_patch(ctx, d_fv, (const int *)d_maxkeys, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP,
-                                    nP > 0 ? d_patches : nullptr, st, nullptr, nullptr, nullptr, 0, patch_layout);
-    if (rc) return rc;
-    return nP;
+    return features_body("smh_features_f32", "smh_features_ex_f32", ctx, d_S, d_harm, d_perc, harm_layout, B, T, W, shift, patch_layout, d_fv,
+                         d_patches, nullptr, nullptr, d_maxkeys, stream);
 }
 
 extern "C" int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc,
@@ -62,14 +60,11 @@ extern "C" int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const f
                                    d_maxkeys, stream);
 }
 
+// smh_feat::features_image_ok, the launcher's own predicate, plus SMH_FEAT_TWO_KERNELS: that switch steers the routers that ask here
+// (feature_route, the ragged planner, pipeline.HotPath); a caller that hands layout-2 medians to smh_features_* still gets the launcher.
 extern "C" int smh_features_blocked_ok(const smh_ctx *ctx, int T, int with_l0) {
-    if (!ctx || T < 1) return 0;
-    const int rows = ctx->feat_rows;
-    if (!ctx->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS") || getenv("SMH_FEAT_TWO_KERNELS")) return 0;
-    if (with_l0 && (rows % 4 != 0 || rows > 128)) return 0;
-    size_t lds = sizeof(float) * ((size_t)2 * rows * (T | 1) + 3 * (size_t)2 * rows) + 128;
-    if (with_l0) lds += sizeof(float) * 2 * rows * 32;  // as launch_features_clip
-    return lds <= 158 * 1024 ? 1 : 0;
+    if (!ctx || T < 1 || getenv("SMH_FEAT_TWO_KERNELS")) return 0;
+    return smh_feat::features_image_ok(ctx, T, with_l0 != 0) ? 1 : 0;
 }
 
 extern "C" size_t smh_harm_buffer_floats(int K, int T) {  // room for every harm layout of one clip
@@ -81,23 +76,8 @@ extern "C" int smh_features_l0_f32(const smh_ctx *ctx, const float *d_S, const f
                                    int harm_layout, int B, int T, int W, int shift, float *d_fv, float *d_patches,
                                    const float *d_w0, float *d_x0p, int32_t *d_maxkeys, void *stream) {
     SMH_REQUIRE(ctx && d_S && d_harm && d_perc && d_fv && d_maxkeys && d_w0 && d_x0p, "smh_features_l0_f32: null argument");
-    SMH_REQUIRE(B >= 0 && B <= 65535 && T >= 1, "smh_features_l0_f32: bad shape B=%d T=%d", B, T);
-    SMH_REQUIRE(harm_layout >= 0 && harm_layout <= 2, "smh_features_l0_f32: harm_layout must be 0, 1 or 2");
-    SMH_REQUIRE(W >= 1 && shift >= 1, "smh_features_l0_f32: bad patch geometry W=%d shift=%d", W, shift);
-    const int nP = smh_num_patches(smh_tiled_frames(T, W), W, shift);
-    if (B == 0 || nP <= 0) return nP;
-    hipStream_t st = (hipStream_t)stream;
-    if (harm_layout == 2) {
-        int rc2 = smh_feat::launch_features_clip(ctx, d_S, d_harm, d_perc, B, T, W, shift, nP, d_fv, d_patches, d_w0, d_x0p, st);
-        if (rc2 < 0) return rc2;
-        SMH_REQUIRE(rc2 == 1, "smh_features_l0_f32: harm_layout 2 needs smh_features_blocked_ok(ctx, T=%d, 1)", T);
-        return nP;
-    }
-    int rc = smh_feat::launch_hp_feat(ctx, d_S, d_harm, d_perc, harm_layout, B, T, d_fv, (int *)d_maxkeys, st);
-    if (rc) return rc;
-    rc = smh_feat::launch_std_patch(ctx, d_fv, (const int *)d_maxkeys, B, T, W, shift, nP, d_patches, st, d_w0, d_x0p);
-    if (rc) return rc;
-    return nP;
+    return features_body("smh_features_l0_f32", "smh_features_l0_f32", ctx, d_S, d_harm, d_perc, harm_layout, B, T, W, shift,
+                         smh_feat::kLayoutTimeMajor, d_fv, d_patches, d_w0, d_x0p, d_maxkeys, stream);
 }
 
 extern "C" int smh_features_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc, int B,
@@ -144,14 +124,12 @@ extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio,
     float *perc = d_perc ? d_perc : (float *)(w + spec);
     float *harm = d_harm ? d_harm : (float *)(w + 2 * spec);
     int32_t *maxkeys = (int32_t *)(w + 2 * spec + hspec);
-    int nP = 0;
-    if (d_patches) {
-        SMH_REQUIRE(W >= 1 && shift >= 1, "smh_frontend_f32: bad patch geometry W=%d shift=%d", W, shift);
-        nP = smh_num_patches(smh_tiled_frames(T, W), W, shift);
-    }
+    PatchOut po;
+    int rc = smh_feat::patch_out("smh_frontend_f32", d_patches, false, T, W, shift, patch_layout, po);
+    if (rc) return rc;
+    const int nP = po.nP;
     if (B == 0) return nP;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
     const int route = smh_rag::feature_route(ctx, T);
     if (!d_S && !d_harm && !d_perc && route == 2) {
         // Clips beyond the LDS image (longer than ~1.6 s at 240 rows), no taps: the streaming kernels of the ragged front end, fed the
@@ -159,14 +137,12 @@ extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio,
         // the one smh_stft_mag_f32 would pick for this batch: the generic one when a clip starts off an 8-byte boundary (odd n_samples
         // and B > 1), whose S differs in the last bits from the specialised kernel's that a lone aligned clip gets.
         const bool aligned8 = ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0;
-        rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, W, shift, nP, d_fv, nP > 0 ? d_patches : nullptr, d_work, work_bytes, aligned8, st,
-                                patch_layout);
+        rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, po, d_fv, d_work, work_bytes, aligned8, st);
         if (rc < 0) return rc;
         if (rc == 1) return nP;
     }
     rc = smh_stft_mag_f32(ctx, d_audio, B, n_samples, S, stream);
     if (rc) return rc;
-    // the harmonic median is written time-major (coalesced stores) unless the caller taps it
     // the harmonic median is written in the layout its consumer reads best unless the caller taps it:
     // 16-frame blocks for the single-kernel feature path, time-major otherwise
     const int want = d_harm ? 0 : (route <= 1 ? 2 : 1);
@@ -175,8 +151,7 @@ extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio,
     if (want == 2 && tm != 2)
         return smh::set_error(SMH_E_INVALID, "smh_frontend_f32: the medians of T=%d wrote harm layout %d, the feature route needs 2", T, tm);
     if (tm == 2) {
-        rc = smh_feat::launch_features_clip(ctx, S, harm, perc, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP, d_fv,
-                                            nP > 0 ? d_patches : nullptr, nullptr, nullptr, st, patch_layout);
+        rc = smh_feat::launch_features_image(ctx, S, harm, perc, {B, T, nullptr, nullptr, 0}, po, d_fv, nullptr, nullptr, st);
         if (rc < 0) return rc;
         if (rc == 1) return nP;
         return smh::set_error(SMH_E_INVALID, "smh_frontend_f32: internal layout mismatch");
@@ -185,9 +160,7 @@ extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio,
     if (rc) return rc;
     // (the workspace's S and perc parts -- 2 * spec bytes at its start, also when the caller took the taps into buffers of its own --
     // are dead behind the feature kernel: the long-clip patch path standardises into them instead of allocating per call)
-    rc = smh_feat::launch_std_patch(ctx, d_fv, (const int *)maxkeys, B, T, W > 0 ? W : 1, shift > 0 ? shift : 1, nP,
-                                    nP > 0 ? d_patches : nullptr, st, nullptr, nullptr, (d_S || d_perc) ? nullptr : w, 2 * spec,
-                                    patch_layout);
+    rc = smh_feat::launch_std_patch(ctx, d_fv, (const int *)maxkeys, B, T, po, st, nullptr, nullptr, (d_S || d_perc) ? nullptr : w, 2 * spec);
     if (rc) return rc;
     return nP;
 }

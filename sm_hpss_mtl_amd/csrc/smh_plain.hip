@@ -38,6 +38,7 @@ namespace {
 using smh_feat::final_value;
 using smh_feat::floor_of_max;
 using smh_feat::MelTable;
+using smh_feat::PatchOut;
 using smh_feat::xcd_item;
 using smh_rag::align_up;
 using smh_rag::Clip;
@@ -229,21 +230,19 @@ plain_finish_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int
 }
 
 // both kernels over n_clips clips described by g; keys: n_clips ints, zero on entry when the context is a log one
-int launch_pair(const smh_ctx *ctx, const float *S, float *fv, float *patches, int *keys, const Geo &g, int n_clips, int W, int shift,
-                hipStream_t st) {
+int launch_pair(const smh_ctx *ctx, const float *S, float *fv, const PatchOut &po, int *keys, const Geo &g, int n_clips, hipStream_t st) {
     const int K = ctx->K, rows = ctx->feat_rows, log_db = ctx->cfg.log_db ? 1 : 0;
     if (n_clips <= 0 || g.n_items <= 0) return SMH_OK;
     const size_t lds = ctx->n_mels > 0 ? sizeof(float) * (size_t)K * kTile : 0;
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)plain_project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds, 1024)));
     const unsigned gp = (unsigned)(8 * (((long long)g.n_items + 7) / 8));
-    hipLaunchKernelGGL(plain_project_kernel, dim3(gp), dim3(64 * kProjWaves), lds, st, smh_feat::mel_table(ctx), S, K, rows, log_db, fv,
-                       keys, g);
-    int rc = smh::launch_status("plain_project_kernel");
+    // (the attribute never below 1024: a spectrogram context launches with no dynamic LDS at all)
+    int rc = smh::launch_lds(plain_project_kernel, "plain_project_kernel", dim3(gp), dim3(64 * kProjWaves), lds, std::max<size_t>(lds, 1024), st,
+                             smh_feat::mel_table(ctx), S, K, rows, log_db, fv, keys, g);
     if (rc) return rc;
-    if (!log_db && !patches) return SMH_OK;
+    if (!log_db && !po.patches) return SMH_OK;
     const int nrb = (rows + kRowBlock - 1) / kRowBlock;
     hipLaunchKernelGGL(plain_finish_kernel, dim3((unsigned)n_clips * (unsigned)nrb), dim3(64 * kFinWaves), 0, st, fv, (const int *)keys,
-                       log_db, K, rows, nrb, W > 0 ? W : 1, shift > 0 ? shift : 1, patches, g);
+                       log_db, K, rows, nrb, po.W, po.shift, po.patches, g);
     return smh::launch_status("plain_finish_kernel");
 }
 
@@ -261,22 +260,20 @@ extern "C" int smh_plain_features_f32(const smh_ctx *ctx, const float *d_S, int 
     SMH_REQUIRE(B >= 0 && B <= 65535 && T >= 1, "smh_plain_features_f32: bad shape B=%d T=%d", B, T);
     int rc = check_context(ctx, "smh_plain_features_f32");
     if (rc) return rc;
-    int nP = 0;
-    if (d_patches) {
-        SMH_REQUIRE(W >= 1 && shift >= 1, "smh_plain_features_f32: bad patch geometry W=%d shift=%d", W, shift);
-        nP = smh_num_patches(smh_tiled_frames(T, W), W, shift);
-    }
-    if (B == 0) return nP;
+    PatchOut po;
+    rc = smh_feat::patch_out("smh_plain_features_f32", d_patches, false, T, W, shift, smh_feat::kLayoutTimeMajor, po);
+    if (rc) return rc;
+    if (B == 0) return po.nP;
     const int ntiles = (T + kTile - 1) / kTile;
     SMH_REQUIRE((long long)B * ntiles < (1ll << 31) - 8, "smh_plain_features_f32: B=%d clips of T=%d frames exceed one grid", B, T);
     hipStream_t st = (hipStream_t)stream;
     if (ctx->cfg.log_db) SMH_CHECK_HIP(hipMemsetAsync(d_maxkeys, 0, (size_t)B * sizeof(int32_t), st));
     Geo g;
     g.clips = nullptr, g.items = nullptr, g.n_items = B * ntiles;
-    g.T = T, g.Ttiled = smh_tiled_frames(T, W > 0 ? W : 1), g.nP = nP, g.ntiles = ntiles;
-    rc = launch_pair(ctx, d_S, d_fv, nP > 0 ? d_patches : nullptr, (int *)d_maxkeys, g, B, W, shift, st);
+    g.T = T, g.Ttiled = smh_tiled_frames(T, po.W), g.nP = po.nP, g.ntiles = ntiles;
+    rc = launch_pair(ctx, d_S, d_fv, po, (int *)d_maxkeys, g, B, st);
     if (rc) return rc;
-    return nP;
+    return po.nP;
 }
 
 extern "C" size_t smh_plain_frontend_workspace_bytes(const smh_ctx *ctx, int B, int n_samples) {
@@ -319,10 +316,10 @@ size_t plain_clip_bytes(const smh_ctx *ctx, int T) {
 }
 constexpr size_t kPlainFixedBytes = 6 * 256;  // alignment slack between the regions of a sub-batch
 
-int plain_sub_batch(const smh_ctx *ctx, const float *d_audio, const HostClip *hc, int n, int W, int shift, float *d_fv,
-                    float *d_patches, char *d_work, size_t work_bytes, hipStream_t st) {
+int plain_sub_batch(const smh_ctx *ctx, const float *d_audio, const HostClip *hc, int n, const PatchOut &po, float *d_fv, char *d_work,
+                    size_t work_bytes, hipStream_t st) {
     std::vector<Clip> clips;
-    const size_t spec = smh_rag::fill_clips(hc, n, ctx->K, d_patches != nullptr, clips);
+    const size_t spec = smh_rag::fill_clips(hc, n, ctx->K, po.patches != nullptr, clips);
     // the tables: [clips][stft items][projection items][max keys = 0]
     smh_rag::Tables t;
     Geo g;
@@ -338,7 +335,7 @@ int plain_sub_batch(const smh_ctx *ctx, const float *d_audio, const HostClip *hc
     rc = smh_stft::launch_rag(ctx, d_audio, d_S, g.clips, t.at<const Item>(o_stft), n_stft, true, st);
     if (rc) return rc;
     g.T = g.Ttiled = g.nP = g.ntiles = 0;
-    return launch_pair(ctx, d_S, d_fv, d_patches, t.at<int>(o_keys), g, n, W, shift, st);
+    return launch_pair(ctx, d_S, d_fv, po, t.at<int>(o_keys), g, n, st);
 }
 
 // the specialised n_fft = 400 STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when
@@ -376,9 +373,11 @@ extern "C" int smh_plain_frontend_ragged_f32(const smh_ctx *ctx, const float *d_
                                              void *d_work, size_t work_bytes, void *stream) {
     SMH_REQUIRE(ctx && d_audio && d_fv && d_work && h_offsets && h_lengths && B >= 0, "smh_plain_frontend_ragged_f32: bad argument");
     const bool patches = d_patches != nullptr;
-    SMH_REQUIRE(!patches || (W >= 1 && shift >= 1), "smh_plain_frontend_ragged_f32: bad patch geometry W=%d shift=%d", W, shift);
+    PatchOut po;
+    int rc = smh_feat::patch_out("smh_plain_frontend_ragged_f32", d_patches, false, 0, W, shift, smh_feat::kLayoutTimeMajor, po);
+    if (rc) return rc;
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0, "smh_plain_frontend_ragged_f32: the workspace must start on a 16-byte boundary");
-    int rc = check_context(ctx, "smh_plain_frontend_ragged_f32");
+    rc = check_context(ctx, "smh_plain_frontend_ragged_f32");
     if (rc) return rc;
     Layout p;
     rc = smh_rag::plan_layout(ctx, "plain ragged", h_offsets, h_lengths, B, W, shift, patches, ctx->feat_rows, p);
@@ -388,10 +387,10 @@ extern "C" int smh_plain_frontend_ragged_f32(const smh_ctx *ctx, const float *d_
     std::vector<HostClip> hc;
     hc.reserve(B);
     for (int b = 0; b < B; ++b)
-        if (taken(b)) hc.push_back(smh_rag::host_clip(p, h_offsets, b, W, 0));
+        if (taken(b)) hc.push_back(smh_rag::host_clip(p, h_offsets, b, po.W, 0));
     rc = smh_rag::run_sub_batches(
         hc.size(), kPlainFixedBytes, work_bytes, st, [&](size_t b) { return plain_clip_bytes(ctx, hc[b].T); }, [&](size_t b0, size_t nb) {
-            return plain_sub_batch(ctx, d_audio, hc.data() + b0, (int)nb, W, shift, d_fv, d_patches, (char *)d_work, work_bytes, st);
+            return plain_sub_batch(ctx, d_audio, hc.data() + b0, (int)nb, po, d_fv, (char *)d_work, work_bytes, st);
         });
     if (rc) return rc;
     // the clips off an 8-byte boundary, through smh_plain_frontend_f32 (the workspace is free again in stream order)

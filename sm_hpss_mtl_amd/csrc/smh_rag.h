@@ -11,6 +11,10 @@
 
 #include "smh_common.h"
 
+namespace smh_feat {
+struct PatchOut;  // smh_feat.h: where a call's patches go
+}
+
 namespace smh_rag {
 
 // one clip of a ragged call (64 bytes; offsets in floats from the call's base pointers)
@@ -38,6 +42,11 @@ struct Item {
 //   0  the LDS image, even T: features_half_kernel      1  the LDS image, odd T (or SMH_FEAT_NOPAIR): features_clip_kernel
 //   2  the streaming kernels of smh_ragged.hip           3  neither: launch_hp_feat + launch_std_patch on the whole clip
 int feature_route(const smh_ctx *ctx, int T);
+// smh_frontend_f32's route 2 for B equal clips: the streaming kernels of smh_ragged.hip on the tables of B equal clips (returns 1 if
+// it ran, 0 if this context or shape has no ragged kernels, < 0 on error), and what that adds to the workspace
+size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T);
+int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, const smh_feat::PatchOut &po, float *d_fv, void *d_work,
+              size_t work_bytes, bool stft_aligned8, hipStream_t st);
 
 // ---- the host-side planner of a ragged entry (smh_frontend_ragged_*, smh_plain_frontend_ragged_*) -------------------------------
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -60,7 +69,7 @@ struct HostClip {  // one clip a sub-batch takes
     int T, Ttiled, nP;
     int cls;  // the front end's own class of the clip (smh_ragged.hip: the feature route; unused by smh_plain.hip)
 };
-HostClip host_clip(const Layout &p, const long long *off, int b, int W, int cls);
+HostClip host_clip(const Layout &p, const long long *off, int b, int W /* >= 1: PatchOut's */, int cls);
 // the descriptors of a sub-batch (harm_off and row0 stay 0); returns the floats of S: the sum of K * T, each rounded up to 4
 size_t fill_clips(const HostClip *hc, int n, int K, bool patches, std::vector<Clip> &clips);
 
@@ -120,11 +129,3 @@ bool blocked_harm_ok(int K, int T, int lh, int lp);
 int launch_rag(const float *d_S, float *d_harm, float *d_perc, int K, int lh, int lp, const smh_rag::Clip *d_clips,
                const smh_rag::Item *d_items, int n_items, hipStream_t st);
 }  // namespace smh_median
-
-namespace smh_feat {
-// clips whose featuregram fits an LDS image (smh_features_blocked_ok): the kernels of the equal-length path with per-clip shapes.
-// list: n clip indices, all of even T (even_T != 0: features_half_kernel) or all of odd T (features_clip_kernel); max_T over them.
-int launch_features_rag(const smh_ctx *c, const float *S, const float *harmb, const float *perc, const smh_rag::Clip *d_clips,
-                        const int *d_list, int n, int max_T, int even_T, int W, int shift, float *fv, float *patches, hipStream_t st,
-                        int layout /* smh_feat::kLayoutImage / kLayoutTimeMajor */);
-}  // namespace smh_feat

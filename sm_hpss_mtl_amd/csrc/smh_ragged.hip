@@ -7,7 +7,7 @@
 //
 //   stft400_kernel / stft_mag_kernel      items (clip, 20- or 16-frame tile)          audio -> S            (workspace)
 //   hpss_median_split_kernel              items (clip, 76-frame tile + halo)          S -> harm (16-frame blocked), perc
-//   clips whose featuregram fits an LDS image (T <= 161 for 240 rows; smh_features_blocked_ok):
+//   clips whose featuregram fits an LDS image (smh_feat::clip_image_bytes: T <= 165 for 240 rows; smh_features_blocked_ok):
 //     features_half_kernel<RAG> (even T) / features_clip_kernel<RAG> (odd T): the equal-length path's kernels, shapes per clip
 //   longer clips, three streaming kernels of this file:
 //     rag_walk_kernel     items (clip, 128-frame chunk): soft masks + mel sums -> fv (magnitudes), per-array maximum (atomicMax)
@@ -57,6 +57,7 @@ namespace {
 using smh_feat::FeatPlan;
 using smh_feat::final_value;
 using smh_feat::floor_of_max;
+using smh_feat::PatchOut;
 using smh_feat::xcd_item;
 using smh_rag::align_up;
 using smh_rag::Clip;
@@ -356,6 +357,10 @@ rag_final_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int lo
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
+// this file's rows of the kernel table (smh_feat.hip has the LDS-image kernels'): the instantiations the library holds
+decltype(&rag_walk_kernel<2>) pick_walk_kernel(int pend) { return pend <= 2 ? rag_walk_kernel<2> : rag_walk_kernel<4>; }
+decltype(&rag_final_kernel<false>) pick_final_kernel(bool image) { return image ? rag_final_kernel<true> : rag_final_kernel<false>; }
+
 // (HostClip::cls here: 0: LDS image, even T; 1: LDS image, odd T; 2: streaming kernels)
 struct RagGeom {
     int K, rows, stft_frames, med_frames;
@@ -373,13 +378,13 @@ size_t clip_bytes(const RagGeom &g, const HostClip &c) {
     }
     return 2 * spec + harm + items * sizeof(Item) + extra;
 }
+size_t final_tile_bytes(int rows) { return sizeof(float) * (size_t)2 * rows * (kFinalFrames + 1); }  // rag_final_kernel's [R2][65] tile
 constexpr size_t kFixedBytes = 8 * 256;  // alignment slack between the regions of a sub-batch
 
 bool rag_context_ok(const smh_ctx *ctx) {
     if (!ctx->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS") || getenv("SMH_FEAT_TWO_KERNELS") || getenv("SMH_RAGGED_PERFILE")) return false;
     if (ctx->feat_nseg[1] < 1 || ctx->feat_nseg[1] > 8) return false;
-    const size_t final_lds = sizeof(float) * (size_t)2 * ctx->feat_rows * (kFinalFrames + 1);
-    if (final_lds > 150 * 1024) return false;
+    if (final_tile_bytes(ctx->feat_rows) > 150 * 1024) return false;  // (this tile's own limit, not one of smh_feat.h's image budgets)
     return smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, nullptr) > 0;
 }
 // the block-split walkers fold once per side: window / 2 + 4 < axis length (smh_median.hip: fast_ok)
@@ -390,8 +395,9 @@ bool rag_clip_ok(const smh_ctx *ctx, int T) {
 }
 
 // one sub-batch: tables -> one upload -> one launch per stage
-int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, const HostClip *hc, int n, int W, int shift, float *d_fv,
-                  float *d_patches, char *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout) {
+int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, const HostClip *hc, int n, const PatchOut &po, float *d_fv,
+                  char *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st) {
+    float *const d_patches = po.patches;  // (po.nP is not used here: every kernel below reads a clip's nP from its Clip)
     std::vector<Clip> clips;
     const size_t spec = smh_rag::fill_clips(hc, n, g.K, d_patches != nullptr, clips);
     std::vector<int> list[3];
@@ -438,19 +444,15 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
     // (The LDS-image clips' small grids were tried on a side stream beside the streaming kernels: the fork / join events cost the host
     // 0.4 ms per call and the call got slower, 0.74 -> 1.10 ms per 256 files; everything stays on the caller's stream.)
     for (int k = 0; k < 2; ++k) {  // list 0: even T, list 1: odd T
-        rc = smh_feat::launch_features_rag(ctx, d_S, d_harm, d_perc, d_clips, t.at<const int>(o_list[k]), (int)list[k].size(), max_T[k],
-                                           k == 0, W > 0 ? W : 1, shift > 0 ? shift : 1, d_fv, d_patches, st, layout);
-        if (rc) return rc;
+        rc = smh_feat::launch_features_image(ctx, d_S, d_harm, d_perc, {(int)list[k].size(), max_T[k], d_clips, t.at<const int>(o_list[k]), k == 0},
+                                             po, d_fv, nullptr, nullptr, st);
+        if (rc < 0) return rc;
     }
     if (!list[2].empty()) {
         const FeatPlan fp = smh_feat::feat_plan(ctx, 1);
         const unsigned gw = (unsigned)(8 * ((2 * (long long)n_walk + 7) / 8));
-        if (fp.pend <= 2)
-            hipLaunchKernelGGL(rag_walk_kernel<2>, dim3(gw), dim3(64 * fp.nseg), 0, st, fp, d_S, d_harm, d_perc, g.K, g.rows, d_fv, d_keys,
-                               d_clips, t.at<const Item>(o_walk), n_walk);
-        else
-            hipLaunchKernelGGL(rag_walk_kernel<4>, dim3(gw), dim3(64 * fp.nseg), 0, st, fp, d_S, d_harm, d_perc, g.K, g.rows, d_fv, d_keys,
-                               d_clips, t.at<const Item>(o_walk), n_walk);
+        hipLaunchKernelGGL(pick_walk_kernel(fp.pend), dim3(gw), dim3(64 * fp.nseg), 0, st, fp, d_S, d_harm, d_perc, g.K, g.rows, d_fv, d_keys,
+                           d_clips, t.at<const Item>(o_walk), n_walk);
         rc = smh::launch_status("rag_walk_kernel");
         if (rc) return rc;
         if (d_patches) {
@@ -460,28 +462,19 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
             rc = smh::launch_status("rag_stats_kernel");
             if (rc) return rc;
         }
-        const size_t lds = sizeof(float) * (size_t)2 * g.rows * (kFinalFrames + 1);
+        const size_t lds = final_tile_bytes(g.rows);
         const unsigned gf = (unsigned)(8 * (((long long)n_final + 7) / 8));
-        if (layout == smh_feat::kLayoutImage && d_patches) {
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)rag_final_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(rag_final_kernel<true>, dim3(gf), dim3(512), lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows,
-                               W > 0 ? W : 1, shift > 0 ? shift : 1, d_patches, (const float4 *)d_stats, d_clips, t.at<const Item>(o_final),
-                               n_final);
-        } else {
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)rag_final_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(rag_final_kernel<false>, dim3(gf), dim3(512), lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows,
-                               W > 0 ? W : 1, shift > 0 ? shift : 1, d_patches, (const float4 *)d_stats, d_clips, t.at<const Item>(o_final),
-                               n_final);
-        }
-        rc = smh::launch_status("rag_final_kernel");
+        rc = smh::launch_lds(pick_final_kernel(po.layout == smh_feat::kLayoutImage && d_patches), "rag_final_kernel", dim3(gf), dim3(512), lds,
+                             lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows, po.W, po.shift, d_patches, (const float4 *)d_stats,
+                             d_clips, t.at<const Item>(o_final), n_final);
         if (rc) return rc;
     }
     return SMH_OK;
 }
 
 // all clips of `hc` through the ragged kernels, in as few sub-batches as the workspace allows
-int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip> &hc, int W, int shift, float *d_fv, float *d_patches,
-            void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout) {
+int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip> &hc, const PatchOut &po, float *d_fv, void *d_work,
+            size_t work_bytes, bool stft_aligned8, hipStream_t st) {
     if (hc.empty()) return SMH_OK;
     RagGeom g;
     g.K = ctx->K, g.rows = ctx->feat_rows;
@@ -490,8 +483,7 @@ int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip
     SMH_REQUIRE(g.med_frames > 0, "ragged front end: no median kernel for this context");
     return smh_rag::run_sub_batches(
         hc.size(), kFixedBytes, work_bytes, st, [&](size_t b) { return clip_bytes(g, hc[b]); }, [&](size_t b0, size_t nb) {
-            return run_sub_batch(ctx, g, d_audio, hc.data() + b0, (int)nb, W, shift, d_fv, d_patches, (char *)d_work, work_bytes,
-                                 stft_aligned8, st, layout);
+            return run_sub_batch(ctx, g, d_audio, hc.data() + b0, (int)nb, po, d_fv, (char *)d_work, work_bytes, stft_aligned8, st);
         });
 }
 
@@ -532,7 +524,7 @@ size_t work_size(int B, size_t single, size_t total) {
 }
 
 HostClip host_clip(const Layout &p, const long long *off, int b, int W, int cls) {
-    return {off[b], p.fv_off[b], p.patch_off[b], p.T[b], smh_tiled_frames(p.T[b], W > 0 ? W : 1), p.nP[b], cls};
+    return {off[b], p.fv_off[b], p.patch_off[b], p.T[b], smh_tiled_frames(p.T[b], W), p.nP[b], cls};
 }
 
 size_t fill_clips(const HostClip *hc, int n, int K, bool patches, std::vector<Clip> &clips) {
@@ -608,8 +600,7 @@ int run_alone(const Layout &p, int B, int W, int shift, int fv_rows, float *d_fv
     return SMH_OK;
 }
 
-// smh_frontend_f32's route for B equal clips beyond the LDS image: the streaming kernels above (returns 1 if it ran, 0 if this
-// context or shape has no ragged kernels, < 0 on error)
+// ---- smh_frontend_f32's route for B equal clips beyond the LDS image (smh_rag.h) -----------------------------------------------
 size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T) {
     RagGeom g;
     g.K = ctx->K, g.rows = ctx->feat_rows, g.stft_frames = 16, g.med_frames = 16;  // (upper bounds of the item counts)
@@ -620,16 +611,16 @@ size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T) {
     return (size_t)B * (clip_bytes(g, h) - 2 * spec - harm) + kFixedBytes + 4 * 256 + (size_t)B * 16;
 }
 
-int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, int W, int shift, int nP, float *d_fv,
-              float *d_patches, void *d_work, size_t work_bytes, bool stft_aligned8, hipStream_t st, int layout) {
+int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, const PatchOut &po, float *d_fv, void *d_work,
+              size_t work_bytes, bool stft_aligned8, hipStream_t st) {
     if (!rag_context_ok(ctx) || !rag_clip_ok(ctx, T) || (reinterpret_cast<uintptr_t>(d_work) % 16) != 0) return 0;
     const int rows2 = 2 * ctx->feat_rows;
     std::vector<HostClip> hc(B);
     for (int b = 0; b < B; ++b) {
-        hc[b].audio_off = (long long)b * n_samples, hc[b].fv_off = (long long)b * rows2 * T, hc[b].patch_off = (long long)b * nP;
-        hc[b].T = T, hc[b].Ttiled = smh_tiled_frames(T, W > 0 ? W : 1), hc[b].nP = nP, hc[b].cls = 2;
+        hc[b].audio_off = (long long)b * n_samples, hc[b].fv_off = (long long)b * rows2 * T, hc[b].patch_off = (long long)b * po.nP;
+        hc[b].T = T, hc[b].Ttiled = smh_tiled_frames(T, po.W), hc[b].nP = po.nP, hc[b].cls = 2;
     }
-    int rc = run_rag(ctx, d_audio, hc, W, shift, d_fv, d_patches, d_work, work_bytes, stft_aligned8, st, layout);
+    int rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, stft_aligned8, st);
     return rc ? rc : 1;
 }
 
@@ -707,10 +698,12 @@ extern "C" int smh_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d
     SMH_REQUIRE(patch_layout == smh_feat::kLayoutImage || patch_layout == smh_feat::kLayoutTimeMajor,
                 "smh_frontend_ragged_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d", patch_layout);
     const bool patches = d_patches != nullptr;
-    SMH_REQUIRE(!patches || (W >= 1 && shift >= 1), "smh_frontend_ragged_f32: bad patch geometry W=%d shift=%d", W, shift);
+    PatchOut po;
+    int rc = smh_feat::patch_out("smh_frontend_ragged_f32", d_patches, false, 0, W, shift, patch_layout, po);
+    if (rc) return rc;
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0, "smh_frontend_ragged_f32: the workspace must start on a 16-byte boundary");
     Layout p;
-    int rc = smh_rag::plan_layout(ctx, "ragged", h_offsets, h_lengths, B, W, shift, patches, 2 * ctx->feat_rows, p);
+    rc = smh_rag::plan_layout(ctx, "ragged", h_offsets, h_lengths, B, W, shift, patches, 2 * ctx->feat_rows, p);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     std::vector<int> cls;
@@ -718,8 +711,8 @@ extern "C" int smh_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d
     std::vector<HostClip> hc;
     hc.reserve(B);
     for (int b = 0; b < B; ++b)
-        if (cls[b] >= 0) hc.push_back(smh_rag::host_clip(p, h_offsets, b, W, cls[b]));
-    rc = run_rag(ctx, d_audio, hc, W, shift, d_fv, d_patches, d_work, work_bytes, true, st, patch_layout);
+        if (cls[b] >= 0) hc.push_back(smh_rag::host_clip(p, h_offsets, b, po.W, cls[b]));
+    rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, true, st);
     if (rc) return rc;
     // the clips no ragged kernel covers, one by one on the same stream (the workspace is free again in stream order)
     return smh_rag::run_alone(p, B, W, shift, 2 * ctx->feat_rows, d_fv, d_patches, [&](int b) { return cls[b] >= 0; },

@@ -5,6 +5,7 @@ libsmh.so.  Inputs/outputs are float32 CUDA(=HIP) tensors, spectrogram-like tens
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from dataclasses import dataclass
 
@@ -148,6 +149,17 @@ def _f32c(t, name):
     return t.contiguous()
 
 
+# What differs between the harmonic-percussive (True) and the plain front end in Frontend.run / run_ragged: featuregram rows per
+# feat_rows, taps, the four entries, the label a ragged error carries, and whether the entries take a patch layout behind `shift`.
+_Family = collections.namedtuple("_Family", "row_mult taps workspace equal ragged_sizes ragged ragged_label takes_layout")
+_FAMILIES = {
+    True: _Family(2, ("S", "harm", "perc"), "smh_frontend_workspace_bytes", "smh_frontend_layout_f32", "smh_frontend_ragged_sizes",
+                  "smh_frontend_ragged_layout_f32", "smh_frontend_ragged_f32", True),
+    False: _Family(1, ("S",), "smh_plain_frontend_workspace_bytes", "smh_plain_frontend_f32", "smh_plain_frontend_ragged_sizes",
+                   "smh_plain_frontend_ragged_f32", "smh_plain_frontend_ragged_f32", False),
+}
+
+
 class Frontend:
     """Owns one `smh_ctx` (window, FFT twiddles, mel CSR tables) for a fixed configuration."""
 
@@ -162,6 +174,7 @@ class Frontend:
         self.K = 1 + cfg.n_fft // 2
         self.rows = self.lib.smh_ctx_feat_rows(self._h)
         self._work = None
+        self._family = _FAMILIES[bool(cfg.hpss)]
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -341,28 +354,24 @@ class Frontend:
         return {"fv": fv, "patches": patches, "n_patches": nP, "maxkeys": keys}
 
     # ---- fused fast path ----
-    def _plain_layout(self, layout):
+    def _geometry(self, W, shift, layout):
+        """The (W, shift[, patch layout]) arguments of this configuration's fused entries."""
         lay = _layout(layout)
-        if not self.cfg.hpss and layout != "time_major":
+        if self._family.takes_layout:
+            return (W or 0, shift or 0, lay)
+        if layout != "time_major":
             raise ValueError("the plain front end (hpss=False) writes time-major patches only; layout=%r needs a harmonic-percussive "
                              "configuration" % (layout,))
-        return lay
+        return (W or 0, shift or 0)
 
     def run(self, audio, W=None, shift=None, taps=False, out=None, layout="time_major"):
         """audio (B, n_samples) -> dict(fv=(B, 2*rows, T)[, patches=(B*nP, W, 2*rows)][, S, harm, perc]).
         layout="image": patches=(B*nP, 2*rows, W), the Conv2D models' images, written by the same kernels (no transpose pass).
         `out` may carry preallocated 'fv' / 'patches' tensors (steady-state loops allocate nothing).
         A plain configuration (hpss=False) gives fv=(B, rows, T) and patches=(B*nP, W, rows), time-major only; its only tap is S."""
-        lay = self._plain_layout(layout)
-        # what differs between the two front ends: the featuregram's rows, the workspace / entry pair and the taps
-        if self.cfg.hpss:
-            F, names = 2 * self.rows, ("S", "harm", "perc")
-            work_bytes, label = self.lib.smh_frontend_workspace_bytes, "smh_frontend_layout_f32"
-            entry = lambda h, a, B_, N_, W_, sh, *rest: self.lib.smh_frontend_layout_f32(h, a, B_, N_, W_, sh, lay, *rest)
-        else:
-            F, names = self.rows, ("S",)
-            work_bytes, entry, label = (self.lib.smh_plain_frontend_workspace_bytes, self.lib.smh_plain_frontend_f32,
-                                        "smh_plain_frontend_f32")
+        fam = self._family
+        geom = self._geometry(W, shift, layout)
+        F, names = fam.row_mult * self.rows, fam.taps
         audio = _f32c(audio, "audio")
         B, N = audio.shape
         T = self.num_frames(N)
@@ -379,12 +388,13 @@ class Frontend:
             patches = out.get("patches")
             if patches is None or patches.shape != _patch_shape(B * nP, W, F, layout):
                 patches = torch.empty(_patch_shape(B * nP, W, F, layout), dtype=torch.float32, device=dev)
-        need = work_bytes(self._h, B, N)
+        need = getattr(self.lib, fam.workspace)(self._h, B, N)
         if self._work is None or self._work.numel() < need or self._work.device != dev:
             self._work = torch.empty(need if self.cfg.hpss else max(need, 1), dtype=torch.uint8, device=dev)
         tap = {k: torch.empty((B, self.K, T), dtype=torch.float32, device=dev) for k in names} if taps else {}
-        got = _lib.check(entry(self._h, _ptr(audio), B, N, W or 0, shift or 0, _ptr(fv), _ptr(patches) if nP else None,
-                               _ptr(self._work), self._work.numel(), *(_ptr(tap.get(k)) for k in names), _stream()), label)
+        got = _lib.check(getattr(self.lib, fam.equal)(self._h, _ptr(audio), B, N, *geom, _ptr(fv), _ptr(patches) if nP else None,
+                                                      _ptr(self._work), self._work.numel(), *(_ptr(tap.get(k)) for k in names),
+                                                      _stream()), fam.equal)
         assert got == nP, (got, nP)
         res = {"fv": fv, "n_patches": nP}
         if W is not None:
@@ -400,7 +410,7 @@ class Frontend:
         the clips are laid out at 16-byte aligned offsets, so each takes the same kernels as there.  (Not an equal-length
         batch of an odd number of samples: its clips start off 8-byte boundaries and take the generic STFT kernel, whose S
         differs from the specialised kernel's in the last bits.)"""
-        lay = self._plain_layout(layout)
+        fam, geom = self._family, self._geometry(W, shift, layout)
         B = len(clips)
         if B == 0:
             return {"fv": [], "patches": [], "n_patches": [], "T": []}
@@ -430,19 +440,16 @@ class Frontend:
         hT, hnP = (C.c_int * B)(), (C.c_int * B)()
         work = C.c_size_t()
         # a plain configuration (hpss=False) takes the plain pair of entries: same contract, (rows, T_b) and (nP_b, W, rows) per clip
-        stem = "smh_frontend_ragged" if self.cfg.hpss else "smh_plain_frontend_ragged"
-        sizes, ragged = getattr(self.lib, stem + "_sizes"), getattr(self.lib, stem + "_f32")
-        if self.cfg.hpss:
-            ragged = lambda h, a, o_, l_, B_, W_, sh, *rest: self.lib.smh_frontend_ragged_layout_f32(h, a, o_, l_, B_, W_, sh, lay, *rest)
-        _lib.check(sizes(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP, C.byref(work)), stem + "_sizes")
-        F = (2 if self.cfg.hpss else 1) * self.rows
+        _lib.check(getattr(self.lib, fam.ragged_sizes)(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP,
+                                                       C.byref(work)), fam.ragged_sizes)
+        F = fam.row_mult * self.rows
         fv = torch.empty(max(int(fv_off[B]), 1), dtype=torch.float32, device=dev)
         patches = torch.empty(_patch_shape(max(int(p_off[B]), 1), W or 1, F, layout), dtype=torch.float32, device=dev) if W else None
         if self._work is None or self._work.numel() < work.value or self._work.device != dev:
             self._work = torch.empty(max(work.value, 1), dtype=torch.uint8, device=dev)
-        _lib.check(ragged(self._h, _ptr(audio), h_off, h_len, B, W or 0, shift or 0, _ptr(fv),
-                          _ptr(patches) if (W and int(p_off[B]) > 0) else None, _ptr(self._work), self._work.numel(), _stream()),
-                   stem + "_f32")
+        _lib.check(getattr(self.lib, fam.ragged)(self._h, _ptr(audio), h_off, h_len, B, *geom, _ptr(fv),
+                                                 _ptr(patches) if (W and int(p_off[B]) > 0) else None, _ptr(self._work),
+                                                 self._work.numel(), _stream()), fam.ragged_label)
         res = {"fv": [fv[int(fv_off[b]):int(fv_off[b + 1])].view(F, int(hT[b])) for b in range(B)],
                "T": [int(hT[b]) for b in range(B)], "n_patches": [int(hnP[b]) for b in range(B)]}
         if W:
