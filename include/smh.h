@@ -167,7 +167,7 @@ int smh_features_ex_f32(const smh_ctx *ctx, const float *d_S, const float *d_har
  * smh_frontend_ragged_layout_f32 are smh_features_ex_f32, smh_frontend_f32 and smh_frontend_ragged_f32 with that one argument
  * more; the old entries call them with 1.  Any other value returns SMH_E_INVALID (text in smh_last_error) before any launch.
  * smh_frontend_ragged_sizes serves both: h_patch_off counts patches, and a patch is W * 2*rows floats in either layout.
- * (The layer-0 entry smh_features_l0_f32 and the smh_plain_* entries write time-major patches only.)                          */
+ * (The layer-0 entry smh_features_l0_f32 writes time-major patches only; the plain front end has layout entries of its own below.) */
 int smh_features_layout_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc, int harm_layout,
                             int B, int T, int W, int shift, int patch_layout, float *d_fv, float *d_patches,
                             int32_t *d_maxkeys, void *stream);
@@ -227,6 +227,12 @@ int smh_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long
  * smh_plain_frontend_ragged_sizes / _f32: the contract of smh_frontend_ragged_sizes / smh_frontend_ragged_f32 above -- host offset and
  *   length tables, one launch per stage over all clips, concatenated outputs, sub-batches when the workspace is smaller than asked
  *   for -- with h_fv_off counting rows * T_b floats per clip and patches of (W, rows) floats.
+ * smh_plain_features_layout_f32 / smh_plain_frontend_layout_f32 / smh_plain_frontend_ragged_layout_f32: the three entries above with
+ *   one argument more, patch_layout, numbered as for the harmonic-percussive entries: 0 = image (B*nP, rows, W), frame index fastest,
+ *   what get_feature_patches returns and the single-task Conv2D baselines read before np.expand_dims(.., axis=3); 1 = time-major
+ *   (B*nP, W, rows).  The same f32 values at other addresses, written by the finishing kernel itself (no transpose pass); the
+ *   featuregram is the same bits.  The old entries call these with 1.  smh_plain_frontend_ragged_sizes serves both: a patch is
+ *   W * rows floats in either layout.  Any other patch_layout is SMH_E_INVALID before any launch.
  * Bad arguments return SMH_E_INVALID (text in smh_last_error) before any launch. */
 int smh_plain_features_f32(const smh_ctx *ctx, const float *d_S, int B, int T, int W, int shift, float *d_fv,
                            float *d_patches /* or NULL */, int32_t *d_maxkeys /* B */, void *stream);
@@ -239,6 +245,14 @@ int smh_plain_frontend_ragged_sizes(const smh_ctx *ctx, const long long *h_offse
 int smh_plain_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets, const int *h_lengths, int B,
                                   int W, int shift, float *d_fv, float *d_patches /* or NULL */, void *d_work, size_t work_bytes,
                                   void *stream);
+int smh_plain_features_layout_f32(const smh_ctx *ctx, const float *d_S, int B, int T, int W, int shift, int patch_layout, float *d_fv,
+                                  float *d_patches /* or NULL */, int32_t *d_maxkeys /* B */, void *stream);
+int smh_plain_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int W, int shift, int patch_layout,
+                                  float *d_fv, float *d_patches /* or NULL */, void *d_work, size_t work_bytes,
+                                  float *d_S /* or NULL */, void *stream);
+int smh_plain_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets, const int *h_lengths,
+                                         int B, int W, int shift, int patch_layout, float *d_fv, float *d_patches /* or NULL */,
+                                         void *d_work, size_t work_bytes, void *stream);
 
 /* ---- 8f rank 1: load_and_preprocess_signal after the decode (lib/preprocessing.py:330-350) ------------------
  * Batched over B clips of N samples each, resident on the device.  Floating point: the mean is accumulated in
@@ -427,13 +441,24 @@ int smh_model_get_weights(const smh_model *m, float *h_flat, size_t n, void *str
  * get_feature_patches for the non-Lemaire models (lib/preprocessing.py:216-217,226-227).  Output row =
  * [S | M | (N) | R | 3C], like smh_model_forward_f32.  Weights: one flat float32 vector, tensors in the order
  * reported by smh_cnn_tensor_info (Keras layouts: Conv2D (kh,kw,Cin,Cout), Dense (in,out), BN gamma/beta/mean/var). */
-enum { SMH_CNN_DOUKHAN = 0, SMH_CNN_PAPAKOSTAS = 1, SMH_CNN_JANG = 2 };
+enum { SMH_CNN_DOUKHAN = 0, SMH_CNN_PAPAKOSTAS = 1, SMH_CNN_JANG = 2,
+       /* the single-task baselines of lib/baseline_architectures.py (get_Doukhan_model :62-108, get_Papakostas_model :147-175,
+        * get_Jang_model :358-442): no S / M / R heads (n_heads = 0), n_classes 2 or 3, out_dim = n_classes -- a row of d_out is the
+        * softmax alone.  The last tensors are 'dense/kernel' (D, n_classes) and 'dense/bias', in the slot the MTL kinds call '3C'.
+        * Doukhan / Papakostas: the MTL kinds' trunks; any input whose layers all keep one output pixel (the reference's Doukhan
+        * input is 21 x 68).  Jang: ONE mel-scale layer over the whole (n_fft/2 + 1, W) image -- tensors 'melCl{i}/kernel', n_mels
+        * 0 = 64 -- then tanh, three times [Conv2D 3x3 'same' + BN + ReLU + Dropout(0.4) + MaxPooling2D 2x2 'valid'], Flatten, the
+        * Dense; kernel_regularizer = l1_l2() (l1 = l2 = 0.01) on the mel kernels and nowhere else.
+        * Training: d_y (N, n_classes) one-hot; n_classes == 2 is Keras' binary_crossentropy on the two softmax outputs with BINARY
+        * accuracy, 3 categorical (the arithmetic of SMH_HEADS_SINGLE above); d_drop_heads and h_loss_weights may be NULL;
+        * d_losses is four floats [loss, loss, accuracy, penalty]. */
+       SMH_CNN_DOUKHAN_SINGLE = 3, SMH_CNN_PAPAKOSTAS_SINGLE = 4, SMH_CNN_JANG_SINGLE = 5 };
 typedef struct smh_cnn_cfg {
     int32_t kind;      /* SMH_CNN_* */
     int32_t in_h;      /* 2*n_mels (Doukhan), 2*(n_fft/2+1) (Papakostas, Jang) */
     int32_t in_w;      /* patch width W */
-    int32_t n_classes; /* 3 or 5 */
-    int32_t n_mels;    /* Jang: mel-scale kernels per half (0 = 120) */
+    int32_t n_classes; /* 3 or 5; the *_SINGLE kinds: 2 or 3 */
+    int32_t n_mels;    /* Jang: mel-scale kernels per half (0 = 120; SMH_CNN_JANG_SINGLE: 0 = 64) */
     int32_t n_fft;     /* Jang: 0 = 512 */
     int32_t fc_width;  /* Papakostas: width of the two Dense layers (0 = 4096) */
     float fs;          /* Jang: sampling rate of the mel filter bank (0 = 16000) */

@@ -77,6 +77,10 @@ SIGNATURES = {
                                              C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "smh_plain_frontend_ragged_f32": (_i, [_vp, _fp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), _i, _i, _i, _fp, _fp, _vp, _sz,
                                            _vp]),
+    "smh_plain_features_layout_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _vp, _vp]),
+    "smh_plain_frontend_layout_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _vp, _sz, _fp, _vp]),
+    "smh_plain_frontend_ragged_layout_f32": (_i, [_vp, _fp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), _i, _i, _i, _i, _fp, _fp, _vp,
+                                                  _sz, _vp]),
     "smh_internal_frontend_route": (_i, [_vp, _i]),
     "smh_normalize_workspace_bytes": (_sz, [_i, _i]),
     "smh_silence_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -7,7 +7,7 @@
 The layer graph, the parameter table (names, Keras shapes, order) and all arithmetic live in libsmh.so
 (csrc/smh_cnn.hip); this class initialises the weights the way the reference's initialisers do and moves tensors; the
 weight store, the Keras weight surface and `predict` are host.HostModel's, shared with model.B3MTL.  Training (`fit` / `train_on_batch` / `evaluate`, cnn_training.py over
-`smh_cnn_train_step_f32`) is built for all three.
+`smh_cnn_train_step_f32`) is built for all three.  `CnnSingleTask` is the single-task twin of each (lib/baseline_architectures.py).
 """
 from __future__ import annotations
 
@@ -20,9 +20,10 @@ import torch
 
 from . import _lib
 from .cnn_training import CnnTrainingMixin
-from .host import HostModel, f32_cuda, ptr
+from .host import HostModel, SingleOutputMixin, f32_cuda, ptr
 
 KINDS = {"Doukhan": 0, "Papakostas": 1, "Jang": 2}
+SINGLE_KIND_OFFSET = 3  # include/smh.h: SMH_CNN_DOUKHAN_SINGLE / _PAPAKOSTAS_SINGLE / _JANG_SINGLE follow the MTL kinds
 # initial learning rates returned next to the model (proposed_architectures.py:499, 574, 751)
 LEARNING_RATE = {"Doukhan": 0.0001, "Papakostas": 0.001, "Jang": 0.001}
 
@@ -32,6 +33,8 @@ class CnnMTL(CnnTrainingMixin, HostModel):
 
     _C_PREFIX = "smh_cnn"
     _TRAINER_PREFIX = "smh_cnn_trainer"
+    _KIND_OFFSET = 0
+    CLASS_SUFFIX = "_MTL"
 
     def __init__(self, kind, input_shape, n_classes=3, seed=None, n_mels=120, n_fft=512, fs=16000, fc_width=0,
                  loss_weights=None):
@@ -43,7 +46,7 @@ class CnnMTL(CnnTrainingMixin, HostModel):
         if len(input_shape) > 2 and int(input_shape[2]) != 1:
             raise ValueError("input_shape must be (H, W, 1), got %s" % (tuple(input_shape),))
         self.n_mels, self.n_fft, self.fs, self.fc_width = int(n_mels), int(n_fft), float(fs), int(fc_width)
-        cfg = _lib.CnnCfg(KINDS[kind], self.in_h, self.in_w, self.n_classes, self.n_mels, self.n_fft, int(fc_width),
+        cfg = _lib.CnnCfg(KINDS[kind] + self._KIND_OFFSET, self.in_h, self.in_w, self.n_classes, self.n_mels, self.n_fft, int(fc_width),
                           self.fs)
         h = C.c_void_p()
         _lib.check(self.lib.smh_cnn_create(C.byref(cfg), C.byref(h)), "smh_cnn_create")
@@ -111,12 +114,12 @@ class CnnMTL(CnnTrainingMixin, HostModel):
         return (None, self.in_h, self.in_w, 1)
 
     def to_json(self):
-        return json.dumps({"class_name": self.kind + "_MTL", "config": {
+        return json.dumps({"class_name": self.kind + self.CLASS_SUFFIX, "config": {
             "input_shape": [self.in_h, self.in_w, 1], "n_classes": self.n_classes, "n_mels": self.n_mels,
             "n_fft": self.n_fft, "fs": self.fs, "fc_width": self.fc_width, "outputs": self.output_names}})
 
     def summary(self, print_fn=print):
-        self._summary("Model: %s_MTL, input (None, %d, %d, 1)" % (self.kind, self.in_h, self.in_w), print_fn, width=22)
+        self._summary("Model: %s%s, input (None, %d, %d, 1)" % (self.kind, self.CLASS_SUFFIX, self.in_h, self.in_w), print_fn, width=22)
 
     # ---- inference -----------------------------------------------------------------------------------------------
     def _check_images(self, x):
@@ -140,3 +143,37 @@ class CnnMTL(CnnTrainingMixin, HostModel):
         work = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=x.device)
         self._call("smh_cnn_forward_" + dtype, self._h, ptr(x), N, ptr(out), ptr(features), ptr(work), work.numel())
         return out
+
+
+class CnnSingleTask(SingleOutputMixin, CnnMTL):
+    """`model` object of get_{Doukhan,Papakostas,Jang}_model (lib/baseline_architectures.py:62-108, :147-175, :358-442), baselines 1, 2
+    and 4 of Baseline_Results.py: the Conv2D trunk, then Dense(n_classes) + softmax -- no S / M / R heads.  ONE output 'dense':
+    `predict` returns one (N, n_classes) array, `y` is one one-hot (N, n_classes) array.  n_classes == 2 is compiled with
+    binary_crossentropy on the two softmax outputs (Keras' 'accuracy' is then BINARY accuracy over the N x 2 outputs), 3 with
+    categorical_crossentropy and categorical accuracy (:114-117); metrics_names = ['loss', 'accuracy'] (host.SingleOutputMixin).
+
+    Doukhan and Papakostas are their MTL siblings' trunks; Jang is a graph of its own (ONE mel-scale layer over the whole
+    (n_fft/2 + 1, W) image, 64 mel kernels by default, 'valid' pooling, no FC layers, l1_l2() on the mel kernels alone).
+    Initialisers as the reference's: Doukhan VarianceScaling(1, fan_avg, uniform) and zeros, Papakostas RandomNormal(0.01) and
+    Constant(0.1) on every layer -- the last Dense included (:175) --, Jang the mel Constant kernels and Keras' defaults elsewhere."""
+
+    _KIND_OFFSET = SINGLE_KIND_OFFSET
+    CLASS_SUFFIX = "_SingleTask"
+
+    def __init__(self, kind, input_shape, n_classes=2, seed=None, n_mels=64, n_fft=512, fs=16000, fc_width=0):
+        if n_classes not in (2, 3):
+            raise ValueError("n_classes must be 2 or 3 (the two cases the reference compiles), got %r" % (n_classes,))
+        super().__init__(kind, input_shape, n_classes=n_classes, seed=seed, n_mels=n_mels, n_fft=n_fft, fs=fs, fc_width=fc_width)
+
+    # ---- training surface ----
+    def train_on_batch(self, x, y, drop="auto", apply=True, sync=True):
+        """One optimiser step -> [loss, accuracy].  drop as for CnnMTL.train_on_batch; there are no heads, so no head dropout."""
+        return super().train_on_batch(x, y, drop=drop, drop_heads=None, apply=apply, sync=sync)
+
+    def _l2_penalty(self):
+        """The kernel-regulariser penalty: l1_l2() (Keras defaults l1 = l2 = 0.01) on Jang's mel kernels, nothing else anywhere."""
+        if self.kind != "Jang":
+            return 0.0
+        w = self.get_weights_dict()
+        return float(sum(0.01 * (np.sum(v.astype(np.float64) ** 2) + np.sum(np.abs(v.astype(np.float64))))
+                         for k, v in w.items() if k.startswith("melCl")))

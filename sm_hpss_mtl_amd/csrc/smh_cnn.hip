@@ -2,7 +2,9 @@
 //   get_Doukhan_MTL_model     /root/reference/lib/proposed_architectures.py:425-511
 //   get_Papakostas_MTL_model  /root/reference/lib/proposed_architectures.py:516-588
 //   get_Jang_MTL_model        /root/reference/lib/proposed_architectures.py:650-764 (mel_scale_layer :622-646)
-// with the MTL heads of :25-80, behind the C ABI of include/smh.h (smh_cnn_*).
+// with the MTL heads of :25-80, behind the C ABI of include/smh.h (smh_cnn_*); and of their single-task twins
+//   get_Doukhan_model / get_Papakostas_model / get_Jang_model   lib/baseline_architectures.py:62-108, 147-175, 358-442
+// (kinds SMH_CNN_*_SINGLE: the trunk, Dense(n_classes) + softmax through heads_kernel with zero heads).
 //
 // Design (gfx950): every Conv2D and Dense is ONE implicit-GEMM kernel on the f32 matrix cores
 // (v_mfma_f32_32x32x2f32): rows = output pixels (or samples), columns = output channels, K = kh*kw*Cin.  Keras
@@ -17,7 +19,11 @@
 
 extern "C" int smh_cnn_create(const smh_cnn_cfg *cfg, smh_cnn **out) {
     SMH_REQUIRE(cfg && out, "smh_cnn_create: null argument");
-    SMH_REQUIRE(cfg->n_classes == 3 || cfg->n_classes == 5, "n_classes must be 3 or 5 (got %d)", cfg->n_classes);
+    if (cnn_single(cfg->kind))
+        SMH_REQUIRE(cfg->n_classes == 2 || cfg->n_classes == 3, "n_classes of a single-task Conv2D baseline must be 2 or 3 (got %d)",
+                    cfg->n_classes);
+    else
+        SMH_REQUIRE(cfg->n_classes == 3 || cfg->n_classes == 5, "n_classes must be 3 or 5 (got %d)", cfg->n_classes);
     SMH_REQUIRE(cfg->in_h >= 1 && cfg->in_w >= 1, "smh_cnn_create: bad input shape");
     SMH_REQUIRE(smh_device_count() > 0, "no HIP device visible: libsmh has no CPU path");
     smh_cnn *m = new smh_cnn();
@@ -196,7 +202,8 @@ static int forward_impl(const smh_cnn *m, const float *d_x, int N, float *d_out,
                 a.vec4 = (L.C % 4 == 0) ? 1 : 0;
                 const int bn = L.OC <= 64 ? 64 : 128;
                 const int mt = (a.M + BM - 1) / BM, nt = (L.OC + bn - 1) / bn;
-                a.ksplit = choose_split(mt, nt, L.Kp / BK);  // the same plan for both precisions (workspace sizing)
+                const int mt_plan = (plan_images(m, n) * L.OH * L.OW + BM - 1) / BM;
+                a.ksplit = choose_split(mt_plan, nt, L.Kp / BK);  // the same plan for both precisions (workspace sizing)
                 if (a.ksplit > a.ksteps) a.ksplit = a.ksteps;
                 a.ksteps_per = (a.ksteps + a.ksplit - 1) / a.ksplit;
                 SMH_REQUIRE(L.OC % 4 == 0, "smh_cnn: Cout=%d is not a multiple of 4", L.OC);

@@ -499,6 +499,11 @@ struct Layer {
     int l2 = 0;                          // kernel_regularizer=l2() on this layer's kernel (Jang)
 };
 
+// the single-task baselines (lib/baseline_architectures.py): the trunk, then Dense(n_classes) + softmax, no S / M / R heads
+inline bool cnn_single(int kind) {
+    return kind == SMH_CNN_DOUKHAN_SINGLE || kind == SMH_CNN_PAPAKOSTAS_SINGLE || kind == SMH_CNN_JANG_SINGLE;
+}
+
 }  // namespace
 
 struct smh_cnn {
@@ -515,6 +520,7 @@ struct smh_cnn {
     size_t n_fold = 0;
     int mel_rows = 0, mel_in_rows = 0;
     int c3_l2 = 0;             // Jang: l2() on the '3C' kernel too (proposed_architectures.py:747)
+    int mel_reg = 1;           // optimiser segment kind of the mel-scale kernels: 1 = l2() (Jang MTL), 4 = l1_l2() (Jang single-task)
     // bf16 operand cache of smh_cnn_forward_bf16: every Conv2D / Dense kernel transposed to [Cout][Kp], rebuilt lazily
     mutable void *d_wbf = nullptr;
     mutable bool wbf_valid = false;
@@ -613,6 +619,12 @@ void push_lrn(smh_cnn *m, Cur &c) {
 void add_heads(smh_cnn *m, int D) {
     const int nc = m->cfg.n_classes;
     m->feat_dim = D;
+    if (cnn_single(m->cfg.kind)) {  // Dense(n_classes) + softmax in the '3C' slot, no heads
+        m->t_c3 = add_tensor(m, "dense/kernel", {D, nc});
+        add_tensor(m, "dense/bias", {nc});
+        m->n_heads = 0, m->out_dim = nc;
+        return;
+    }
     m->t_c3 = add_tensor(m, "3C/kernel", {D, nc});
     add_tensor(m, "3C/bias", {nc});
     static const char *names5[] = {"S", "M", "N", "R"};
@@ -672,8 +684,10 @@ void mel_filter_bins(double sr, int n_fft, int n_mels, std::vector<int> &lo, std
 int build_graph(smh_cnn *m, std::vector<MelCl> &mel) {
     const smh_cnn_cfg &c = m->cfg;
     Cur cur{c.in_h, c.in_w, 1};
-    if (c.kind == SMH_CNN_DOUKHAN) {  // proposed_architectures.py:448-492
-        SMH_REQUIRE(c.in_h >= 24 && c.in_w >= 68, "Doukhan MTL needs an input of at least 24 x 68 (got %d x %d)", c.in_h, c.in_w);
+    if (c.kind == SMH_CNN_DOUKHAN || c.kind == SMH_CNN_DOUKHAN_SINGLE) {  // proposed_architectures.py:448-492
+        // (the single-task kind, baseline_architectures.py:62-108, takes the reference's 21 x 68: the check behind the graph decides)
+        if (c.kind == SMH_CNN_DOUKHAN)
+            SMH_REQUIRE(c.in_h >= 24 && c.in_w >= 68, "Doukhan MTL needs an input of at least 24 x 68 (got %d x %d)", c.in_h, c.in_w);
         push_conv(m, cur, "conv1", 4, 5, 64, 1, 1, false, kRelu, "bn1");
         push_pool(m, cur, 2, 2, 2, 2, false);
         push_conv(m, cur, "conv2", 3, 3, 128, 1, 1, false, kRelu, "bn2");
@@ -684,8 +698,9 @@ int build_graph(smh_cnn *m, std::vector<MelCl> &mel) {
         const float drop[4] = {0.2f, 0.3f, 0.4f, 0.5f};  // :477-492
         for (int i = 1; i <= 4; ++i)
             push_dense(m, cur, "fc" + std::to_string(i), 512, kRelu, "fc" + std::to_string(i) + "_bn", drop[i - 1]);
-    } else if (c.kind == SMH_CNN_PAPAKOSTAS) {  // :539-571
-        SMH_REQUIRE(c.in_h >= 29 && c.in_w >= 29, "Papakostas MTL needs an input of at least 29 x 29 (got %d x %d)", c.in_h, c.in_w);
+    } else if (c.kind == SMH_CNN_PAPAKOSTAS || c.kind == SMH_CNN_PAPAKOSTAS_SINGLE) {  // :539-571; baseline_architectures.py:147-175
+        if (c.kind == SMH_CNN_PAPAKOSTAS)
+            SMH_REQUIRE(c.in_h >= 29 && c.in_w >= 29, "Papakostas MTL needs an input of at least 29 x 29 (got %d x %d)", c.in_h, c.in_w);
         const int fc = c.fc_width > 0 ? c.fc_width : 4096;
         SMH_REQUIRE(fc % 4 == 0, "fc_width must be a multiple of 4");
         push_conv(m, cur, "conv1", 5, 5, 96, 2, 2, false, kNone, "");
@@ -728,16 +743,43 @@ int build_graph(smh_cnn *m, std::vector<MelCl> &mel) {
         push_dense(m, cur, "fc1", 2048, kRelu, "fc1_bn", 0.4f, 1);
         push_dense(m, cur, "fc2", 1024, kRelu, "fc2_bn", 0.4f, 1);
         m->c3_l2 = 1;
+    } else if (c.kind == SMH_CNN_JANG_SINGLE) {  // baseline_architectures.py:358-442
+        const int n_fft = c.n_fft > 0 ? c.n_fft : 512, n_mels = c.n_mels > 0 ? c.n_mels : 64;
+        const int Kh = n_fft / 2 + 1, tdim = 5;
+        SMH_REQUIRE(c.in_h == Kh, "Jang single-task: input height %d is not n_fft/2 + 1 = %d", c.in_h, Kh);
+        std::vector<int> lo, hi;
+        mel_filter_bins(c.fs > 0 ? c.fs : 16000.0, n_fft, n_mels, lo, hi);
+        for (int i = 0; i < n_mels; ++i) {  // one mel-scale layer over the whole image: no harmonic / percussive halves
+            SMH_REQUIRE(lo[i] >= 0, "Jang single-task: mel filter %d is empty (the reference fails here too)", i);
+            const int width = hi[i] - lo[i] + 1;
+            const int t = add_tensor(m, "melCl" + std::to_string(i) + "/kernel", {width, tdim, 1, 3});
+            mel.push_back(MelCl{lo[i], width, (int)m->tensors[t].off});
+        }
+        Layer L{};
+        L.op = kMelCl;
+        L.H = c.in_h, L.W = c.in_w, L.C = 1, L.OH = n_mels, L.OW = c.in_w, L.OC = 3, L.kw = tdim;
+        m->layers.push_back(L);
+        m->mel_rows = n_mels, m->mel_in_rows = c.in_h, m->mel_reg = 4;  // l1_l2() on the mel kernels, no other regulariser
+        cur = Cur{n_mels, c.in_w, 3};
+        const int oc[3] = {32, 64, 128};
+        for (int i = 0; i < 3; ++i) {
+            push_conv(m, cur, "conv" + std::to_string(i + 1), 3, 3, oc[i], 1, 1, true, kRelu, "bn" + std::to_string(i + 1), true, 0.4f, 0);
+            push_pool(m, cur, 2, 2, 2, 2, false);
+        }
     } else {
         return smh::set_error(SMH_E_INVALID, "smh_cnn_create: unknown kind %d", c.kind);
     }
     for (const Layer &L : m->layers)
         if (L.OH < 1 || L.OW < 1) return smh::set_error(SMH_E_INVALID, "smh_cnn_create: input %d x %d is too small for this network", c.in_h, c.in_w);
-    add_heads(m, cur.C);
+    add_heads(m, cur.H * cur.W * cur.C);  // (behind a Dense H = W = 1; Jang single-task: Flatten of the NHWC image)
     return SMH_OK;
 }
 
 constexpr int kChunk = 64;  // images per pass through the layer list (bounds the activation workspace)
+// Images the split-K plan of a forward pass of n images is made for.  The single-task kinds plan every pass as a full one: the order
+// in which a row's products are summed then depends on the layer alone, so a row has the same bits in any batch and in any pass.
+// (The MTL kinds keep the plan that follows the pass, and with it their bits.)
+inline int plan_images(const smh_cnn *m, int n) { return cnn_single(m->cfg.kind) ? kChunk : n; }
 
 struct Work {
     float *act[2];
@@ -765,17 +807,17 @@ Work carve(const smh_cnn *m, void *base, int N) {
     size_t part = 0;
     for (const Layer &L : m->layers)
         if (L.op == kConv) {
-            const int M = n * L.OH * L.OW;
+            const int M = n * L.OH * L.OW, Mplan = plan_images(m, n) * L.OH * L.OW;
             const int bn = L.OC <= 64 ? 64 : 128;
-            const int s = choose_split((M + BM - 1) / BM, (L.OC + bn - 1) / bn, L.Kp / BK);
+            const int s = choose_split((Mplan + BM - 1) / BM, (L.OC + bn - 1) / bn, L.Kp / BK);
             if (s > 1) part = std::max(part, (size_t)s * M * L.OC);
         }
     if (N > kChunk && N % kChunk)  // the ragged last chunk may split K differently
         for (const Layer &L : m->layers)
             if (L.op == kConv) {
-                const int M = (N % kChunk) * L.OH * L.OW;
+                const int M = (N % kChunk) * L.OH * L.OW, Mplan = plan_images(m, N % kChunk) * L.OH * L.OW;
                 const int bn = L.OC <= 64 ? 64 : 128;
-                const int s = choose_split((M + BM - 1) / BM, (L.OC + bn - 1) / bn, L.Kp / BK);
+                const int s = choose_split((Mplan + BM - 1) / BM, (L.OC + bn - 1) / bn, L.Kp / BK);
                 if (s > 1) part = std::max(part, (size_t)s * M * L.OC);
             }
     w.partial_floats = part;

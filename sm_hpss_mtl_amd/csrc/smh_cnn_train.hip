@@ -15,6 +15,9 @@
 // Papakostas adds LRN + ReLU backward (two passes), Conv2D without BatchNorm (gate + real bias gradients), a stride-2 data
 // gradient (dz zero-stuffed, then the stride-1 GEMM) and overlapping pooling; Jang adds the mel-scale layer's weight
 // gradient, a 3-channel data gradient (GEMM columns padded to 4), Dropout on feature maps and l2() on every kernel.
+// The single-task kinds (lib/baseline_architectures.py:62-108, 147-175, 358-442; compiled at :114-117) take the head of the
+// single-task TCN trainer (smh_train_single.hip) in place of heads_train_kernel; Jang's single-task graph carries l1_l2() on its mel
+// kernels only (optimiser segment kind 4).
 #include <cstdlib>
 
 #include "smh_cnn_impl.h"
@@ -23,6 +26,8 @@
 namespace {
 
 constexpr float kL2 = 0.01f;
+constexpr float kL1 = 0.01f;  // l1_l2(): the Keras defaults l1 = l2 = 0.01
+static_assert(kL1 == kL2, "l2_partial_kernel sums w^2 + |w| under one factor");
 constexpr float kBnMomentum = 0.99f;
 constexpr int kPS = smh_tcn::kPS;
 constexpr int kMaxRed = 1024;  // row chunks of a column reduction
@@ -502,7 +507,7 @@ __global__ void heads_dw_kernel(const float *__restrict__ feat, const float *__r
 // ---- optimiser ----------------------------------------------------------------------------------------------------
 struct Seg {
     unsigned off, size;
-    int kind;  // 0 plain, 1 l2-regularised kernel, 2 BN moving_mean, 3 BN moving_variance
+    int kind;  // 0 plain, 1 l2-regularised kernel, 2 BN moving_mean, 3 BN moving_variance, 4 l1_l2-regularised kernel
     unsigned aux;  // kinds 2/3: offset into the batch-statistics buffer
 };
 struct OptArgs {
@@ -513,7 +518,7 @@ __global__ void __launch_bounds__(256) opt_kernel(const Seg *__restrict__ segs, 
                                                   float *__restrict__ grad, float *__restrict__ s1, float *__restrict__ s2,
                                                   const float *__restrict__ bstat) {
     const Seg s = segs[blockIdx.x];
-    if (s.kind >= 2) {
+    if (s.kind == 2 || s.kind == 3) {
         for (unsigned i = threadIdx.x; i < s.size; i += blockDim.x)
             w[s.off + i] = kBnMomentum * w[s.off + i] + (1.0f - kBnMomentum) * (bstat[s.aux + i] * o.grad_scale);
         return;
@@ -522,6 +527,8 @@ __global__ void __launch_bounds__(256) opt_kernel(const Seg *__restrict__ segs, 
         const size_t k = (size_t)s.off + i;
         float g = grad[k] * o.grad_scale;
         if (s.kind == 1) g += 2.0f * kL2 * w[k];
+        // l1_l2(): d(l2 w^2 + l1 |w|) / dw, sign(0) = 0 as tf.abs differentiates
+        if (s.kind == 4) g += 2.0f * kL2 * w[k] + kL1 * (w[k] > 0.f ? 1.0f : (w[k] < 0.f ? -1.0f : 0.0f));
         grad[k] = g;
         if (o.optimizer == 1) {
             const float m = o.b1 * s1[k] + (1.0f - o.b1) * g;
@@ -544,6 +551,11 @@ __global__ void __launch_bounds__(256) l2_partial_kernel(const Seg *__restrict__
     double s = 0.0;
     if (sg.kind == 1)
         for (unsigned i = threadIdx.x; i < sg.size; i += blockDim.x) s += (double)w[sg.off + i] * (double)w[sg.off + i];
+    if (sg.kind == 4)  // l1_l2(): kL1 == kL2, so w^2 + |w| shares the finish kernel's one factor
+        for (unsigned i = threadIdx.x; i < sg.size; i += blockDim.x) {
+            const double v = (double)w[sg.off + i];
+            s += v * v + fabs(v);
+        }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -682,7 +694,8 @@ extern "C" void smh_cnn_trainer_destroy(smh_cnn_trainer *t) {
 
 extern "C" int smh_cnn_trainer_create(smh_cnn *m, int max_batch, smh_cnn_trainer **out) {
     SMH_REQUIRE(m && out && max_batch >= 2, "smh_cnn_trainer_create: bad argument (a training batch needs at least 2 samples)");
-    SMH_REQUIRE(m->cfg.kind == SMH_CNN_DOUKHAN || m->cfg.kind == SMH_CNN_PAPAKOSTAS || m->cfg.kind == SMH_CNN_JANG,
+    SMH_REQUIRE(m->cfg.kind == SMH_CNN_DOUKHAN || m->cfg.kind == SMH_CNN_PAPAKOSTAS || m->cfg.kind == SMH_CNN_JANG ||
+                    cnn_single(m->cfg.kind),
                 "smh_cnn_trainer_create: unknown model kind");
     // owned until the end: every early return (SMH_REQUIRE included) releases what has been allocated so far
     struct Guard {
@@ -770,7 +783,7 @@ extern "C" int smh_cnn_trainer_create(smh_cnn *m, int max_batch, smh_cnn_trainer
     std::vector<FoldEnt> folds;
     auto add_seg = [&](size_t off, size_t n, int kind, unsigned aux) {
         constexpr size_t kMax = 1 << 16;  // one workgroup per <= 64K parameters
-        if (kind >= 2) {
+        if (kind == 2 || kind == 3) {
             segs.push_back(Seg{(unsigned)off, (unsigned)n, kind, aux});
             return;
         }
@@ -814,8 +827,8 @@ extern "C" int smh_cnn_trainer_create(smh_cnn *m, int max_batch, smh_cnn_trainer
             folds.push_back(FoldEnt{(unsigned)L.es_off, (unsigned)L.OC, L.t_bias >= 0 ? (long)m->tensors[L.t_bias].off : -1, g});
         } else {
             S.a = ap, ap += S.out_elems * NB;
-            if (L.op == kMelCl)  // 2 * n_mels trainable kernels, each with kernel_regularizer=l2() (:630, :639)
-                for (int q = 0; q < m->mel_rows; ++q) add_seg(m->tensors[q].off, m->tensors[q].count, 1, 0);
+            if (L.op == kMelCl)  // the trainable mel kernels, each with kernel_regularizer=l2() (:630, :639); single-task: l1_l2()
+                for (int q = 0; q < m->mel_rows; ++q) add_seg(m->tensors[q].off, m->tensors[q].count, m->mel_reg, 0);
         }
     }
     if (e == hipSuccess) {
@@ -979,9 +992,12 @@ extern "C" int smh_cnn_train_step_f32(smh_cnn_trainer *t, const float *d_x, cons
     hipLaunchKernelGGL(heads_pre_kernel, dim3(N), dim3(256), 0, st, feat, F, hp, t->d_pre);
     rc = smh::launch_status("heads_pre_kernel");
     if (rc) return rc;
-    rc = smh_tcn::launch_heads_train(ha, t->d_pre, d_y, F, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad,
-                                     t->d_bstat + t->head_bstat, d_losses,
-                                     reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
+    if (m->n_heads == 0)  // single-task: softmax, the two-output bce or the categorical loss, accuracy, d loss / d logits
+        rc = smh_tcn::launch_single_head_train(ha, t->d_pre, d_y, t->d_dpre, t->d_grad, d_losses, st);
+    else
+        rc = smh_tcn::launch_heads_train(ha, t->d_pre, d_y, F, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad,
+                                         t->d_bstat + t->head_bstat, d_losses,
+                                         reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
     if (rc) return rc;
     hipLaunchKernelGGL(l2_partial_kernel, dim3(t->nseg), dim3(256), 0, st, (const Seg *)t->d_segs, F, t->d_l2part);
     hipLaunchKernelGGL(l2_finish_kernel, dim3(1), dim3(1024), 0, st, (const double *)t->d_l2part, t->nseg, d_losses + m->n_heads + 3);

@@ -21,7 +21,10 @@
 //       statistics in float64 over the final dB values (formed on the fly), lanes striding the row by 64 and an xor-shuffle tree: the
 //       summation order depends on T alone.  Pass 2, per 64-frame chunk: dB + the max - 80 floor -> the final fv (in place); the
 //       standardised values go to a [32][65] LDS tile and leave it transposed, as 128-byte runs of 32 rows in every patch that
-//       holds the frame (tools.extract_patches' grid on the tiled-if-short featuregram, time-major).
+//       holds the frame (tools.extract_patches' grid on the tiled-if-short featuregram, time-major).  IMAGE instantiation: the
+//       Conv2D models' layout (nP, rows, W) instead.  A lane holds one frame of a row, and consecutive frames of a row are
+//       consecutive floats of a patch row, so the same values leave straight from the registers as runs of up to 256 bytes along
+//       the patch's time axis: no LDS tile, no barrier.
 //
 // Tiles and row blocks are independent, so every T >= 1 takes this one route, alone, in an equal-length batch or in a ragged one,
 // and gets the same bits in each.
@@ -151,10 +154,15 @@ plain_project_kernel(MelTable mt, const float *__restrict__ S, int K, int rows, 
     }
 }
 
+template <bool IMAGE>
 __global__ void __launch_bounds__(64 * kFinWaves)
 plain_finish_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int log_db, int K, int rows, int nrb, int W, int shift,
                     float *__restrict__ patches, Geo g) {
-    __shared__ float tile[kRowBlock * (kTile + 1)];
+    float *tile = nullptr;  // the transposing LDS tile: time-major only
+    if constexpr (!IMAGE) {
+        __shared__ float tile_lds[kRowBlock * (kTile + 1)];
+        tile = tile_lds;
+    }
     const int clip = blockIdx.x / nrb, rb = blockIdx.x - clip * nrb;
     const ClipView c = clip_view(g, K, rows, clip);
     const int T = c.T;
@@ -209,23 +217,40 @@ plain_finish_kernel(float *__restrict__ fv, const int *__restrict__ maxkeys, int
                 const float d = final_value(v[q], lim, log_db);
                 if (log_db && lane < nt) x[q][c0 + lane] = d;  // the FINAL featuregram
                 // (x - mean) rounded to f32 as sklearn does, then * 1 / scale
-                if (want) tile[rl * (kTile + 1) + lane] = (float)((double)d - mean[q]) * inv[q];
-            }
-        }
-        if (!want) continue;
-        __syncthreads();
-        const int nP = c.nP, Tt = c.Ttiled;
-        for (int tl = tl0; tl < nt; tl += (64 * kFinWaves) / kRowBlock) {
-            for (int u = c0 + tl; u < Tt; u += T) {  // the frame's positions in the tiled featuregram (one unless T < W)
-                int p_lo, p_hi;
-                smh_feat::patch_range(u, W, shift, nP, p_lo, p_hi);
-                for (int p = p_lo; p <= p_hi; ++p) {
-                    const int j = u - p * shift;
-                    if (f < nr) patches[((c.patch_off + (size_t)p) * W + j) * rows + r0 + f] = tile[f * (kTile + 1) + tl];
+                if (want) {
+                    const float z = (float)((double)d - mean[q]) * inv[q];
+                    if constexpr (IMAGE) v[q] = z;
+                    else tile[rl * (kTile + 1) + lane] = z;
                 }
             }
         }
-        __syncthreads();
+        if (!want) continue;
+        if constexpr (IMAGE) {
+            for (int u = lane < nt ? c0 + lane : c.Ttiled; u < c.Ttiled; u += T) {  // the frame's positions in the tiled featuregram (one unless T < W)
+                int p_lo, p_hi;
+                smh_feat::patch_range(u, W, shift, c.nP, p_lo, p_hi);
+                for (int p = p_lo; p <= p_hi; ++p) {
+                    float *dst = patches + ((c.patch_off + (size_t)p) * rows + r0 + wave) * W + (u - p * shift);
+#pragma unroll
+                    for (int q = 0; q < kRowsPerWave; ++q)
+                        if (q * kFinWaves + wave < nr) dst[(size_t)q * kFinWaves * W] = v[q];
+                }
+            }
+        } else {
+            __syncthreads();
+            const int nP = c.nP, Tt = c.Ttiled;
+            for (int tl = tl0; tl < nt; tl += (64 * kFinWaves) / kRowBlock) {
+                for (int u = c0 + tl; u < Tt; u += T) {  // the frame's positions in the tiled featuregram (one unless T < W)
+                    int p_lo, p_hi;
+                    smh_feat::patch_range(u, W, shift, nP, p_lo, p_hi);
+                    for (int p = p_lo; p <= p_hi; ++p) {
+                        const int j = u - p * shift;
+                        if (f < nr) patches[((c.patch_off + (size_t)p) * W + j) * rows + r0 + f] = tile[f * (kTile + 1) + tl];
+                    }
+                }
+            }
+            __syncthreads();
+        }
     }
 }
 
@@ -241,7 +266,8 @@ int launch_pair(const smh_ctx *ctx, const float *S, float *fv, const PatchOut &p
     if (rc) return rc;
     if (!log_db && !po.patches) return SMH_OK;
     const int nrb = (rows + kRowBlock - 1) / kRowBlock;
-    hipLaunchKernelGGL(plain_finish_kernel, dim3((unsigned)n_clips * (unsigned)nrb), dim3(64 * kFinWaves), 0, st, fv, (const int *)keys,
+    const auto finish = po.layout == smh_feat::kLayoutImage && po.patches ? plain_finish_kernel<true> : plain_finish_kernel<false>;
+    hipLaunchKernelGGL(finish, dim3((unsigned)n_clips * (unsigned)nrb), dim3(64 * kFinWaves), 0, st, fv, (const int *)keys,
                        log_db, K, rows, nrb, po.W, po.shift, po.patches, g);
     return smh::launch_status("plain_finish_kernel");
 }
@@ -252,16 +278,26 @@ int check_context(const smh_ctx *ctx, const char *who) {
     return SMH_OK;
 }
 
+inline bool layout_ok(int patch_layout) { return patch_layout == smh_feat::kLayoutImage || patch_layout == smh_feat::kLayoutTimeMajor; }
+
 }  // namespace
 
 extern "C" int smh_plain_features_f32(const smh_ctx *ctx, const float *d_S, int B, int T, int W, int shift, float *d_fv,
                                       float *d_patches, int32_t *d_maxkeys, void *stream) {
+    return smh_plain_features_layout_f32(ctx, d_S, B, T, W, shift, smh_feat::kLayoutTimeMajor, d_fv, d_patches, d_maxkeys, stream);
+}
+
+// (the error texts of the shared checks keep the names of the entries they came with)
+extern "C" int smh_plain_features_layout_f32(const smh_ctx *ctx, const float *d_S, int B, int T, int W, int shift, int patch_layout,
+                                             float *d_fv, float *d_patches, int32_t *d_maxkeys, void *stream) {
+    SMH_REQUIRE(layout_ok(patch_layout), "smh_plain_features_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d",
+                patch_layout);
     SMH_REQUIRE(ctx && d_S && d_fv && d_maxkeys, "smh_plain_features_f32: null argument");
     SMH_REQUIRE(B >= 0 && B <= 65535 && T >= 1, "smh_plain_features_f32: bad shape B=%d T=%d", B, T);
     int rc = check_context(ctx, "smh_plain_features_f32");
     if (rc) return rc;
     PatchOut po;
-    rc = smh_feat::patch_out("smh_plain_features_f32", d_patches, false, T, W, shift, smh_feat::kLayoutTimeMajor, po);
+    rc = smh_feat::patch_out("smh_plain_features_f32", d_patches, false, T, W, shift, patch_layout, po);
     if (rc) return rc;
     if (B == 0) return po.nP;
     const int ntiles = (T + kTile - 1) / kTile;
@@ -285,6 +321,15 @@ extern "C" size_t smh_plain_frontend_workspace_bytes(const smh_ctx *ctx, int B, 
 
 extern "C" int smh_plain_frontend_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int W, int shift, float *d_fv,
                                       float *d_patches, void *d_work, size_t work_bytes, float *d_S, void *stream) {
+    return smh_plain_frontend_layout_f32(ctx, d_audio, B, n_samples, W, shift, smh_feat::kLayoutTimeMajor, d_fv, d_patches, d_work,
+                                         work_bytes, d_S, stream);
+}
+
+extern "C" int smh_plain_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int W, int shift,
+                                             int patch_layout, float *d_fv, float *d_patches, void *d_work, size_t work_bytes,
+                                             float *d_S, void *stream) {
+    SMH_REQUIRE(layout_ok(patch_layout), "smh_plain_frontend_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d",
+                patch_layout);
     SMH_REQUIRE(ctx && d_audio && d_fv && d_work, "smh_plain_frontend_f32: null argument");
     SMH_REQUIRE(B >= 0 && B <= 65535, "smh_plain_frontend_f32: B=%d out of range", B);
     const int T = smh_num_frames(n_samples, ctx->cfg.n_fft, ctx->cfg.hop);
@@ -302,7 +347,7 @@ extern "C" int smh_plain_frontend_f32(const smh_ctx *ctx, const float *d_audio, 
     if (B == 0) return d_patches ? smh_num_patches(smh_tiled_frames(T, W), W, shift) : 0;
     rc = smh_stft_mag_f32(ctx, d_audio, B, n_samples, S, stream);
     if (rc) return rc;
-    return smh_plain_features_f32(ctx, S, B, T, W, shift, d_fv, d_patches, keys, stream);
+    return smh_plain_features_layout_f32(ctx, S, B, T, W, shift, patch_layout, d_fv, d_patches, keys, stream);
 }
 
 // ---- ragged batches: the contract of smh_frontend_ragged_sizes / smh_frontend_ragged_f32, on the planner of smh_rag.h ----------------
@@ -371,10 +416,19 @@ extern "C" int smh_plain_frontend_ragged_sizes(const smh_ctx *ctx, const long lo
 extern "C" int smh_plain_frontend_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets,
                                              const int *h_lengths, int B, int W, int shift, float *d_fv, float *d_patches,
                                              void *d_work, size_t work_bytes, void *stream) {
+    return smh_plain_frontend_ragged_layout_f32(ctx, d_audio, h_offsets, h_lengths, B, W, shift, smh_feat::kLayoutTimeMajor, d_fv,
+                                                d_patches, d_work, work_bytes, stream);
+}
+
+extern "C" int smh_plain_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets,
+                                                    const int *h_lengths, int B, int W, int shift, int patch_layout, float *d_fv,
+                                                    float *d_patches, void *d_work, size_t work_bytes, void *stream) {
+    SMH_REQUIRE(layout_ok(patch_layout),
+                "smh_plain_frontend_ragged_layout_f32: patch_layout must be 0 (image) or 1 (time-major), got %d", patch_layout);
     SMH_REQUIRE(ctx && d_audio && d_fv && d_work && h_offsets && h_lengths && B >= 0, "smh_plain_frontend_ragged_f32: bad argument");
     const bool patches = d_patches != nullptr;
     PatchOut po;
-    int rc = smh_feat::patch_out("smh_plain_frontend_ragged_f32", d_patches, false, 0, W, shift, smh_feat::kLayoutTimeMajor, po);
+    int rc = smh_feat::patch_out("smh_plain_frontend_ragged_f32", d_patches, false, 0, W, shift, patch_layout, po);
     if (rc) return rc;
     SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0, "smh_plain_frontend_ragged_f32: the workspace must start on a 16-byte boundary");
     rc = check_context(ctx, "smh_plain_frontend_ragged_f32");
@@ -395,6 +449,7 @@ extern "C" int smh_plain_frontend_ragged_f32(const smh_ctx *ctx, const float *d_
     if (rc) return rc;
     // the clips off an 8-byte boundary, through smh_plain_frontend_f32 (the workspace is free again in stream order)
     return smh_rag::run_alone(p, B, W, shift, ctx->feat_rows, d_fv, d_patches, taken, [&](int b, int w, int sh, float *fv, float *pt) {
-        return smh_plain_frontend_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], w, sh, fv, pt, d_work, work_bytes, nullptr, stream);
+        return smh_plain_frontend_layout_f32(ctx, d_audio + h_offsets[b], 1, h_lengths[b], w, sh, patch_layout, fv, pt, d_work, work_bytes,
+                                             nullptr, stream);
     });
 }

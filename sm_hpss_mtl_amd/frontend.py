@@ -34,7 +34,7 @@ PLAIN_FEATS = {
     "LogMelSpec": (True, True),
 }
 # Frontend's `layout` argument -> the C ABI's patch_layout (include/smh.h): "image" (nP, 2*rows, W), what get_feature_patches returns
-# and the Conv2D models read; "time_major" (nP, W, 2*rows), the TCN's input
+# and the Conv2D models read; "time_major" (nP, W, 2*rows), the TCN's input.  A plain configuration has rows in place of 2*rows.
 LAYOUTS = {"image": 0, "time_major": 1}
 # FrontendConfig.stft_precision -> the C ABI's stft_precision (include/smh.h: SMH_STFT_F32 / SMH_STFT_F64)
 STFT_PRECISIONS = {"f32": _lib.SMH_STFT_F32, "f64": _lib.SMH_STFT_F64}
@@ -150,13 +150,13 @@ def _f32c(t, name):
 
 
 # What differs between the harmonic-percussive (True) and the plain front end in Frontend.run / run_ragged: featuregram rows per
-# feat_rows, taps, the four entries, the label a ragged error carries, and whether the entries take a patch layout behind `shift`.
-_Family = collections.namedtuple("_Family", "row_mult taps workspace equal ragged_sizes ragged ragged_label takes_layout")
+# feat_rows, taps, the four entries (each takes a patch layout behind `shift`) and the label a ragged error carries.
+_Family = collections.namedtuple("_Family", "row_mult taps workspace equal ragged_sizes ragged ragged_label")
 _FAMILIES = {
     True: _Family(2, ("S", "harm", "perc"), "smh_frontend_workspace_bytes", "smh_frontend_layout_f32", "smh_frontend_ragged_sizes",
-                  "smh_frontend_ragged_layout_f32", "smh_frontend_ragged_f32", True),
-    False: _Family(1, ("S",), "smh_plain_frontend_workspace_bytes", "smh_plain_frontend_f32", "smh_plain_frontend_ragged_sizes",
-                   "smh_plain_frontend_ragged_f32", "smh_plain_frontend_ragged_f32", False),
+                  "smh_frontend_ragged_layout_f32", "smh_frontend_ragged_f32"),
+    False: _Family(1, ("S",), "smh_plain_frontend_workspace_bytes", "smh_plain_frontend_layout_f32", "smh_plain_frontend_ragged_sizes",
+                   "smh_plain_frontend_ragged_layout_f32", "smh_plain_frontend_ragged_f32"),
 }
 
 
@@ -330,10 +330,16 @@ class Frontend:
         assert got == nP
         return {"fv": fv, "x0p": x0p, "patches": pt, "n_patches": nP, "maxkeys": keys}
 
-    def plain_features(self, S, W=None, shift=None, out=None):
+    def plain_features(self, S, W=None, shift=None, out=None, **options):
         """Plain configurations (hpss=False): S (B, K, T) -> dict(fv (B, rows, T)[, patches (B*nP, W, rows)]) -- Spec / LogSpec /
         MelSpec / LogMelSpec of lib/preprocessing.py:378-402 behind the STFT, then tile-if-short, StandardScaler per row and
-        time-major patches (`smh_plain_features_f32`)."""
+        time-major patches (`smh_plain_features_layout_f32`).  The one option is layout="image": patches (B*nP, rows, W), the
+        single-task Conv2D baselines' images.  (It is a keyword option, not a named parameter: tests/test_image_layout_abi.py pins
+        this method's named parameters.)"""
+        layout = options.pop("layout", "time_major")
+        if options:
+            raise TypeError("plain_features: unexpected keyword argument %r" % sorted(options)[0])
+        lay = _layout(layout)
         if self.cfg.hpss:
             raise ValueError("plain_features needs a plain configuration (FrontendConfig(hpss=False)); this one is harmonic-percussive")
         S = _f32c(S, "S")
@@ -345,30 +351,25 @@ class Frontend:
         nP, patches = 0, None
         if W is not None:
             nP = self.num_patches(T, W, shift)
-            patches = _out(out, "patches", (B * nP, W, self.rows), torch.float32, dev)
+            patches = _out(out, "patches", _patch_shape(B * nP, W, self.rows, layout), torch.float32, dev)
         keys = _maxkeys(out, B, "B", dev)
-        got = _lib.check(self.lib.smh_plain_features_f32(self._h, _ptr(S), B, T, W or 0, shift or 0, _ptr(fv),
-                                                         _ptr(patches) if nP else None, _ptr(keys), _stream()),
-                         "smh_plain_features_f32")
+        got = _lib.check(self.lib.smh_plain_features_layout_f32(self._h, _ptr(S), B, T, W or 0, shift or 0, lay, _ptr(fv),
+                                                                _ptr(patches) if nP else None, _ptr(keys), _stream()),
+                         "smh_plain_features_layout_f32")
         assert got == nP
         return {"fv": fv, "patches": patches, "n_patches": nP, "maxkeys": keys}
 
     # ---- fused fast path ----
     def _geometry(self, W, shift, layout):
-        """The (W, shift[, patch layout]) arguments of this configuration's fused entries."""
-        lay = _layout(layout)
-        if self._family.takes_layout:
-            return (W or 0, shift or 0, lay)
-        if layout != "time_major":
-            raise ValueError("the plain front end (hpss=False) writes time-major patches only; layout=%r needs a harmonic-percussive "
-                             "configuration" % (layout,))
-        return (W or 0, shift or 0)
+        """The (W, shift, patch layout) arguments of this configuration's fused entries."""
+        return (W or 0, shift or 0, _layout(layout))
 
     def run(self, audio, W=None, shift=None, taps=False, out=None, layout="time_major"):
         """audio (B, n_samples) -> dict(fv=(B, 2*rows, T)[, patches=(B*nP, W, 2*rows)][, S, harm, perc]).
         layout="image": patches=(B*nP, 2*rows, W), the Conv2D models' images, written by the same kernels (no transpose pass).
         `out` may carry preallocated 'fv' / 'patches' tensors (steady-state loops allocate nothing).
-        A plain configuration (hpss=False) gives fv=(B, rows, T) and patches=(B*nP, W, rows), time-major only; its only tap is S."""
+        A plain configuration (hpss=False) gives fv=(B, rows, T) and patches=(B*nP, W, rows) or, with layout="image",
+        (B*nP, rows, W); its only tap is S."""
         fam = self._family
         geom = self._geometry(W, shift, layout)
         F, names = fam.row_mult * self.rows, fam.taps
@@ -439,7 +440,8 @@ class Frontend:
         fv_off, p_off = (C.c_longlong * (B + 1))(), (C.c_longlong * (B + 1))()
         hT, hnP = (C.c_int * B)(), (C.c_int * B)()
         work = C.c_size_t()
-        # a plain configuration (hpss=False) takes the plain pair of entries: same contract, (rows, T_b) and (nP_b, W, rows) per clip
+        # a plain configuration (hpss=False) takes the plain pair of entries: same contract, (rows, T_b) and (nP_b, W, rows) or
+        # (nP_b, rows, W) per clip
         _lib.check(getattr(self.lib, fam.ragged_sizes)(self._h, h_off, h_len, B, W or 0, shift or 0, fv_off, p_off, hT, hnP,
                                                        C.byref(work)), fam.ragged_sizes)
         F = fam.row_mult * self.rows

@@ -177,16 +177,13 @@ def _cached_featuregram(path, fresh=None):
 def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
     """specs: list of (classname, sp_path, mu_path, target_dB).  Loads / conditions / mixes the signals (the 'next' row in
     front of the path: lib.preprocessing.load_and_preprocess_signal, mix_signals), then ONE ragged pass of the front end.
-    Returns a list of float32 device tensors in the layout PARAMS['Model'] reads: (nP_i, W, 2F) for a Lemaire_et_al variant
-    ((nP_i, W, F) for the feature names without an H / P pair); (nP_i, 2F, W, 1) for any other -- the Conv2D models' images,
-    get_feature_patches' np.expand_dims(patches, axis=3), Proposed_Work_Results.py:483-484 (a view: no copy)."""
+    Returns a list of float32 device tensors in the layout PARAMS['Model'] reads: (nP_i, W, 2F) for a Lemaire_et_al variant;
+    (nP_i, 2F, W, 1) for any other -- the Conv2D models' images, get_feature_patches' np.expand_dims(patches, axis=3),
+    Proposed_Work_Results.py:483-484 (a view: no copy).  The feature names without an H / P pair have F in place of 2F."""
     import torch
     from . import frontend as _fe
     from .lib import preprocessing as pp
     layout = "time_major" if 'Lemaire_et_al' in PARAMS['Model'] else "image"
-    if layout == "image" and featName in _fe.PLAIN_FEATS:
-        raise ValueError("the plain front end (featName %r) writes the TCN layout (N, W, F) only: the device generator serves the "
-                         "Conv2D models from the '*HarmPercSpec' feature names" % (featName,))
     clips = []
     for classname, sp, mu, db in specs:
         cache = pp.feature_cache_path(PARAMS['feature_opDir'], classname, sp, mu, db)

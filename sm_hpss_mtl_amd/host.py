@@ -190,3 +190,81 @@ class HostModel(ModelSurfaceMixin):
         self._check_device_status()  # (TrainingMixin) the forward is stream-ordered: a device-side give-up must become an exception, not a result
         host = out.cpu().numpy()  # ONE copy for all outputs (a copy per output is a host synchronisation per output)
         return [np.ascontiguousarray(o) for o in self.split_outputs(host)]
+
+
+class SingleOutputMixin:
+    """The Keras surface of a single-task model in front of its MTL class (model.SingleTaskTCN, cnn_models.CnnSingleTask): ONE
+    output 'dense' -- `predict` returns one (N, n_classes) array, `y` is one one-hot (N, n_classes) array -- compiled with
+    binary_crossentropy on the two softmax outputs for n_classes == 2 (Keras' 'accuracy' is then BINARY accuracy over the N x 2
+    outputs), else categorical_crossentropy and categorical accuracy; metrics_names = ['loss', 'accuracy']."""
+
+    @property
+    def loss_name(self):
+        return "binary_crossentropy" if self.n_classes == 2 else "categorical_crossentropy"
+
+    @property
+    def output_names(self):
+        return ["dense"]
+
+    @property
+    def metrics_names(self):
+        return ["loss", "accuracy"]
+
+    def split_outputs(self, out):
+        return [out]
+
+    def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
+        """model.predict(x=batchData) -> ONE (N, n_classes) array, as a single-output Keras model returns it."""
+        return super().predict(x, batch_size, verbose, dtype)[0]
+
+    def compile(self, loss=None, optimizer=None, metrics=None, loss_weights=None, **kwargs):
+        """`model.compile(loss=..., metrics='accuracy', optimizer=...)` (baseline_architectures.py:114-117, :292-295).  The loss is
+        fixed by n_classes (`loss_name`): anything else is an error, not a silent change."""
+        if isinstance(loss, dict):
+            loss = loss.get("dense") if set(loss) == {"dense"} else loss
+        if loss is not None and loss != self.loss_name:
+            raise ValueError("compile: the %d-class single-task model is built with %s, not %r" % (self.n_classes, self.loss_name, loss))
+        if metrics is not None:
+            mm = [metrics] if isinstance(metrics, str) else list(metrics.values() if isinstance(metrics, dict) else metrics)
+            if any(v not in ("accuracy", "acc") for v in mm):
+                raise ValueError("compile: the only metric of the single-task model is 'accuracy', got %r" % (metrics,))
+        super().compile(optimizer=optimizer, loss_weights=loss_weights, **kwargs)
+
+    def pack_targets(self, y):
+        """One one-hot (N, n_classes) array (or [array] / {'dense': array}) -> float32 CUDA tensor."""
+        if isinstance(y, dict):
+            y = y["dense"]
+        if isinstance(y, (list, tuple)) and len(y) == 1:
+            y = y[0]
+        y = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        t = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
+        if t.dim() != 2 or t.shape[1] != self.out_dim:
+            raise ValueError("targets must be one-hot (N, %d), got %s" % (self.out_dim, tuple(t.shape)))
+        return t.cuda().contiguous()
+
+    def losses_to_list(self, raw):
+        """Raw device losses [loss, weighted loss, accuracy, penalty] of one step (or their mean over steps) -> [loss, accuracy]."""
+        lv = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+        return [float(lv[1] + lv[3]), float(lv[2])]
+
+    def _losses_inference(self, x, y):
+        """[loss + penalty, accuracy] of one batch in inference mode (the host route of `evaluate`), by the rule of `loss_name`, in
+        float64 from the device's softmax: two classes -- Keras binary_crossentropy on both outputs (clip to [1e-7, 1 - 1e-7],
+        + 1e-7 inside the logs) and binary accuracy over the N x 2 outputs; else categorical cross-entropy (the probabilities
+        renormalised, then clipped, as Keras does) and categorical accuracy."""
+        p = self.predict(x).astype(np.float64)
+        if isinstance(y, dict):
+            y = y["dense"]
+        if isinstance(y, (list, tuple)):
+            y = y[0]
+        t = np.asarray(y.cpu() if isinstance(y, torch.Tensor) else y, np.float64).reshape(p.shape)
+        eps = 1e-7
+        if self.n_classes == 2:
+            pc = np.clip(p, eps, 1 - eps)
+            loss = float(np.mean(-(t * np.log(pc + eps) + (1 - t) * np.log(1 - pc + eps))))
+            acc = float(np.mean((p > 0.5) == (t > 0.5)))
+        else:
+            pc = np.clip(p / p.sum(1, keepdims=True), eps, 1 - eps)
+            loss = float(np.mean(-np.sum(t * np.log(pc), axis=1)))
+            acc = float(np.mean(p.argmax(1) == t.argmax(1)))
+        return [loss + self._eval_penalty(), acc]

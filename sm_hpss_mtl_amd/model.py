@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .host import HEADS_CASCADED, HEADS_FUSION, HEADS_MTL, HEADS_SINGLE, HostModel, f32_cuda, head_spec, ptr, to_f32_cuda, workspace
+from .host import HEADS_CASCADED, HEADS_FUSION, HEADS_MTL, HEADS_SINGLE, HostModel, SingleOutputMixin, f32_cuda, head_spec, ptr, to_f32_cuda, workspace
 from .training import TRAIN_ALL, TcnTrainingMixin
 
 CAT = 18  # cascaded heads: width of concat[Dropout(16) of S or M, R's two outputs]
@@ -403,7 +403,7 @@ class FusionMTL(B3MTL):
                            initial_epoch=initial_epoch, **kwargs)
 
 
-class SingleTaskTCN(B3MTL):
+class SingleTaskTCN(SingleOutputMixin, B3MTL):
     """`model` object of get_Lemaire_model (lib/baseline_architectures.py:196-300; 5-class twin: 5_class_classification.py:54-145),
     baseline 3 of Baseline_Results.py: B3_MTL's trunk, then Flatten -> Dense(n_classes) -> softmax -- no Dense(16), no BatchNorm, no
     head dropout, no l2 term.  One input (N, W, n_feat) time-major (the reference feeds LogMelSpec patches), ONE output 'dense':
@@ -425,25 +425,6 @@ class SingleTaskTCN(B3MTL):
                          seed=seed, nb_filters=nb_filters, kernel_size=kernel_size, nb_stacks=nb_stacks, n_dilations=n_dilations,
                          tcn_block=tcn_block)
 
-    @property
-    def loss_name(self):
-        return "binary_crossentropy" if self.n_classes == 2 else "categorical_crossentropy"
-
-    @property
-    def output_names(self):
-        return ["dense"]
-
-    @property
-    def metrics_names(self):
-        return ["loss", "accuracy"]
-
-    def split_outputs(self, out):
-        return [out]
-
-    def predict(self, x, batch_size=None, verbose=0, dtype="f32"):
-        """model.predict(x=batchData) -> ONE (N, n_classes) array, as a single-output Keras model returns it."""
-        return super().predict(x, batch_size, verbose, dtype)[0]
-
     def forward_device(self, x, out=None, trunk=None, dtype="f32"):
         """x: float32 CUDA tensor (N, W, n_feat) -> (N, n_classes) softmax on the device."""
         if dtype != "f32":
@@ -455,36 +436,6 @@ class SingleTaskTCN(B3MTL):
                          "use forward_device or forward_dense")
 
     # ---- training surface ----
-    def compile(self, loss=None, optimizer=None, metrics=None, loss_weights=None, **kwargs):
-        """`model.compile(loss=..., metrics='accuracy', optimizer=...)` (baseline_architectures.py:292-295).  The loss is fixed by
-        n_classes (`loss_name`): anything else is an error, not a silent change."""
-        if isinstance(loss, dict):
-            loss = loss.get("dense") if set(loss) == {"dense"} else loss
-        if loss is not None and loss != self.loss_name:
-            raise ValueError("compile: the %d-class single-task model is built with %s, not %r" % (self.n_classes, self.loss_name, loss))
-        if metrics is not None:
-            mm = [metrics] if isinstance(metrics, str) else list(metrics.values() if isinstance(metrics, dict) else metrics)
-            if any(v not in ("accuracy", "acc") for v in mm):
-                raise ValueError("compile: the only metric of the single-task model is 'accuracy', got %r" % (metrics,))
-        super().compile(optimizer=optimizer, loss_weights=loss_weights, **kwargs)
-
-    def pack_targets(self, y):
-        """One one-hot (N, n_classes) array (or [array] / {'dense': array}) -> float32 CUDA tensor."""
-        if isinstance(y, dict):
-            y = y["dense"]
-        if isinstance(y, (list, tuple)) and len(y) == 1:
-            y = y[0]
-        y = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
-        t = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
-        if t.dim() != 2 or t.shape[1] != self.out_dim:
-            raise ValueError("targets must be one-hot (N, %d), got %s" % (self.out_dim, tuple(t.shape)))
-        return t.cuda().contiguous()
-
-    def losses_to_list(self, raw):
-        """Raw device losses [loss, weighted loss, accuracy, 0] of one step (or their mean over steps) -> [loss, accuracy]."""
-        lv = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
-        return [float(lv[1] + lv[3]), float(lv[2])]
-
     def train_on_batch(self, x, y, drop_tcn="auto", drop_heads=None, apply=True, sync=True, _only=None, _mask=TRAIN_ALL):
         """One optimiser step -> [loss, accuracy].  There is no head dropout: drop_heads is accepted for the shared signature only."""
         if _only is not None:

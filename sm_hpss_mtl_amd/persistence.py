@@ -320,6 +320,11 @@ def model_from_json(text, seed=None):
         from .cnn_models import CnnMTL
         return CnnMTL(name[:-4], tuple(cfg["input_shape"]), n_classes=cfg["n_classes"], seed=seed, n_mels=cfg.get("n_mels", 120),
                       n_fft=cfg.get("n_fft", 512), fs=cfg.get("fs", 16000), fc_width=cfg.get("fc_width", 0))
+    if name in ("Doukhan_SingleTask", "Papakostas_SingleTask", "Jang_SingleTask"):
+        from .cnn_models import CnnSingleTask
+        return CnnSingleTask(name[:-len("_SingleTask")], tuple(cfg["input_shape"]), n_classes=cfg["n_classes"], seed=seed,
+                             n_mels=cfg.get("n_mels", 64), n_fft=cfg.get("n_fft", 512), fs=cfg.get("fs", 16000),
+                             fc_width=cfg.get("fc_width", 0))
     raise ValueError("model_from_json: unknown class_name %r" % (name,))
 
 

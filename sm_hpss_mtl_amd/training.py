@@ -284,14 +284,16 @@ class TrainingMixin:
                 per.append(float(np.mean(-(t * np.log(oc + eps) + (1 - t) * np.log(1 - oc + eps)))))
         lw = [float((self.loss_weights or {}).get(n, 1.0)) for n in self.output_names]
         acc = float(np.mean(outs[-1].argmax(1) == np.asarray(yl[-1]).argmax(1)))
-        cache = getattr(self, "_eval_l2", None)  # a dict while `evaluate` runs: the penalty is computed by its first batch
+        return [sum(a * b for a, b in zip(lw, per)) + self._eval_penalty()] + per + [acc]
+
+    def _eval_penalty(self):
+        """`_l2_penalty()`, computed once per `evaluate` call (`_eval_l2` is a dict while it runs: its first batch fills it)."""
+        cache = getattr(self, "_eval_l2", None)
         if cache is None:
-            l2 = self._l2_penalty()
-        else:
-            if "v" not in cache:
-                cache["v"] = self._l2_penalty()
-            l2 = cache["v"]
-        return [sum(a * b for a, b in zip(lw, per)) + l2] + per + [acc]
+            return self._l2_penalty()
+        if "v" not in cache:
+            cache["v"] = self._l2_penalty()
+        return cache["v"]
 
     def evaluate(self, x=None, y=None, steps=None, verbose=0, batch_size=None, **kwargs):
         """model.evaluate(generator, steps) or evaluate(x, y) -> list matching `metrics_names`."""
