@@ -106,8 +106,11 @@ int smh_median_freq_f32(const smh_ctx *ctx, const float *d_S, int B, int K, int 
 /* Layout-aware variants used by the fused pipeline (no reference counterpart: the reference never
  * materialises harm on a device).  harm_layout 0 = (B,K,T) as above; 1 = (B,T,K) time-major, which lets
  * the harmonic lanes (one per bin) store coalesced -- about 30 us per 1024 clips faster on MI355X.
- * smh_hpss_median_ex_f32 returns the layout it actually wrote (it falls back to 0 for window pairs or
- * tiny axes outside the fused kernel table); pass that value on to smh_features_ex_f32.              */
+ * smh_hpss_median_ex_f32 returns the layout it actually wrote; pass that value on to smh_features_ex_f32.
+ * It falls back to 0 for window pairs or tiny axes outside the fused kernel table, and it writes 1 for a
+ * requested 2 wherever no block-split kernel runs: a window above 21 (pairs such as (31,31) or (11,51),
+ * single windows from 23), or a spectrogram so tall (K of several hundred bins and more) that the bins
+ * alone exceed the block-split kernel's waves.  B == 0 returns the requested layout.                  */
 int smh_hpss_median_ex_f32(const smh_ctx *ctx, const float *d_S, int B, int K, int T, int l_harm, int l_perc,
                            float *d_harm, float *d_perc, int harm_layout, void *stream);
 /* the harmonic median alone (= smh_median_time_f32) in any of those layouts; returns the layout written */

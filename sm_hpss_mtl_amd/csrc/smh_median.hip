@@ -159,13 +159,24 @@ int launch_small(const float *S, int B, int K, int T, int w, int along_t, float 
     return smh::launch_status("median_small_kernel");
 }
 
+// The kernel a launch takes and what it writes: the one decision of launch(), which the test-only smh_internal_median_route reports.
+enum Family { kFamCopy = 0, kFamSmall = 1, kFamSplit = 2, kFamPersist = 3, kFamDeleteInsert = 4, kFamTwoSingles = 5 };
+struct Route {
+    int family, layout;  // layout: the harm layout that is written
+    Plan plan;           // tile and roles of the chosen kernel (copy, small, two singles: zero)
+    KernelFn fn;
+    const SplitEntry *se;
+    const PersistEntry *pe;
+    int n_cu;
+};
+
 // harm_tmajor: 0 = (B,K,T), 1 = (B,T,K), 2 = (B, ceil(T/16), K, 16) (block-split kernels; any other kernel writes layout 1
-// instead).  *written (optional) receives the layout that was produced.
-int launch(const float *S, int B, int K, int T, int lh, int lp, float *harm, float *perc, hipStream_t st,
-           int harm_tmajor = 0, int *written = nullptr) {
-    if (written) *written = harm_tmajor;
-    KernelFn fn = (lh && lp) ? find_pair_kernel(lh, lp) : find_single_kernel(lh, lp);
-    if (!fn) return smh::set_error(SMH_E_INVALID, "no median kernel for (l_harm,l_perc)=(%d,%d)", lh, lp);
+// instead).  r->layout receives the layout that will be produced.
+int launch_route(int B, int K, int T, int lh, int lp, int harm_tmajor, Route *r) {
+    *r = Route{};
+    r->layout = harm_tmajor;
+    r->fn = (lh && lp) ? find_pair_kernel(lh, lp) : find_single_kernel(lh, lp);
+    if (!r->fn) return smh::set_error(SMH_E_INVALID, "no median kernel for (l_harm,l_perc)=(%d,%d)", lh, lp);
     Plan p;
     int rc = make_plan(K, T, lh, lp, &p);
     if (rc) return rc;
@@ -192,34 +203,58 @@ int launch(const float *S, int B, int K, int T, int lh, int lp, float *harm, flo
         Plan q = p;
         if (p.ntiles == 1 && conflict_free && 2 * tile_bytes <= smh::kLdsBytesPerCU && B >= 2 * n_cu &&
             make_split_roles(K, T, lh, lp, pe->threads / 64, &q)) {
-            const int lds = 2 * tile_bytes;
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)pe->fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            hipLaunchKernelGGL(pe->fn, dim3(n_cu), dim3((q.nwh + q.nwp) * 64), lds, st, S, harm, perc, B, K, T, q.nsh,
-                               q.nsp, q.nwh, harm_tmajor);
-            return smh::launch_status("hpss_median_persist_kernel");
+            r->family = kFamPersist, r->plan = q, r->pe = pe, r->n_cu = n_cu;
+            return SMH_OK;
         }
     }
     // (layout 2 is also written tile by tile: the blocked walker addresses harm[t / 16][k][t % 16] by absolute frame)
     if (const SplitEntry *se = no_split ? nullptr : find_split_kernel(lh, lp)) {
         Plan q = p;
         if (make_split_roles(K, p.TT, lh, lp, se->threads / 64, &q)) {
-            SMH_CHECK_HIP(hipFuncSetAttribute((const void *)se->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds));
-            dim3 grid(q.ntiles, B), block((q.nwh + q.nwp) * 64);
-            const bool probe_noload = smh::probe_env("SMH_MEDIAN_PROBE_NOLOAD") != nullptr;  // timing experiment, outputs invalid
-            hipLaunchKernelGGL(se->fn, grid, block, q.lds, st, S, harm, perc, K, T, q.TT, q.stride, q.nsh, q.nsp, q.nwh,
-                               harm_tmajor, probe_noload ? 1.f : -__builtin_inff(), __builtin_inff(), nullptr, nullptr, 0);
-            return smh::launch_status("hpss_median_split_kernel");
+            r->family = kFamSplit, r->plan = q, r->se = se;
+            return SMH_OK;
         }
     }
-    if (harm_tmajor == 2) {  // the delete/insert kernel has no blocked store
-        harm_tmajor = 1;
-        if (written) *written = 1;
+    if (harm_tmajor == 2) r->layout = 1;  // the delete/insert kernel has no blocked store
+    r->family = kFamDeleteInsert, r->plan = p;
+    return SMH_OK;
+}
+
+int launch_routed(const Route &r, const float *S, int B, int K, int T, float *harm, float *perc, hipStream_t st) {
+    if (r.family == kFamPersist) {
+        const Plan &q = r.plan;
+        const int lds = 2 * persist_tile_bytes(K, T);
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)r.pe->fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL(r.pe->fn, dim3(r.n_cu), dim3((q.nwh + q.nwp) * 64), lds, st, S, harm, perc, B, K, T, q.nsh,
+                           q.nsp, q.nwh, r.layout);
+        return smh::launch_status("hpss_median_persist_kernel");
     }
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    if (r.family == kFamSplit) {
+        const Plan &q = r.plan;
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)r.se->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds));
+        dim3 grid(q.ntiles, B), block((q.nwh + q.nwp) * 64);
+        const bool probe_noload = smh::probe_env("SMH_MEDIAN_PROBE_NOLOAD") != nullptr;  // timing experiment, outputs invalid
+        hipLaunchKernelGGL(r.se->fn, grid, block, q.lds, st, S, harm, perc, K, T, q.TT, q.stride, q.nsh, q.nsp, q.nwh,
+                           r.layout, probe_noload ? 1.f : -__builtin_inff(), __builtin_inff(), nullptr, nullptr, 0);
+        return smh::launch_status("hpss_median_split_kernel");
+    }
+    const Plan &p = r.plan;
+    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
     dim3 grid(p.ntiles, B), block((p.nwh + p.nwp) * 64);
-    hipLaunchKernelGGL(fn, grid, block, p.lds, st, S, harm, perc, K, T, p.TT, p.stride, p.nsh, p.nsp, p.nwh,
-                       harm_tmajor, -__builtin_inff(), __builtin_inff());
+    hipLaunchKernelGGL(r.fn, grid, block, p.lds, st, S, harm, perc, K, T, p.TT, p.stride, p.nsh, p.nsp, p.nwh,
+                       r.layout, -__builtin_inff(), __builtin_inff());
     return smh::launch_status("hpss_median_kernel");
+}
+
+// *written (optional) receives the layout that was produced.
+int launch(const float *S, int B, int K, int T, int lh, int lp, float *harm, float *perc, hipStream_t st,
+           int harm_tmajor = 0, int *written = nullptr) {
+    if (written) *written = harm_tmajor;
+    Route r;
+    int rc = launch_route(B, K, T, lh, lp, harm_tmajor, &r);
+    if (rc) return rc;
+    if (written) *written = r.layout;
+    return launch_routed(r, S, B, K, T, harm, perc, st);
 }
 
 int check_args(const void *S, int B, int K, int T, int w, const char *name) {
@@ -233,6 +268,34 @@ int check_args(const void *S, int B, int K, int T, int w, const char *name) {
 
 // the register-window kernel folds once per side: it needs window/2 < axis length
 bool fast_ok(int n, int w) { return w >= 3 && w / 2 + 4 < n; }
+
+// both filters in one launch: the pair kernel's folds fit both axes
+bool pair_fused(int K, int T, int lh, int lp) { return fast_ok(T, lh) && fast_ok(K, lp) && find_pair_kernel(lh, lp); }
+
+// smh_hpss_median_f32 and launch_hpss: the fused launch, else one launch per filter (window pairs outside the fused table, or
+// tiny axes), which writes the reference layout
+int hpss_route(int B, int K, int T, int lh, int lp, int want_tmajor, Route *r) {
+    if (pair_fused(K, T, lh, lp)) return launch_route(B, K, T, lh, lp, want_tmajor, r);
+    *r = Route{};
+    r->family = kFamTwoSingles;
+    return SMH_OK;
+}
+
+// smh_median_time_f32: copy for a window of one, the rank-counting kernel for axes the register window cannot fold
+int time_route(int B, int K, int T, int lh, Route *r) {
+    if (lh == 1 || !fast_ok(T, lh)) {
+        *r = Route{};
+        r->family = lh == 1 ? kFamCopy : kFamSmall;
+        return SMH_OK;
+    }
+    return launch_route(B, K, T, lh, 0, 0, r);
+}
+
+// smh_median_time_ex_f32: whatever smh_median_time_f32 cannot launch, and a requested layout 0, is that entry's
+int time_ex_route(int B, int K, int T, int lh, int harm_layout, Route *r) {
+    if (lh == 1 || !fast_ok(T, lh) || harm_layout == 0) return time_route(B, K, T, lh, r);
+    return launch_route(B, K, T, lh, 0, harm_layout, r);
+}
 
 }  // namespace
 
@@ -274,13 +337,12 @@ int launch_rag(const float *d_S, float *d_harm, float *d_perc, int K, int lh, in
 // Returns 1 if the time-major layout was produced, 0 if the reference layout was used, <0 on error.
 int launch_hpss(const float *S, int B, int K, int T, int lh, int lp, float *harm, float *perc, int want_tmajor,
                 hipStream_t st) {
-    if (fast_ok(T, lh) && fast_ok(K, lp) && find_pair_kernel(lh, lp)) {
-        int written = want_tmajor;
-        int rc = launch(S, B, K, T, lh, lp, harm, perc, st, want_tmajor, &written);
-        return rc ? rc : written;
-    }
-    int rc = smh_hpss_median_f32(nullptr, S, B, K, T, lh, lp, harm, perc, (void *)st);
-    return rc ? rc : 0;
+    Route r;
+    int rc = hpss_route(B, K, T, lh, lp, want_tmajor, &r);
+    if (rc) return rc;
+    rc = r.family == kFamTwoSingles ? smh_hpss_median_f32(nullptr, S, B, K, T, lh, lp, harm, perc, (void *)st)
+                                    : launch_routed(r, S, B, K, T, harm, perc, st);
+    return rc ? rc : r.layout;
 }
 
 // whether launch_hpss(want_tmajor = 2) writes the 16-frame blocked harm image: the pair kernel's folds fit both axes and the
@@ -288,7 +350,7 @@ int launch_hpss(const float *S, int B, int K, int T, int lh, int lp, float *harm
 // a call whose medians came back in another layout than this promised)
 bool blocked_harm_ok(int K, int T, int lh, int lp) {
     static const bool no_split = getenv("SMH_MEDIAN_NOSPLIT") != nullptr;
-    if (no_split || !(fast_ok(T, lh) && fast_ok(K, lp) && find_pair_kernel(lh, lp))) return false;
+    if (no_split || !pair_fused(K, T, lh, lp)) return false;
     const SplitEntry *se = find_split_kernel(lh, lp);
     Plan p, q;
     return se && make_plan(K, T, lh, lp, &p) == SMH_OK && make_split_roles(K, p.TT, lh, lp, se->threads / 64, &q);
@@ -302,12 +364,15 @@ extern "C" int smh_median_time_f32(const smh_ctx *, const float *d_S, int B, int
     SMH_REQUIRE(d_harm || B == 0, "smh_median_time_f32: null output");
     if (B == 0) return SMH_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (l_harm == 1) {
+    Route r;
+    rc = time_route(B, K, T, l_harm, &r);
+    if (rc) return rc;
+    if (r.family == kFamCopy) {
         SMH_CHECK_HIP(hipMemcpyAsync(d_harm, d_S, (size_t)B * K * T * sizeof(float), hipMemcpyDeviceToDevice, st));
         return SMH_OK;
     }
-    if (!fast_ok(T, l_harm)) return launch_small(d_S, B, K, T, l_harm, 1, d_harm, st);
-    return launch(d_S, B, K, T, l_harm, 0, d_harm, nullptr, st);
+    if (r.family == kFamSmall) return launch_small(d_S, B, K, T, l_harm, 1, d_harm, st);
+    return launch_routed(r, d_S, B, K, T, d_harm, nullptr, st);
 }
 
 // the harmonic median alone in any of the three layouts of smh_hpss_median_ex_f32 (returns the layout written)
@@ -318,13 +383,15 @@ extern "C" int smh_median_time_ex_f32(const smh_ctx *, const float *d_S, int B, 
     SMH_REQUIRE(harm_layout >= 0 && harm_layout <= 2, "smh_median_time_ex_f32: harm_layout must be 0, 1 or 2");
     SMH_REQUIRE(d_harm || B == 0, "smh_median_time_ex_f32: null output");
     if (B == 0) return harm_layout;
-    if (l_harm == 1 || !fast_ok(T, l_harm) || harm_layout == 0) {
+    Route r;
+    rc = time_ex_route(B, K, T, l_harm, harm_layout, &r);
+    if (rc) return rc;
+    if (r.family == kFamCopy || r.family == kFamSmall) {
         rc = smh_median_time_f32(nullptr, d_S, B, K, T, l_harm, d_harm, stream);
         return rc ? rc : 0;
     }
-    int written = harm_layout;
-    rc = launch(d_S, B, K, T, l_harm, 0, d_harm, nullptr, (hipStream_t)stream, harm_layout, &written);
-    return rc ? rc : written;
+    rc = launch_routed(r, d_S, B, K, T, d_harm, nullptr, (hipStream_t)stream);
+    return rc ? rc : r.layout;
 }
 
 extern "C" int smh_median_freq_f32(const smh_ctx *, const float *d_S, int B, int K, int T, int l_perc, float *d_perc,
@@ -350,8 +417,10 @@ extern "C" int smh_hpss_median_f32(const smh_ctx *, const float *d_S, int B, int
     if (rc) return rc;
     SMH_REQUIRE((d_harm && d_perc) || B == 0, "smh_hpss_median_f32: null output");
     if (B == 0) return SMH_OK;
-    if (fast_ok(T, l_harm) && fast_ok(K, l_perc) && find_pair_kernel(l_harm, l_perc))
-        return launch(d_S, B, K, T, l_harm, l_perc, d_harm, d_perc, (hipStream_t)stream);
+    Route r;
+    rc = hpss_route(B, K, T, l_harm, l_perc, 0, &r);
+    if (rc) return rc;
+    if (r.family != kFamTwoSingles) return launch_routed(r, d_S, B, K, T, d_harm, d_perc, (hipStream_t)stream);
     // window pairs outside the fused table, or tiny axes: one launch per filter
     rc = smh_median_time_f32(nullptr, d_S, B, K, T, l_harm, d_harm, stream);
     if (rc) return rc;
@@ -368,4 +437,34 @@ extern "C" int smh_hpss_median_ex_f32(const smh_ctx *, const float *d_S, int B, 
     SMH_REQUIRE((d_harm && d_perc) || B == 0, "smh_hpss_median_ex_f32: null output");
     if (B == 0) return harm_layout;
     return smh_median::launch_hpss(d_S, B, K, T, l_harm, l_perc, d_harm, d_perc, harm_layout, (hipStream_t)stream);
+}
+
+// Test-only (not in include/smh.h): the route one call of a median entry point takes, from the functions the entry points themselves
+// decide with; launches nothing.  entry: 0 smh_hpss_median_ex_f32, 1 smh_median_time_ex_f32, 2 smh_hpss_median_f32,
+// 3 smh_median_time_f32 (l_perc / harm_layout are ignored where the entry has no such argument).  out[0..5] = family (0 copy,
+// 1 rank counting, 2 block-split, 3 persistent, 4 delete/insert, 5 one launch per filter; -1 for B == 0: no launch), harm layout
+// written, ntiles, TT, nsh, nsp (zero for families 0, 1 and 5).  Returns SMH_OK, or the error the entry point would return.
+extern "C" int smh_internal_median_route(int entry, int K, int T, int l_harm, int l_perc, int B, int harm_layout, int *out) {
+    static const char *const names[] = {"smh_hpss_median_ex_f32", "smh_median_time_ex_f32", "smh_hpss_median_f32", "smh_median_time_f32"};
+    SMH_REQUIRE(entry >= 0 && entry <= 3 && out, "smh_internal_median_route: bad entry or null output");
+    const bool pair = entry == 0 || entry == 2;
+    if (entry >= 2) harm_layout = 0;
+    int rc = check_args(out, B, K, T, l_harm, names[entry]);
+    if (rc) return rc;
+    if (pair && (rc = check_args(out, B, K, T, l_perc, names[entry]))) return rc;
+    SMH_REQUIRE(harm_layout >= 0 && harm_layout <= 2, "%s: harm_layout must be 0, 1 or 2", names[entry]);
+    Route r{};
+    r.family = -1, r.layout = harm_layout;
+    if (B > 0) {
+        rc = pair ? hpss_route(B, K, T, l_harm, l_perc, harm_layout, &r)
+                  : entry == 1 ? time_ex_route(B, K, T, l_harm, harm_layout, &r) : time_route(B, K, T, l_harm, &r);
+        if (rc) return rc;
+        if (r.family == kFamTwoSingles) {  // either single launch may still refuse the shape
+            Route one;
+            if ((rc = time_route(B, K, T, l_harm, &one))) return rc;
+            if (l_perc != 1 && fast_ok(K, l_perc) && (rc = launch_route(B, K, T, 0, l_perc, 0, &one))) return rc;
+        }
+    }
+    out[0] = r.family, out[1] = r.layout, out[2] = r.plan.ntiles, out[3] = r.plan.TT, out[4] = r.plan.nsh, out[5] = r.plan.nsp;
+    return SMH_OK;
 }
