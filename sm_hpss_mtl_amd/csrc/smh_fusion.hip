@@ -394,23 +394,17 @@ extern "C" size_t smh_fusion_dense_workspace_bytes(const smh_model *m, int Tc, i
 
 extern "C" int smh_fusion_forward_dense_f32(smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes,
                                             float *d_out, void *stream) {
-    SMH_REQUIRE(m && d_fv && d_work && d_out, "smh_fusion_forward_dense_f32: null argument");
+    int rc = dense_entry_ok("smh_fusion_forward_dense_f32", m, d_fv, Tc, shift, d_work, work_bytes, smh_fusion_dense_workspace_bytes(m, Tc, shift),
+                            d_out, 4, "smh_fusion_forward_f32");
+    if (rc) return rc;
     SMH_REQUIRE(m->heads == SMH_HEADS_FUSION, "smh_fusion_forward_dense_f32: the model is not an intermediate-fusion model; a B3_MTL or "
                 "cascaded model takes smh_model_forward_dense_f32");
     const int W = m->cfg.patch_size, F = m->cfg.n_feat;
-    SMH_REQUIRE(shift >= 1 && Tc >= W, "smh_fusion_forward_dense_f32: needs shift >= 1 and at least patch_size=%d frames (Tc=%d, shift=%d); "
-                "shorter chunks are tiled by get_feature_patches and take smh_fusion_forward_f32", W, Tc, shift);
-    SMH_REQUIRE(F % 4 == 0, "smh_fusion_forward_dense_f32: the per-branch n_feat=%d must be a multiple of 4 (whole k steps per half)", F);
-    SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_fv) % 16) == 0 &&
-                    (reinterpret_cast<uintptr_t>(d_out) % 4) == 0,
-                "smh_fusion_forward_dense_f32: d_fv and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries");
-    SMH_REQUIRE(work_bytes >= smh_fusion_dense_workspace_bytes(m, Tc, shift), "smh_fusion_forward_dense_f32: workspace of %zu bytes, need %zu",
-                work_bytes, smh_fusion_dense_workspace_bytes(m, Tc, shift));
     const int nP = smh_num_patches(Tc, W, shift);
     if (nP <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     float *x0 = static_cast<float *>(d_work);
-    int rc = launch_l0_frames(d_fv, m->d_w0cat, x0, F, Tc, st);
+    rc = launch_l0_frames(d_fv, m->d_w0cat, x0, F, Tc, st);
     if (rc) return rc;
     const size_t half = (size_t)m->D / 2;
     const int chunk = std::min(nP, kFusionDenseChunk);

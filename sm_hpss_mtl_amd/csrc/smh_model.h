@@ -22,6 +22,9 @@ constexpr int kCatTail = 4 * kHidden + 4 * kCat + kCat + 1;
 // Packed per-block weights: 64 A-operand slots per lane (48 dilated-conv + 16 1x1), four slots per lane contiguous
 // ([slot / 4][lane][slot % 4], see load_block_lds), then [b1 32][b2 32]
 constexpr int kBlockFloats = 24 * 2 * 64 + 8 * 2 * 64 + 32 + 32;
+// LDS budget of every network kernel (the f32, 2.8-block and split-bf16 forwards, the MFMA and the scalar backward): 4 KB under
+// smh::kLdsBytesPerCU.  Inherited -- neither the code nor its history says what the 4 KB are left for.
+constexpr size_t kNetLdsLimit = smh::kLdsBytesPerCU - 4 * 1024;
 
 struct TcnArgs {
     int N, T, F, FQ, G, GRP, n_blocks, n_dil, vec_ok;
@@ -160,7 +163,26 @@ inline size_t trunk_floats_v2(const smh_model_cfg &c) {
     return v2_block0_floats(c.n_feat) + (size_t)(c.nb_stacks * c.n_dilations - 1) * kV2BlockFloats;
 }
 Offsets offsets(const smh_model *m);
-void fill_args(const smh_model *m, int N, TcnArgs *a, size_t *lds);
+// How a forward of N patches is launched (smh_tcn.hip; DESIGN 4.4 "Forward plan: one function").  ForwardSwitches: the SMH_TCN_*
+// switches as read_forward_switches reads them once per launch / query (G 0, skew -1: not set; skew16: lab builds only).  ForwardPlan:
+// patches and LDS rows per workgroup, column tiles, waves, the kernel's MODE (kOneSet .. kSkew16), weight slots, split last tile, LDS
+// bytes.  plan_forward is host arithmetic alone -- no HIP call, no getenv -- and returns SMH_OK or the refusal of a patch too long
+// for the LDS; the launcher, both test queries, launch_forward_v2 and the bf16 forward's plan take their geometry from it.
+struct ForwardSwitches {
+    int G = 0, skew = -1, waves = 0;
+    bool has_waves = false, prefetch = true, split = true, skew16 = false;
+};
+ForwardSwitches read_forward_switches();
+struct ForwardPlan {
+    int G, GRP, units, nwaves, mode, wlds, split_last;
+    size_t lds;
+};
+int plan_forward(const smh_model *m, int N, bool train, bool trace, const ForwardSwitches &sw, ForwardPlan *p);
+void fill_args(const smh_model *m, int N, const ForwardPlan &p, TcnArgs *a);
+// the argument checks shared by the dense file-level entries (`name`): pointers and their alignment, n_feat a multiple of
+// feat_multiple, shift and chunk length (short_clip_entry: where shorter chunks go), the workspace size
+int dense_entry_ok(const char *name, const smh_model *m, const float *d_fv, int Tc, int shift, const void *d_work, size_t work_bytes,
+                   size_t need_bytes, const float *d_out, int feat_multiple, const char *short_clip_entry);
 int repack(smh_model *m, hipStream_t st);  // d_flat -> packed operand buffers
 int launch_forward_bf16_train(smh_model *m, const float *d_x, int N, const TrainIO *tio, hipStream_t st);  // smh_tcn_bf16.hip
 bool backward_bf16_supported(int T, int n_dil);  // smh_train_bf16.hip: the patch geometry fits the split-bf16 backward's LDS plan

@@ -1181,10 +1181,11 @@ int repack(smh_model *m, hipStream_t st) {
     return smh::launch_status("repack_kernel");
 }
 
-void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
+// The kernel arguments of a forward of N patches under plan p: the model's constants, the plan's G / GRP / wlds / split_last, and
+// everything a caller may set afterwards (input mode, pair, probes) at its default
+void fill_args(const smh_model *m, int N, const ForwardPlan &p, TcnArgs *pa) {
     TcnArgs &a = *pa;
-    const int T = m->cfg.patch_size;
-    a.N = N, a.T = T, a.F = m->cfg.n_feat, a.FQ = m->FQ, a.n_blocks = m->n_blocks, a.n_dil = m->cfg.n_dilations;
+    a.N = N, a.T = m->cfg.patch_size, a.F = m->cfg.n_feat, a.FQ = m->FQ, a.n_blocks = m->n_blocks, a.n_dil = m->cfg.n_dilations;
     a.vec_ok = (a.F % 4 == 0) && (a.FQ % 4 == 0) && (a.FQ * 4 == a.F);
     a.skip_heads = 0;
     a.trunk_only = 0;
@@ -1199,6 +1200,27 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     for (int i = 0; i < kMaxHeads; ++i) a.head_odim[i] = m->head_odim[i], a.head_sigmoid[i] = m->head_sigmoid[i];
     a.cascade = m->heads == SMH_HEADS_CASCADED;
     a.single = m->heads == SMH_HEADS_SINGLE;
+    a.G = p.G, a.GRP = p.GRP, a.wlds = p.wlds, a.split_last = p.split_last;
+}
+
+// The implementation switches of the forward (A/B runs, tuning tools and tests), one getenv each.  Read at the top of every launch
+// and query rather than once per process: tests flip SMH_TCN_SKEW / SMH_TCN_SPLIT between calls on one model.
+ForwardSwitches read_forward_switches() {
+    const auto num = [](const char *ev, int unset) { return ev ? atoi(ev) : unset; };
+    ForwardSwitches s;
+    s.G = num(getenv("SMH_TCN_G"), 0);  // tuning only (tools/tune_model.py)
+    s.skew = num(getenv("SMH_TCN_SKEW"), -1);  // 0 / 2: never / whenever it can run (tests, tuning)
+    const char *waves = getenv("SMH_TCN_WAVES");  // tuning only
+    s.has_waves = waves != nullptr, s.waves = num(waves, 0);
+    s.prefetch = num(getenv("SMH_TCN_PREFETCH"), 1) != 0;  // tuning only
+    s.split = num(getenv("SMH_TCN_SPLIT"), 1) != 0;  // 0 switches the split last tile off (tests: the two forms agree bit for bit)
+    s.skew16 = num(smh::lab_env("SMH_TCN_SKEW16"), 0) != 0;
+    return s;
+}
+
+int plan_forward(const smh_model *m, int N, bool train, bool trace, const ForwardSwitches &sw, ForwardPlan *pp) {
+    ForwardPlan &p = *pp;
+    const int T = m->cfg.patch_size;
     // patches per workgroup: up to 272 rows (17 column tiles) of LDS-resident activations, at most one
     // MFMA tile of patches, and never fewer workgroups than CUs when the batch allows it
     int gmax = 272 / T;
@@ -1209,82 +1231,32 @@ void fill_args(const smh_model *m, int N, TcnArgs *pa, size_t *plds) {
     int G = (N + 255) / 256;
     if (G < 1) G = 1;
     if (G > gmax) G = gmax;
-    if (const char *ev = getenv("SMH_TCN_G")) {  // tuning only (tools/tune_model.py)
-        const int g = atoi(ev);
-        if (g >= 1 && g <= gmax) G = g;
-    }
-    a.G = G;
+    if (sw.G >= 1 && sw.G <= gmax) G = sw.G;
+    p.G = G;
     int GRP = ((G * T + 15) / 16) * 16;
     const int head_scratch = 8 * 4 * 128 + kMaxG * kPS;  // Dense partial sums (8 parts x 4 patches x <= 128) + pre[kMaxG][kPS]
     if (GRP * SX < head_scratch) GRP = (head_scratch + SX - 1) / SX;  // the head scratch lives in one buffer
     if (GRP * SX < m->FQ * 2 * 64) GRP = (m->FQ * 2 * 64 + SX - 1) / SX;  // layer-0 A operands are staged there
     GRP = ((GRP + 15) / 16) * 16;
-    a.GRP = GRP;
+    p.GRP = GRP;
     const size_t lds_x = sizeof(float) * 2 * (size_t)(GRP + 1) * SX, lds_w = sizeof(float) * 2 * (size_t)kBlockFloats;  // + the zero rows
     const size_t lds_xch = sizeof(float) * (2 * 64 * 4 + 4);  // the exchange area of split_last (half_tile_compute)
-    a.wlds = lds_x + lds_w + lds_xch <= 156 * 1024 ? 1 : 0;  // activations (x2) + two weight slots, when they fit
-    a.split_last = 0;
-    *plds = lds_x + (a.wlds ? lds_w + lds_xch : 0);
-}
-
-// whether the forward of `a` with `units` column tiles per workgroup runs the skewed task schedule (else the barrier schedule)
-static bool skew_schedule(const TcnArgs &a, int units) {
-    const bool skew_ok = a.wlds && units <= 32 && units >= 1 && a.n_blocks * units < 2048 && a.T >= 16;  // (T >= 16: issue_ops)
-    // (13 tiles: since the lone last-round tile is shared by two waves the barrier schedule is ahead there -- W = 68 x 768 patches
-    // 130.1 against 131.5 us, W = 99 x 510 131.5 / 134.7; at 17 tiles the skew schedule stays ahead, 149.8 / 157.5)
-    bool skew = skew_ok && units >= 12 && 8 * ((units + 7) / 8) - units >= 3 && units != 13;
-    if (const char *ev = getenv("SMH_TCN_SKEW")) skew = atoi(ev) == 2 ? skew_ok : (skew && atoi(ev) != 0);
-    return skew;
-}
-
-int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
-                   hipStream_t st, const ForwardOpts &opt) {
-    TcnArgs a;
-    size_t lds;
-    fill_args(m, N, &a, &lds);
-    a.trunk_only = opt.trunk_only;
-    a.from_x0 = opt.from_x0, a.x0_shift = opt.x0_shift, a.x0_T = opt.x0_T;
-    a.x0_one = opt.from_x0 ? opt.x0_one : 0;
-    if (opt.pair && opt.pair_out) {  // two complete models in one grid (the late-fusion ensemble)
-        const smh_model *p = opt.pair;
-        SMH_REQUIRE(!tio && !opt.trunk_only && d_out && opt.pair_x, "paired full forward: inference of two whole models, each to its own output");
-        SMH_REQUIRE(p->cfg.n_feat == m->cfg.n_feat && p->cfg.patch_size == m->cfg.patch_size && p->n_blocks == m->n_blocks &&
-                        p->cfg.n_dilations == m->cfg.n_dilations && p->nW0 == m->nW0 && p->nWb == m->nWb && p->nW0 > 0 &&
-                        p->heads == m->heads && p->cfg.n_classes == m->cfg.n_classes && p->nWhA == m->nWhA && p->nhp == m->nhp &&
-                        p->out_dim == m->out_dim,
-                    "paired full forward: the two models differ in geometry or head kind");
-        a.pair_X = opt.pair_x, a.pair_W0 = p->d_W0, a.pair_Wb = p->d_Wb, a.pair_trunk = opt.pair_trunk;
-        a.pair_WhA = p->d_WhA, a.pair_hp = p->d_hp, a.pair_out = opt.pair_out, a.pair_status = p->d_status;
-    } else if (opt.pair) {
-        const smh_model *p = opt.pair;
-        SMH_REQUIRE(!tio && opt.trunk_only && d_trunk && opt.pair_x && opt.pair_trunk, "paired trunk launch: inference to the trunk taps only");
-        SMH_REQUIRE(p->cfg.n_feat == m->cfg.n_feat && p->cfg.patch_size == m->cfg.patch_size && p->n_blocks == m->n_blocks &&
-                        p->cfg.n_dilations == m->cfg.n_dilations && p->nW0 == m->nW0 && p->nWb == m->nWb && p->nW0 > 0,
-                    "paired trunk launch: the two trunks differ in geometry");
-        a.pair_X = opt.pair_x, a.pair_W0 = p->d_W0, a.pair_Wb = p->d_Wb, a.pair_trunk = opt.pair_trunk;
-        a.pair_status = a.status;  // both trunks belong to one model: row 1 reports to m's error word, as it always has
-    }
-    // timing probes (outputs invalid; training would read stale activations): only under SMH_ENABLE_PROBES=1, announced on stderr
-    if (const char *ev = smh::probe_env("SMH_TCN_BLOCKS")) a.n_blocks = atoi(ev);  // tools/tune_model.py
-    a.skip_heads = smh::probe_env("SMH_TCN_NOHEADS") ? 1 : 0;
-    if (const char *ev = smh::probe_env("SMH_TCN_TUNE")) a.tune = atoi(ev);
-    if (a.tune & 256) a.spin_limit = 1 << 10;  // test_skew_give_up_is_reported: a withheld flag must end in the error word quickly
-    a.trace = g_trace ? g_trace + (g_trace_launches++ & 1) * kTraceWords : nullptr;  // consecutive launches alternate halves
-    SMH_REQUIRE(lds <= 156 * 1024, "patch_size %d too long for the LDS-resident TCN", a.T);
+    p.wlds = lds_x + lds_w + lds_xch <= kNetLdsLimit ? 1 : 0;  // activations (x2) + two weight slots, when they fit
+    p.lds = lds_x + (p.wlds ? lds_w + lds_xch : 0);
+    SMH_REQUIRE(p.lds <= kNetLdsLimit, "patch_size %d too long for the LDS-resident TCN", T);
     // waves per workgroup: the block time is (column tiles of the busiest wave) x (time per tile) plus a fixed part, so
     // take the fewest waves in 8..12 that minimise ceil(tiles / waves): 17 tiles (4 patches of 68 frames) -> 9 waves,
     // 2 tiles each and one with 1, instead of 8 waves of which one does 3
-    const int units = (std::min(a.G, N) * a.T + 15) / 16;
+    const int units = p.units = (std::min(G, N) * T + 15) / 16;  // the forward's column tiles per workgroup, written here only
     // (only without the LDS weight slots: the 9..12-wave build is held to 170 VGPRs and spills ~60 of them, which costs more
     // than the shorter tile list saves -- training forward, 9 tiles: 134 us with 9 waves, 121 us with 8 and two register sets)
     int nwaves = 8;
-    for (int w = 9; w <= 12 && !a.wlds; ++w)
+    for (int w = 9; w <= 12 && !p.wlds; ++w)
         if ((units + w - 1) / w < (units + nwaves - 1) / nwaves) nwaves = w;
-    if (const char *ev = getenv("SMH_TCN_WAVES")) nwaves = std::max(4, std::min(12, atoi(ev)));  // tuning only
+    if (sw.has_waves) nwaves = std::max(4, std::min(12, sw.waves));
     // 8 waves (two per SIMD, 256 VGPRs each): two weight register sets, the next block's weights are read behind this
     // block's products.  More waves (170 VGPRs): one set, read at the top of the block.
-    bool prefetch = nwaves <= 8 && a.wlds;
-    if (const char *ev = getenv("SMH_TCN_PREFETCH")) prefetch = prefetch && atoi(ev) != 0;  // tuning only
+    const bool prefetch = nwaves <= 8 && p.wlds && sw.prefetch;
     // the skewed task schedule (8 waves, flags instead of barriers) whenever its tables fit -- inference and training forward
     // It pays where the barrier schedule leaves wave slots empty AND there are enough tiles for the windows to overlap
     // (tools/time_model_sizes.py, W = 68: 17 tiles 149 against 160 us, 13 tiles 130 / 134; 9 tiles 107 / 105.5; 5 tiles -- up to 256
@@ -1292,65 +1264,132 @@ int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, fl
     // full rounds of the 8 waves: 162 / 154).  SMH_TCN_SKEW=0 / 2: never / whenever it can run (tests, tuning).
     // (the schedule decodes task n into (block, tile) by multiplication, exact for n < 2048: smh_model_create accepts up to
     // nb_stacks x 16 dilations, the reference tunes nb_stacks up to 10 -- beyond the bound the barrier schedule runs)
-    const bool skew = skew_schedule(a, units);
-    if (skew && !getenv("SMH_TCN_WAVES")) nwaves = 8;
+    const bool skew_ok = p.wlds && units <= 32 && units >= 1 && m->n_blocks * units < 2048 && T >= 16;  // (T >= 16: issue_ops)
+    // (13 tiles: since the lone last-round tile is shared by two waves the barrier schedule is ahead there -- W = 68 x 768 patches
+    // 130.1 against 131.5 us, W = 99 x 510 131.5 / 134.7; at 17 tiles the skew schedule stays ahead, 149.8 / 157.5)
+    bool skew = skew_ok && units >= 12 && 8 * ((units + 7) / 8) - units >= 3 && units != 13;
+    if (sw.skew >= 0) skew = sw.skew == 2 ? skew_ok : (skew && sw.skew != 0);
+    if (skew && !sw.has_waves) nwaves = 8;
     if (skew) nwaves = std::min(nwaves, 8);
+    p.mode = skew ? kSkew : prefetch ? kPrefetch : kOneSet;
     // The 16-wave form of the skew schedule (weights in an LDS ring, four waves per SIMD): inference, when its ring fits beside
     // the activations.  LAB BUILDS ONLY (-DSMH_LAB, then SMH_TCN_SKEW16=1; the production library does not instantiate it): measured on the bench shape it runs 135.7-136.2 us against 133.6-134.2 us for the
     // 8-wave form (tools/gpu/r3_net.sh) -- twice the waves per SIMD buy nothing, i.e. the loop is not short of waves to hide
     // latency behind: exact-f32 MFMA and the VALU work of the epilogues do not overlap.  Kept as the measured
     // experiment and as a third implementation the schedule-agreement test holds bit-identical to the other two.
-    const size_t lds16 = sizeof(float) * (2 * (size_t)(a.GRP + 1) * SX + (size_t)kWeightRing * kBlockFloats + 128);  // + flags and scratch words
-    bool skew16 = false;
-    if (const char *ev = smh::lab_env("SMH_TCN_SKEW16")) skew16 = atoi(ev) != 0 && skew && !tio && !a.trace && lds16 <= 156 * 1024;
-    if (skew16) nwaves = 16, lds = lds16;
+    const size_t lds16 = sizeof(float) * (2 * (size_t)(GRP + 1) * SX + (size_t)kWeightRing * kBlockFloats + 128);  // + flags and scratch words
+    if (sw.skew16 && skew && !train && !trace && lds16 <= kNetLdsLimit) p.mode = kSkew16, nwaves = 16, p.lds = lds16;
+    p.nwaves = nwaves;
     // barrier schedule with two register sets and ONE tile in its last round (5, 9, ... tiles on 8 waves): that tile as two halves on
     // two waves of different SIMDs (half_tile_compute).  SMH_TCN_SPLIT=0 switches it off (tests: the two forms agree bit for bit).
-    a.split_last = (!skew && prefetch && nwaves == 8 && units >= 2 && (units % 8 == 1 || units % 8 == 5)) ? 1 : 0;
-    if (const char *ev = getenv("SMH_TCN_SPLIT")) a.split_last = a.split_last && atoi(ev) != 0;
-    const dim3 grid((N + a.G - 1) / a.G, opt.pair ? 2 : 1), block(64 * nwaves);
-    TrainIO io{nullptr, nullptr, nullptr, nullptr};
-    if (tio) io = *tio;
-#define SMH_LAUNCH_FWD(TR, MD, TC)                                                                                      \
-    do {                                                                                                                \
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)b3mtl_forward_kernel<TR, MD, TC>,                              \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-        hipLaunchKernelGGL((b3mtl_forward_kernel<TR, MD, TC>), grid, block, lds, st, a, d_x, m->d_W0, m->d_Wb,         \
-                           m->d_WhA, m->d_hp, d_trunk, d_out, io);                                                     \
-    } while (0)
-    if (tio) {
-        if (skew) SMH_LAUNCH_FWD(true, kSkew, false);
-        else if (prefetch) SMH_LAUNCH_FWD(true, kPrefetch, false);
-        else SMH_LAUNCH_FWD(true, kOneSet, false);
-    } else if (a.trace) {  // tools/trace_model.py: the stamped instantiations
-        if (skew) SMH_LAUNCH_FWD(false, kSkew, true);
-        else if (prefetch) SMH_LAUNCH_FWD(false, kPrefetch, true);
-        else SMH_LAUNCH_FWD(false, kOneSet, true);
-#ifdef SMH_LAB
-    } else if (skew16) {
-        SMH_LAUNCH_FWD(false, kSkew16, false);
-#endif
-    } else if (skew) {
-        SMH_LAUNCH_FWD(false, kSkew, false);
-    } else {
-        if (prefetch) SMH_LAUNCH_FWD(false, kPrefetch, false);
-        else SMH_LAUNCH_FWD(false, kOneSet, false);
+    p.split_last = (p.mode == kPrefetch && nwaves == 8 && units >= 2 && (units % 8 == 1 || units % 8 == 5) && sw.split) ? 1 : 0;
+    return SMH_OK;
+}
+
+// the forward kernel of a plan's mode: exactly the instantiations the library holds (the stamped ones: tools/trace_model.py)
+using ForwardKernel = void (*)(TcnArgs, const float *, const float *, const float *, const float *, const float *, float *, float *, TrainIO);
+static ForwardKernel pick_forward_kernel(bool train, int mode, bool trace) {
+    if (train) {
+        if (mode == kSkew) return b3mtl_forward_kernel<true, kSkew, false>;
+        if (mode == kPrefetch) return b3mtl_forward_kernel<true, kPrefetch, false>;
+        return b3mtl_forward_kernel<true, kOneSet, false>;
     }
-#undef SMH_LAUNCH_FWD
-    return smh::launch_status("b3mtl_forward_kernel");
+    if (trace) {
+        if (mode == kSkew) return b3mtl_forward_kernel<false, kSkew, true>;
+        if (mode == kPrefetch) return b3mtl_forward_kernel<false, kPrefetch, true>;
+        return b3mtl_forward_kernel<false, kOneSet, true>;
+    }
+#ifdef SMH_LAB
+    if (mode == kSkew16) return b3mtl_forward_kernel<false, kSkew16, false>;
+#endif
+    if (mode == kSkew) return b3mtl_forward_kernel<false, kSkew, false>;
+    if (mode == kPrefetch) return b3mtl_forward_kernel<false, kPrefetch, false>;
+    return b3mtl_forward_kernel<false, kOneSet, false>;
+}
+
+// what a paired launch needs of its second model: the trunk operands of m's shape ...
+static bool same_trunk_geometry(const smh_model *m, const smh_model *p) {
+    return p->cfg.n_feat == m->cfg.n_feat && p->cfg.patch_size == m->cfg.patch_size && p->n_blocks == m->n_blocks &&
+           p->cfg.n_dilations == m->cfg.n_dilations && p->nW0 == m->nW0 && p->nWb == m->nWb && p->nW0 > 0;
+}
+// ... and, where both run to their outputs, the Dense-on-trunk and head operands too
+static bool same_head_geometry(const smh_model *m, const smh_model *p) {
+    return p->heads == m->heads && p->cfg.n_classes == m->cfg.n_classes && p->nWhA == m->nWhA && p->nhp == m->nhp && p->out_dim == m->out_dim;
+}
+
+int launch_forward(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, const TrainIO *tio,
+                   hipStream_t st, const ForwardOpts &opt) {
+    const smh_model *pm = opt.pair;
+    if (pm && opt.pair_out) {  // two complete models in one grid (the late-fusion ensemble)
+        SMH_REQUIRE(!tio && !opt.trunk_only && d_out && opt.pair_x, "paired full forward: inference of two whole models, each to its own output");
+        SMH_REQUIRE(same_trunk_geometry(m, pm) && same_head_geometry(m, pm), "paired full forward: the two models differ in geometry or head kind");
+    } else if (pm) {
+        SMH_REQUIRE(!tio && opt.trunk_only && d_trunk && opt.pair_x && opt.pair_trunk, "paired trunk launch: inference to the trunk taps only");
+        SMH_REQUIRE(same_trunk_geometry(m, pm), "paired trunk launch: the two trunks differ in geometry");
+    }
+    unsigned long long *trace = g_trace ? g_trace + (g_trace_launches++ & 1) * kTraceWords : nullptr;  // consecutive launches alternate halves
+    ForwardPlan p;
+    const int rc = plan_forward(m, N, tio != nullptr, trace != nullptr, read_forward_switches(), &p);
+    if (rc) return rc;
+    TcnArgs a;
+    fill_args(m, N, p, &a);
+    a.trace = trace;
+    a.trunk_only = opt.trunk_only;
+    a.from_x0 = opt.from_x0, a.x0_shift = opt.x0_shift, a.x0_T = opt.x0_T;
+    a.x0_one = opt.from_x0 ? opt.x0_one : 0;
+    // timing probes (outputs invalid; training would read stale activations): only under SMH_ENABLE_PROBES=1, announced on stderr
+    if (const char *ev = smh::probe_env("SMH_TCN_BLOCKS")) a.n_blocks = atoi(ev);  // tools/tune_model.py
+    a.skip_heads = smh::probe_env("SMH_TCN_NOHEADS") ? 1 : 0;
+    if (const char *ev = smh::probe_env("SMH_TCN_TUNE")) a.tune = atoi(ev);
+    if (a.tune & 256) a.spin_limit = 1 << 10;  // test_skew_give_up_is_reported: a withheld flag must end in the error word quickly
+    if (pm) {  // row 1 of the grid: the second model's operands, input and outputs
+        a.pair_X = opt.pair_x, a.pair_W0 = pm->d_W0, a.pair_Wb = pm->d_Wb, a.pair_trunk = opt.pair_trunk;
+        // the trunk pair belongs to one model: row 1 reports to m's error word, as it always has
+        a.pair_status = opt.pair_out ? pm->d_status : a.status;
+        if (opt.pair_out) a.pair_WhA = pm->d_WhA, a.pair_hp = pm->d_hp, a.pair_out = opt.pair_out;
+    }
+    const TrainIO io = tio ? *tio : TrainIO{nullptr, nullptr, nullptr, nullptr};
+    return smh::launch_lds(pick_forward_kernel(tio != nullptr, p.mode, trace != nullptr), "b3mtl_forward_kernel",
+                           dim3((N + p.G - 1) / p.G, pm ? 2 : 1), dim3(64 * p.nwaves), p.lds, p.lds, st, a, d_x, m->d_W0, m->d_Wb, m->d_WhA,
+                           m->d_hp, d_trunk, d_out, io);
+}
+
+int dense_entry_ok(const char *name, const smh_model *m, const float *d_fv, int Tc, int shift, const void *d_work, size_t work_bytes,
+                   size_t need_bytes, const float *d_out, int feat_multiple, const char *short_clip_entry) {
+    SMH_REQUIRE(m && d_fv && d_work && d_out, "%s: null argument", name);
+    SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_fv) % 16) == 0 &&
+                    (reinterpret_cast<uintptr_t>(d_out) % 4) == 0,
+                "%s: d_fv and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries", name);
+    const int W = m->cfg.patch_size, F = m->cfg.n_feat;
+    if (feat_multiple == 8)
+        SMH_REQUIRE(F % 8 == 0, "%s: n_feat=%d must be a multiple of 8 (two halves of whole k steps)", name, F);
+    else
+        SMH_REQUIRE(F % feat_multiple == 0, "%s: the per-branch n_feat=%d must be a multiple of %d (whole k steps per half)", name, F, feat_multiple);
+    SMH_REQUIRE(shift >= 1 && Tc >= W, "%s: needs shift >= 1 and at least patch_size=%d frames (Tc=%d, shift=%d); "
+                "shorter chunks are tiled by get_feature_patches and take %s", name, W, Tc, shift, short_clip_entry);
+    SMH_REQUIRE(work_bytes >= need_bytes, "%s: workspace of %zu bytes, need %zu", name, work_bytes, need_bytes);
+    return SMH_OK;
 }
 
 }  // namespace smh_tcn
 
+// tests: the plan of a forward of N patches under the current switches (train: the training forward) as
+// {G, GRP, units, nwaves, mode, wlds, split_last, lds}; 0, or -1 where that forward would be refused
+extern "C" int smh_internal_tcn_plan(const smh_model *m, int N, int train, int out[8]) {
+    if (!m || N < 1 || m->cfg.block_variant != 0 || m->heads == SMH_HEADS_FUSION) return -1;
+    ForwardPlan p;
+    if (plan_forward(m, N, train != 0, false, read_forward_switches(), &p)) return -1;
+    const int v[8] = {p.G, p.GRP, p.units, p.nwaves, p.mode, p.wlds, p.split_last, (int)p.lds};
+    std::copy(v, v + 8, out);
+    return 0;
+}
+
 // tests: 1 when smh_model_forward_f32 of N patches takes the skewed block schedule, 0 when the barrier schedule (under the
 // current SMH_TCN_SKEW), -1 when that forward would be refused
 extern "C" int smh_internal_tcn_schedule(const smh_model *m, int N) {
-    if (!m || N < 1 || m->cfg.block_variant != 0 || m->heads == SMH_HEADS_FUSION) return -1;
-    TcnArgs a;
-    size_t lds;
-    fill_args(m, N, &a, &lds);
-    if (lds > 156 * 1024) return -1;
-    return smh_tcn::skew_schedule(a, (std::min(a.G, N) * a.T + 15) / 16) ? 1 : 0;
+    int plan[8];
+    if (smh_internal_tcn_plan(m, N, 0, plan)) return -1;
+    return plan[4] == kSkew || plan[4] == kSkew16 ? 1 : 0;
 }
 
 extern "C" int smh_model_create(const smh_model_cfg *cfg, smh_model **out) {
@@ -1381,22 +1420,15 @@ extern "C" int smh_model_create_heads(const smh_model_cfg *cfg, int heads, smh_m
     m->n_blocks = cfg->nb_stacks * cfg->n_dilations;
     m->heads = heads;
     for (int i = 0; i < kMaxHeads; ++i) m->head_cat[i] = 0, m->head_odim[i] = 0, m->head_sigmoid[i] = 0;
-    if (heads == SMH_HEADS_SINGLE) {  // Flatten -> Dense(n_classes) -> softmax: the '3C' slot of the canonical order is Keras' 'dense'
-        m->n_heads = 0;
-    } else if (heads == SMH_HEADS_CASCADED) {  // proposed_architectures.py:175-323: S, M, R(2) whatever n_classes is
-        m->n_heads = 3;
-        const int od[3] = {1, 1, 2}, sg[3] = {1, 1, 0};
-        for (int i = 0; i < 3; ++i) m->head_odim[i] = od[i], m->head_sigmoid[i] = sg[i];
-        m->head_cat[0] = m->head_cat[1] = kCat;
-    } else if (cfg->n_classes == 5) {  // 5_class_classification.py:150-215: S, M, N, R(3)
-        m->n_heads = 4;
-        const int od[4] = {1, 1, 1, 3}, sg[4] = {1, 1, 1, 0};
-        for (int i = 0; i < 4; ++i) m->head_odim[i] = od[i], m->head_sigmoid[i] = sg[i];
-    } else {  // proposed_architectures.py:25-80: S, M, R(2)
-        m->n_heads = 3;
-        const int od[3] = {1, 1, 2}, sg[3] = {1, 1, 0};
-        for (int i = 0; i < 3; ++i) m->head_odim[i] = od[i], m->head_sigmoid[i] = sg[i];
-    }
+    // The heads behind the Dense-on-trunk, per kind: {heads, outputs of each, sigmoid (1) or linear (0), heads that read the concatenation}
+    struct HeadShapes { int n, odim[kMaxHeads], sigmoid[kMaxHeads], n_cat; };
+    static const HeadShapes kSingle = {0, {}, {}, 0};  // Flatten -> Dense(n_classes) -> softmax: the '3C' slot of the canonical order is Keras' 'dense'
+    static const HeadShapes kSMR = {3, {1, 1, 2}, {1, 1, 0}, 0};  // proposed_architectures.py:25-80: S, M, R(2)
+    static const HeadShapes kSMRCascaded = {3, {1, 1, 2}, {1, 1, 0}, 2};  // proposed_architectures.py:175-323: S, M, R(2) whatever n_classes is
+    static const HeadShapes kSMNR = {4, {1, 1, 1, 3}, {1, 1, 1, 0}, 0};  // 5_class_classification.py:150-215: S, M, N, R(3)
+    const HeadShapes &hs = heads == SMH_HEADS_SINGLE ? kSingle : heads == SMH_HEADS_CASCADED ? kSMRCascaded : cfg->n_classes == 5 ? kSMNR : kSMR;
+    m->n_heads = hs.n;
+    for (int i = 0; i < hs.n; ++i) m->head_odim[i] = hs.odim[i], m->head_sigmoid[i] = hs.sigmoid[i], m->head_cat[i] = i < hs.n_cat ? kCat : 0;
     m->D = cfg->patch_size * C * (heads == SMH_HEADS_FUSION ? 2 : 1);
     m->NH = cfg->n_classes + kHidden * m->n_heads;
     m->n_mt = (m->NH + 15) / 16;
@@ -1564,24 +1596,18 @@ extern "C" size_t smh_model_dense_workspace_bytes(const smh_model *m, int Tc) {
 
 extern "C" int smh_model_forward_dense_f32(const smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes,
                                            float *d_out, void *stream) {
-    SMH_REQUIRE(m && d_fv && d_work && d_out, "smh_model_forward_dense_f32: null argument");
+    int rc = smh_tcn::dense_entry_ok("smh_model_forward_dense_f32", m, d_fv, Tc, shift, d_work, work_bytes, smh_model_dense_workspace_bytes(m, Tc),
+                                     d_out, 8, "smh_model_forward_f32");
+    if (rc) return rc;
     SMH_REQUIRE(m->cfg.block_variant == 0, "smh_model_forward_dense_f32: exists for block_variant 0 only");
     SMH_REQUIRE(m->heads != SMH_HEADS_FUSION, "smh_model_forward_dense_f32: no dense file-level path for an intermediate-fusion model "
                 "(two inputs): build the patches and call smh_fusion_forward_f32");
-    SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_fv) % 16) == 0 &&
-                    (reinterpret_cast<uintptr_t>(d_out) % 4) == 0,
-                "smh_model_forward_dense_f32: d_fv and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries");
     const int W = m->cfg.patch_size, F = m->cfg.n_feat;
-    SMH_REQUIRE(F % 8 == 0, "smh_model_forward_dense_f32: n_feat=%d must be a multiple of 8 (two halves of whole k steps)", F);
-    SMH_REQUIRE(shift >= 1 && Tc >= W, "smh_model_forward_dense_f32: needs shift >= 1 and at least patch_size=%d frames (Tc=%d, shift=%d); "
-                "shorter chunks are tiled by get_feature_patches and take smh_model_forward_f32", W, Tc, shift);
-    SMH_REQUIRE(work_bytes >= smh_model_dense_workspace_bytes(m, Tc), "smh_model_forward_dense_f32: workspace of %zu bytes, need %zu",
-                work_bytes, smh_model_dense_workspace_bytes(m, Tc));
     const int nP = smh_num_patches(Tc, W, shift);
     if (nP <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     float *x0 = static_cast<float *>(d_work);
-    int rc = smh_tcn::launch_l0_frames(d_fv, smh_model_w0_ptr(m), x0, F / 2, Tc, st);
+    rc = smh_tcn::launch_l0_frames(d_fv, smh_model_w0_ptr(m), x0, F / 2, Tc, st);
     if (rc) return rc;
     smh_tcn::ForwardOpts fo;
     fo.from_x0 = 1, fo.x0_shift = shift, fo.x0_T = Tc;

@@ -935,11 +935,16 @@ static int model_bf16_ok(const smh_model *m) {
 static int plan_bf16(const smh_model *m, const PackInfo &pi, int N, int split, int from_x0, TcnArgs *pa, size_t *plds,
                      SplitPlan *sp) {
     TcnArgs &a = *pa;
-    fill_args(m, N, &a, plds);
+    ForwardSwitches sw = read_forward_switches();
+    sw.skew16 = false;  // the f32 lab form's ring: *plds is the barrier kernels' size, which b3mtl_forward_bf16_kernel shares
+    ForwardPlan p;
+    const int rc = plan_forward(m, N, false, false, sw, &p);  // its G, GRP and tile count; the wave count and LDS below are this file's
+    if (rc) return rc;
+    fill_args(m, N, p, &a);
     a.from_x0 = from_x0;
-    SMH_REQUIRE(*plds <= 156 * 1024, "patch_size %d too long for the LDS-resident TCN", a.T);
+    *plds = p.lds;
     if (!split) return SMH_OK;
-    const int units_s = (std::min(a.G, N) * a.T + 15) / 16;
+    const int units_s = p.units;
     const bool two = units_s <= 24;  // at most two column tiles per wave on up to 12 waves
     int nwaves_s = two ? std::min(12, std::max(8, (units_s + 1) / 2)) : 8;
     if (const char *ev = getenv("SMH_BF16_NW")) nwaves_s = two ? std::min(12, std::max((units_s + 1) / 2, atoi(ev))) : 8;  // tuning
@@ -947,7 +952,7 @@ static int plan_bf16(const smh_model *m, const PackInfo &pi, int N, int split, i
     SMH_REQUIRE(a.n_mt <= 5, "smh_model_forward_bf16: more than five M-tiles of Dense-on-trunk outputs");
     const size_t lds_s = 4 * (size_t)(a.GRP + 1) * kRS * sizeof(__bf16) + 2 * 2 * kSlotOps * 16 + sizeof(float) * (size_t)nwaves_s * a.G * kPS;
     SMH_REQUIRE((units_s + nwaves_s - 1) / nwaves_s <= (two ? 2 : 4), "smh_model_forward_bf16: too many column tiles per wave");
-    SMH_REQUIRE(lds_s <= 156 * 1024, "patch_size %d too long for the LDS-resident split-bf16 TCN", a.T);
+    SMH_REQUIRE(lds_s <= kNetLdsLimit, "patch_size %d too long for the LDS-resident split-bf16 TCN", a.T);
     SMH_REQUIRE((size_t)pi.steps0 * 2 * 64 * 2 * 16 <= 2 * (size_t)(a.GRP + 1) * kRS * sizeof(__bf16) || from_x0,
                 "smh_model_forward_bf16: n_feat=%d too wide for the layer-0 operand staging", m->cfg.n_feat);
     *sp = SplitPlan{two, nwaves_s, lds_s};
@@ -1052,18 +1057,12 @@ extern "C" int smh_model_forward_x0_bf16(smh_model *m, const float *d_x0p, int N
 // stays exact f32, once per frame, into d_work), then the split-operand kernel reads every patch as a window of d_work.
 extern "C" int smh_model_forward_dense_bf16(smh_model *m, const float *d_fv, int Tc, int shift, void *d_work, size_t work_bytes,
                                             float *d_out, void *stream) {
-    SMH_REQUIRE(m && d_fv && d_work && d_out, "smh_model_forward_dense_bf16: null argument");
-    int rc = model_bf16_ok(m);
+    int rc = dense_entry_ok("smh_model_forward_dense_bf16", m, d_fv, Tc, shift, d_work, work_bytes, smh_model_dense_workspace_bytes(m, Tc), d_out,
+                            8, "smh_model_forward_bf16");
     if (rc) return rc;
-    SMH_REQUIRE((reinterpret_cast<uintptr_t>(d_work) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_fv) % 16) == 0 &&
-                    (reinterpret_cast<uintptr_t>(d_out) % 4) == 0,
-                "smh_model_forward_dense_bf16: d_fv and d_work are read / written with 16-byte accesses and must start on 16-byte boundaries");
+    rc = model_bf16_ok(m);
+    if (rc) return rc;
     const int W = m->cfg.patch_size, F = m->cfg.n_feat;
-    SMH_REQUIRE(F % 8 == 0, "smh_model_forward_dense_bf16: n_feat=%d must be a multiple of 8 (two halves of whole k steps)", F);
-    SMH_REQUIRE(shift >= 1 && Tc >= W, "smh_model_forward_dense_bf16: needs shift >= 1 and at least patch_size=%d frames (Tc=%d, shift=%d); "
-                "shorter chunks are tiled by get_feature_patches and take smh_model_forward_bf16", W, Tc, shift);
-    SMH_REQUIRE(work_bytes >= smh_model_dense_workspace_bytes(m, Tc), "smh_model_forward_dense_bf16: workspace of %zu bytes, need %zu",
-                work_bytes, smh_model_dense_workspace_bytes(m, Tc));
     const int nP = smh_num_patches(Tc, W, shift);
     if (nP <= 0) return 0;
     {  // the plan's refusals before anything is launched

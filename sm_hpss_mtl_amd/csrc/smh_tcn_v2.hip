@@ -206,11 +206,13 @@ b3mtl_forward_v2_kernel(TcnArgs a, const float *__restrict__ X, const float *__r
 namespace smh_tcn {
 
 int launch_forward_v2(const smh_model *m, const float *d_x, int N, float *d_out, float *d_trunk, hipStream_t st) {
+    ForwardPlan p;
+    const int rc = plan_forward(m, N, false, false, read_forward_switches(), &p);  // its G and GRP; the schedule is this kernel's own
+    if (rc) return rc;
     TcnArgs a;
-    size_t lds;
-    fill_args(m, N, &a, &lds);
-    lds = sizeof(float) * 2 * (size_t)(a.GRP + 1) * SX;  // x and y, each with its zero row; no weight slots
-    SMH_REQUIRE(lds <= 156 * 1024, "patch_size %d too long for the LDS-resident TCN", a.T);
+    fill_args(m, N, p, &a);
+    const size_t lds = sizeof(float) * 2 * (size_t)(a.GRP + 1) * SX;  // x and y, each with its zero row; no weight slots
+    SMH_REQUIRE(lds <= kNetLdsLimit, "patch_size %d too long for the LDS-resident TCN", a.T);
     const dim3 grid((N + a.G - 1) / a.G), block(512);
     SMH_CHECK_HIP(hipFuncSetAttribute((const void *)b3mtl_forward_v2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(b3mtl_forward_v2_kernel, grid, block, lds, st, a, d_x, (const float *)m->d_flat, (const float *)m->d_WhA,

@@ -1446,7 +1446,7 @@ static MfmaPlan mfma_plan(int T) {
     p.RPm = ((kMG * T + 15) / 16) * 16;
     p.lds_m = sizeof(float) * ((size_t)4 * p.RPm * SX + 4 * C * kWS + kMG * kPS + C + kZW);
     p.lds_long = sizeof(float) * ((size_t)4 * p.RPm * SX + kMG * kPS + C + kZW);  // kernels stay in global memory
-    p.short_ok = p.lds_m <= 156 * 1024 && T <= kMfmaMaxT, p.long_ok = p.lds_long <= 156 * 1024 && T <= kMfmaLongT;
+    p.short_ok = p.lds_m <= kNetLdsLimit && T <= kMfmaMaxT, p.long_ok = p.lds_long <= kNetLdsLimit && T <= kMfmaLongT;
     return p;
 }
 
@@ -1548,11 +1548,11 @@ static int train_step(smh_trainer *t, const float *const *x, int nx, const float
     } else {
         const int RP = kBG * ba.T;
         size_t lds = sizeof(float) * ((size_t)4 * RP * kBS + 2 * (3 * C * C + C * C) + C + 3 * RP + kBG * kPS);
-        if (lds > 156 * 1024) {  // long patches (the reference's W = 249): no room for the transposed kernel copies
+        if (lds > kNetLdsLimit) {  // long patches (the reference's W = 249): no room for the transposed kernel copies
             ba.use_wt = 0;
             lds -= sizeof(float) * (3 * C * C + C * C);
         }
-        SMH_REQUIRE(lds <= 156 * 1024, "patch_size %d too long for the backward kernel (at most 264 frames)", ba.T);
+        SMH_REQUIRE(lds <= kNetLdsLimit, "patch_size %d too long for the backward kernel (at most 264 frames)", ba.T);
         SMH_CHECK_HIP(hipFuncSetAttribute((const void *)tcn_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(tcn_backward_kernel, dim3((N + kBG - 1) / kBG), dim3(kBThreads), lds, st, ba, x[0], m->d_flat, t->d_acts,
                            d_drop_tcn, t->d_dpre, t->d_grad);

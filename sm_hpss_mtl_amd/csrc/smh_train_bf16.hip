@@ -606,8 +606,6 @@ tcn_backward_bf16_kernel(BwdArgs a, BwdGeo geo, const float *__restrict__ X, con
                wave, a.n_blocks, tph[0], tph[1], tph[2], tph[3], tph[4], tph[5], tph[6]);
 }
 
-constexpr size_t kLdsMax = 160 * 1024;
-
 bool bwd_geo(int T, int n_dil, BwdGeo *g) {
     if (T < 1 || T > 128) return false;
     g->units = (T + 15) / 16;
@@ -625,8 +623,8 @@ bool bwd_geo(int T, int n_dil, BwdGeo *g) {
     g->per_patch = g->o_du + 2 * g->h_du;
     g->per_patch = (g->per_patch + 15) / 16 * 16;
     if ((size_t)16 * g->units * SX * sizeof(float) > (size_t)g->per_patch) return false;  // the tail's f32 rows live on the patch's images
-    g->G = (size_t)2 * g->per_patch + kSlotBytes <= kLdsMax ? 2 : 1;
-    return (size_t)g->G * g->per_patch + kSlotBytes <= kLdsMax;
+    g->G = (size_t)2 * g->per_patch + kSlotBytes <= (size_t)smh::kLdsBytesPerCU ? 2 : 1;
+    return (size_t)g->G * g->per_patch + kSlotBytes <= (size_t)smh::kLdsBytesPerCU;
 }
 
 }  // namespace

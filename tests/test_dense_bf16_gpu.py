@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from oracle import b3_mtl, frontend as ofe
+from tests import tcn_plans
 
 pytestmark = pytest.mark.gpu
 
@@ -70,7 +71,7 @@ def test_table_matches_the_plan_and_stays_in_bounds():
         assert len(starts) == N == len(range(W // 2, Tc - W // 2, shift))
         assert starts == [min(p * shift, Tc - W) for p in range(N)]
         if N:
-            assert G == min(-(-N // 256), 272 // W)
+            assert G == tcn_plans.group(W, 240, N)[0]
             last = starts[-1] + W - 1
             assert 0 <= starts[0] and last <= Tc - 1 and Tc + last <= 2 * Tc - 1
 
