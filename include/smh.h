@@ -530,6 +530,22 @@ int smh_noise_augment_f32(const float *d_x, float *d_out, size_t n, float scale,
 int smh_dropout_masks_f32(float *d_out, size_t n_a, float keep_a, size_t n_b, float keep_b, unsigned long long seed,
                           unsigned long long offset, void *stream);
 
+/* ---- a16: the fine-tuning feed of the segmentation driver: a batch of windows out of a RESIDENT featuregram, one launch
+ * (csrc/smh_gather.hip; DAFx12_Speech_Music_Detection_B3_MTL_v2.py: generator :346-436 -> get_feature_patches :260-294).
+ * out[n] (time-major: [t][f], image: [f][t]) = FV[f][base[n] + (first[n] + t) % period[n]], t < W, f < F, plus N(0, noise_scale)
+ * drawn exactly as smh_noise_augment_f32(out, out, N*W*F, noise_scale, seed, offset) would draw it over the finished batch
+ * (noise_scale == 0: a bit copy).  The periodic form is the tile-if-short rule (:262-265): a part shorter than W is repeated, so
+ * a window of it wraps inside [base, base + period); with period >= first + W it is a plain window.
+ * FV is (F, T) row-major on the device; h_desc is a HOST table of N x 3 int32 (base, period, first), uploaded through a staging
+ * slot of the context (so a capturing stream is refused); patch_layout as for smh_extract_patches_f32: 0 = image (N, F, W),
+ * 1 = time-major (N, W, F).  d_out: 16-byte aligned.  Every offset is 64-bit (F * T may exceed 2^31).
+ * Checked on the host before anything is enqueued (SMH_E_INVALID, text in smh_last_error, d_out unwritten): null pointers;
+ * N < 0, W < 1, F < 1; another patch_layout; noise_scale < 0; d_out misaligned; a row with base < 0, period < 1, first < 0 or
+ * base + period > T.  N == 0 returns SMH_OK and launches nothing.                                                        */
+int smh_gather_windows_f32(const smh_ctx *ctx, const float *d_FV, int F, long long T, const int *h_desc, int N, int W,
+                           int patch_layout, float noise_scale, unsigned long long seed, unsigned long long offset,
+                           float *d_out, void *stream);
+
 /* ---- a14: one training step = what model.fit runs per batch (Proposed_Work_Results.py:298-307) for the
  * model compiled at lib/proposed_architectures.py:156-165: BCE (S, M[, N]) + MSE (R) + CCE (3C) with optional
  * loss_weights, l2(0.01) on the Dense(16) kernels, SGD(momentum, clipnorm, lr from ExponentialDecay).

@@ -93,6 +93,8 @@ SIGNATURES = {
     "smh_medfilt1d_f32": (_i, [_fp, _i, _i, _i, _fp, _vp]),
     "smh_noise_augment_f32": (_i, [_fp, _fp, _sz, C.c_float, C.c_ulonglong, C.c_ulonglong, _vp]),
     "smh_dropout_masks_f32": (_i, [_fp, _sz, C.c_float, _sz, C.c_float, C.c_ulonglong, C.c_ulonglong, _vp]),
+    "smh_gather_windows_f32": (_i, [_vp, _fp, _i, C.c_longlong, C.POINTER(C.c_int), _i, _i, _i, C.c_float, C.c_ulonglong,
+                                    C.c_ulonglong, _fp, _vp]),
     "smh_cnn_trainer_create": (_i, [_vp, _i, C.POINTER(C.c_void_p)]),
     "smh_cnn_trainer_destroy": (None, [_vp]),
     "smh_cnn_trainer_grad_ptr": (_vp, [_vp]),

@@ -102,6 +102,12 @@ int run_sub_batches(size_t n, size_t fixed, size_t work_bytes, hipStream_t st,
 int run_alone(const Layout &p, int B, int W, int shift, int fv_rows, float *d_fv, float *d_patches,
               const std::function<bool(int)> &taken, const std::function<int(int, int, int, float *, float *)> &alone);
 
+// An entry WITHOUT a workspace argument that needs a small host table on the device (smh_gather.hip): the table goes through a
+// pinned slot of the context into the slot's own device twin, stream-ordered on st, and launch(d_table) enqueues the kernel that
+// reads it; the slot is reused only after that kernel has finished.  Refuses a capturing stream before anything is enqueued.
+int launch_with_table(const smh_ctx *ctx, const char *who, const void *src, size_t bytes, hipStream_t st,
+                      const std::function<int(const void *)> &launch);
+
 }  // namespace smh_rag
 
 namespace smh_stft {

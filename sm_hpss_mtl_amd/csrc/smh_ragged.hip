@@ -35,6 +35,8 @@ struct Staging {
     struct Slot {
         void *host = nullptr;
         size_t cap = 0;
+        void *dev = nullptr;  // device twin of the slot, for the entries without a workspace of their own (launch_with_table)
+        size_t dev_cap = 0;
         hipEvent_t ev = nullptr;
         bool in_flight = false;
     } slot[kSlots];
@@ -46,6 +48,7 @@ void destroy_staging(Staging *s) {
     for (auto &sl : s->slot) {
         if (sl.ev) (void)hipEventDestroy(sl.ev);
         if (sl.host) (void)hipHostFree(sl.host);
+        if (sl.dev) (void)hipFree(sl.dev);
     }
     delete s;
 }
@@ -69,10 +72,10 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kWalkFrames = 128;  // frames per walk item: 64 lanes x a pair of frames
 constexpr int kFinalFrames = 64;  // frames per finalisation item
 
-// host -> device copy of a call's tables through a pinned slot of the context (ring of four; a slot is reused only after its
-// previous copy has completed, which in practice it long has)
-int stage_upload(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst, hipStream_t st) {
-    std::lock_guard<std::mutex> lock(ctx->rag_mu);
+// The next slot of the context's staging ring (four; call with rag_mu held), ready to take `bytes`: its event exists, whatever used
+// it last -- a copy, or the kernel that read its device twin -- has completed (in practice it long has), and its pinned buffer, and
+// with `twin` its device buffer too, hold at least `bytes`.
+int acquire_slot(const smh_ctx *ctx, size_t bytes, bool twin, smh_rag::Staging::Slot **out) {
     if (!ctx->rag_staging) ctx->rag_staging = new smh_rag::Staging();
     smh_rag::Staging &sg = *ctx->rag_staging;
     smh_rag::Staging::Slot &sl = sg.slot[sg.next];
@@ -82,17 +85,32 @@ int stage_upload(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst,
         SMH_CHECK_HIP(hipEventSynchronize(sl.ev));
         sl.in_flight = false;
     }
+    const size_t cap = align_up(std::max<size_t>(bytes, 64 * 1024), 64 * 1024);
     if (sl.cap < bytes) {
         if (sl.host) SMH_CHECK_HIP(hipHostFree(sl.host));
         sl.host = nullptr, sl.cap = 0;
-        const size_t cap = align_up(std::max<size_t>(bytes, 64 * 1024), 64 * 1024);
         SMH_CHECK_HIP(hipHostMalloc(&sl.host, cap, hipHostMallocDefault));
         sl.cap = cap;
     }
-    memcpy(sl.host, src, bytes);
-    SMH_CHECK_HIP(hipMemcpyAsync(d_dst, sl.host, bytes, hipMemcpyHostToDevice, st));
-    SMH_CHECK_HIP(hipEventRecord(sl.ev, st));
-    sl.in_flight = true;
+    if (twin && sl.dev_cap < bytes) {
+        if (sl.dev) SMH_CHECK_HIP(hipFree(sl.dev));
+        sl.dev = nullptr, sl.dev_cap = 0;
+        SMH_CHECK_HIP(hipMalloc(&sl.dev, cap));
+        sl.dev_cap = cap;
+    }
+    *out = &sl;
+    return SMH_OK;
+}
+
+// host -> device copy of a call's tables through a pinned slot of the context
+int stage_upload(const smh_ctx *ctx, const void *src, size_t bytes, void *d_dst, hipStream_t st) {
+    std::lock_guard<std::mutex> lock(ctx->rag_mu);
+    smh_rag::Staging::Slot *sl = nullptr;
+    if (int rc = acquire_slot(ctx, bytes, false, &sl)) return rc;
+    memcpy(sl->host, src, bytes);
+    SMH_CHECK_HIP(hipMemcpyAsync(d_dst, sl->host, bytes, hipMemcpyHostToDevice, st));
+    SMH_CHECK_HIP(hipEventRecord(sl->ev, st));
+    sl->in_flight = true;
     return SMH_OK;
 }
 
@@ -586,6 +604,22 @@ int run_sub_batches(size_t n, size_t fixed, size_t work_bytes, hipStream_t st,
         b0 = b1;
     }
     return SMH_OK;
+}
+
+int launch_with_table(const smh_ctx *ctx, const char *who, const void *src, size_t bytes, hipStream_t st,
+                      const std::function<int(const void *)> &launch) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return smh::set_error(SMH_E_INVALID, "%s uploads its table from a staging buffer: it cannot be captured in a graph", who);
+    std::lock_guard<std::mutex> lock(ctx->rag_mu);
+    Staging::Slot *sl = nullptr;
+    if (int rc = acquire_slot(ctx, bytes, true, &sl)) return rc;
+    memcpy(sl->host, src, bytes);
+    SMH_CHECK_HIP(hipMemcpyAsync(sl->dev, sl->host, bytes, hipMemcpyHostToDevice, st));
+    const int rc = launch(sl->dev);
+    SMH_CHECK_HIP(hipEventRecord(sl->ev, st));  // behind the kernel (also after a failed launch: the copy is enqueued)
+    sl->in_flight = true;
+    return rc;
 }
 
 int run_alone(const Layout &p, int B, int W, int shift, int fv_rows, float *d_fv, float *d_patches, const std::function<bool(int)> &taken,
