@@ -15,6 +15,8 @@
 // layers at small batch) are split along K into ordered partial sums (deterministic, no atomics).  Max-pooling, local
 // response normalisation, Jang's mel-scale kernels (240 small strided convolutions) and the heads are small
 // HBM-bound VALU kernels.
+#include <climits>
+
 #include "smh_cnn_impl.h"
 
 extern "C" int smh_cnn_create(const smh_cnn_cfg *cfg, smh_cnn **out) {
@@ -190,34 +192,21 @@ static int forward_impl(const smh_cnn *m, const float *d_x, int N, float *d_out,
         for (const Layer &L : m->layers) {
             float *dst = w.act[pp];
             if (L.op == kConv) {
-                ConvArgs a{};
-                a.x = src, a.w = m->d_flat + m->tensors[L.t_kernel].off;
-                a.es = m->d_fold + L.es_off, a.eb = a.es + L.OC;
-                a.y = dst, a.partial = w.partial, a.lut = m->d_lut + L.lut_off;
-                a.H = L.H, a.W = L.W, a.Cin = L.C, a.OH = L.OH, a.OW = L.OW, a.Cout = L.OC, a.K = L.K;
-                a.M = n * L.OH * L.OW;
-                a.sh = L.sh, a.sw = L.sw, a.pt = L.pt, a.pl = L.pl, a.act = L.act;
-                a.ksteps = L.Kp / (bf16 ? BKB : BK);
-                a.Kp = L.Kp;
-                a.vec4 = (L.C % 4 == 0) ? 1 : 0;
-                const int bn = L.OC <= 64 ? 64 : 128;
-                const int mt = (a.M + BM - 1) / BM, nt = (L.OC + bn - 1) / bn;
-                const int mt_plan = (plan_images(m, n) * L.OH * L.OW + BM - 1) / BM;
-                a.ksplit = choose_split(mt_plan, nt, L.Kp / BK);  // the same plan for both precisions (workspace sizing)
-                if (a.ksplit > a.ksteps) a.ksplit = a.ksteps;
-                a.ksteps_per = (a.ksteps + a.ksplit - 1) / a.ksplit;
                 SMH_REQUIRE(L.OC % 4 == 0, "smh_cnn: Cout=%d is not a multiple of 4", L.OC);
-                const dim3 grid(mt, nt, a.ksplit);
-                if (bf16) {
+                ConvArgs a = conv_args(m, L, n);
+                a.x = src, a.w = m->d_flat + m->tensors[L.t_kernel].off;
+                a.es = m->d_fold + L.es_off, a.eb = a.es + L.OC, a.act = L.act;
+                a.y = dst, a.partial = w.partial;
+                const GemmPlan p = plan_forward(m->cfg.kind, L, n, bf16);
+                if (bf16) {  // the same plan on the bf16 kernel's k-steps, the transposed bf16 kernels as a second operand
+                    a.ksplit = p.ksplit, a.ksteps = p.ksteps, a.ksteps_per = p.ksteps_per;
+                    const dim3 grid(p.mt, p.nt, p.ksplit);
                     const __bf16 *wt = reinterpret_cast<const __bf16 *>(m->d_wbf) + L.wbf_off;
-                    if (bn == 64) hipLaunchKernelGGL(conv_gemm_bf16_kernel<64>, grid, dim3(256), 0, st, a, wt);
+                    if (p.bn == 64) hipLaunchKernelGGL(conv_gemm_bf16_kernel<64>, grid, dim3(256), 0, st, a, wt);
                     else hipLaunchKernelGGL(conv_gemm_bf16_kernel<128>, grid, dim3(256), 0, st, a, wt);
-                } else if (bn == 64) hipLaunchKernelGGL(conv_gemm_kernel<64>, grid, dim3(256), 0, st, a);
-                else hipLaunchKernelGGL(conv_gemm_kernel<128>, grid, dim3(256), 0, st, a);
-                if (a.ksplit > 1) {
-                    const size_t MN = (size_t)a.M * L.OC;
-                    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((MN + 255) / 256)), dim3(256), 0, st,
-                                       (const float *)w.partial, a.ksplit, MN, L.OC, a.es, a.eb, L.act, dst);
+                    finish_split<0>(a, p, st);
+                } else {
+                    launch_conv_gemm<0>(a, p, st);
                 }
             } else if (L.op == kPool) {
                 const size_t total = (size_t)n * L.OH * L.OW * L.C;
@@ -253,4 +242,49 @@ static int forward_impl(const smh_cnn *m, const float *d_x, int N, float *d_out,
         hipLaunchKernelGGL(heads_kernel, dim3(n), dim3(256), 0, st, src, ha, d_out + (size_t)n0 * m->out_dim);
     }
     return smh::launch_status("smh_cnn forward");
+}
+
+// tests: the launch plan of layer `layer` under the current switches, from the functions the launchers call.  what = 0 / 1: inference
+// forward of one pass of N images, f32 / bf16; 2: training forward; 3: weight gradient; 4: data gradient (2-4: a batch of N, a partial
+// buffer of cap_floats); 5: a column reduction over the layer's (N * OH * OW) x OC output.  out = {bn, mt, nt, ksteps, ksplit,
+// ksteps_per, partial_floats, 0}; a small-K weight gradient {0, 0, 0, 0, nb, rows_per_block, partial_floats, 1}; a column reduction
+// {vec, slabs, rows_per_pass, rows_per_block, blocks, 0, 0, 0}.  Returns 0, or -1 where the layer has no such launch -- or where a
+// count does not fit an int (no graph comes near: a split GEMM has fewer than 256 tiles, so at most 16 * 256 * 128 * 128 = 67 M floats
+// of forward partials, and the other partials are bounded by cap_floats).
+extern "C" int smh_internal_cnn_plan(const smh_cnn *m, int layer, int what, int N, size_t cap_floats, int out[8]) {
+    if (!m || layer < 0 || layer >= (int)m->layers.size() || N < 1 || m->layers[layer].op != kConv) return -1;
+    const Layer &L = m->layers[layer];
+    const CnnSwitches sw = read_cnn_switches();
+    GemmPlan g{};
+    int v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (what == 0 || what == 1) {
+        g = plan_forward(m->cfg.kind, L, N, what == 1);
+    } else if (what == 2) {
+        g = plan_train_forward(L, N, cap_floats);
+    } else if (what == 3) {
+        const WgradPlan w = plan_wgrad(L, N, cap_floats, sw);
+        g = w.gemm;
+        g.partial_floats = w.partial_floats;
+        if (w.smallk) v[4] = w.nb, v[5] = w.rows_per_block, v[7] = 1;
+    } else if (what == 4 && layer > 0) {
+        g = plan_dgrad(L, N, cap_floats, sw);
+    } else if (what == 5) {
+        const ColReducePlan c = plan_col_reduce((size_t)N * L.OH * L.OW, L.OC);
+        if (c.rows_per_block > INT_MAX || c.blocks > INT_MAX) return -1;
+        const int cv[8] = {c.vec, (int)c.slabs, (int)c.rows_per_pass, (int)c.rows_per_block, (int)c.blocks, 0, 0, 0};
+        std::copy(cv, cv + 8, out);
+        return 0;
+    } else {
+        return -1;
+    }
+    if (g.partial_floats > INT_MAX) return -1;
+    if (!v[7]) v[0] = g.bn, v[1] = g.mt, v[2] = g.nt, v[3] = g.ksteps, v[4] = g.ksplit, v[5] = g.ksteps_per;
+    v[6] = (int)g.partial_floats;
+    std::copy(v, v + 8, out);
+    return 0;
+}
+
+// tests: floats of the partial buffer a trainer of this model for max_batch images allocates
+extern "C" size_t smh_internal_cnn_partial_floats(const smh_cnn *m, int max_batch) {
+    return m ? trainer_partial_floats(m->layers, max_batch) : 0;
 }

@@ -3,11 +3,13 @@
 // unit gets its own copy of the kernels it launches.
 #pragma once
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "smh_cnn_plan.h"
 #include "smh_common.h"
 
 namespace {
@@ -15,7 +17,6 @@ namespace {
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-constexpr int BM = 128, BK = 16;
 constexpr float kBnEps = 1e-3f;
 constexpr int kMaxHeads = 4, kHidden = 16;
 enum Act { kNone = 0, kRelu = 1, kTanh = 2 };
@@ -195,13 +196,18 @@ __global__ void splitk_epilogue_kernel(const float *__restrict__ partial, int S,
     y[i] = activate(fmaf(v, es[n], eb[n]), act);
 }
 
+// The same ordered sum without an epilogue, for the weight gradients' partials.  Declared here because finish_split<1> names it, but
+// DEFINED in smh_cnn_train.hip only: MODE 1 (finish_split<1>, launch_conv_gemm<1>) may be instantiated from that file alone.  (Defined
+// here, the kernel would also be emitted into the inference unit's code object.)
+__global__ void partial_sum_kernel(const float *__restrict__ partial, int S, size_t n, float *__restrict__ out);
+
 // ---- mixed-precision variant: bf16 operands (v_mfma_f32_32x32x16_bf16), f32 accumulation and epilogue --------------------
 // Same implicit GEMM; activations are rounded to bf16 while the im2col gather stages them in LDS, the kernels are read
 // from a transposed bf16 copy [Cout][Kp] (k contiguous: one 16-byte load / LDS write / operand read per 8 k).
 // LDS images are [m][k] and [n][k] with 40-element rows (80 bytes: 16-byte aligned, conflict-free per 16 lanes).
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
 typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
-constexpr int BKB = 32, BKP = 40;
+constexpr int BKP = 40;
 
 template <int BN>
 __global__ void __launch_bounds__(256) conv_gemm_bf16_kernel(ConvArgs a, const __bf16 *__restrict__ wt) {
@@ -485,25 +491,6 @@ struct Tensor {
     size_t off, count;
 };
 
-enum Op { kConv, kPool, kLrnRelu, kMelCl };
-struct Layer {
-    Op op;
-    int H, W, C, OH, OW, OC;            // input / output image geometry (Dense: H = W = 1)
-    int kh, kw, sh, sw, pt, pl, act;
-    int t_kernel = -1, t_bias = -1, t_bn = -1;  // parameter table indices (bn = gamma; beta, mean, var follow)
-    size_t es_off = 0;                   // folded scale/shift in d_fold
-    int K = 0, Kp = 0;
-    size_t lut_off = 0;
-    size_t wbf_off = 0;                  // this layer's transposed bf16 kernel [OC][Kp] in d_wbf (bf16 elements)
-    float drop = 0.f;                    // Dropout rate behind this layer's activation (training only)
-    int l2 = 0;                          // kernel_regularizer=l2() on this layer's kernel (Jang)
-};
-
-// the single-task baselines (lib/baseline_architectures.py): the trunk, then Dense(n_classes) + softmax, no S / M / R heads
-inline bool cnn_single(int kind) {
-    return kind == SMH_CNN_DOUKHAN_SINGLE || kind == SMH_CNN_PAPAKOSTAS_SINGLE || kind == SMH_CNN_JANG_SINGLE;
-}
-
 }  // namespace
 
 struct smh_cnn {
@@ -775,12 +762,6 @@ int build_graph(smh_cnn *m, std::vector<MelCl> &mel) {
     return SMH_OK;
 }
 
-constexpr int kChunk = 64;  // images per pass through the layer list (bounds the activation workspace)
-// Images the split-K plan of a forward pass of n images is made for.  The single-task kinds plan every pass as a full one: the order
-// in which a row's products are summed then depends on the layer alone, so a row has the same bits in any batch and in any pass.
-// (The MTL kinds keep the plan that follows the pass, and with it their bits.)
-inline int plan_images(const smh_cnn *m, int n) { return cnn_single(m->cfg.kind) ? kChunk : n; }
-
 struct Work {
     float *act[2];
     float *partial;
@@ -788,39 +769,11 @@ struct Work {
 };
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-int choose_split(int mtiles, int ntiles, int ksteps) {
-    int s = 1;
-    const int blocks = mtiles * ntiles;
-    if (blocks >= 1 && blocks < 256 && ksteps >= 32) {
-        s = (512 + blocks - 1) / blocks;
-        if (s > 16) s = 16;
-        if (s > ksteps / 8) s = ksteps / 8;
-        if (s < 1) s = 1;
-    }
-    return s;
-}
-
 Work carve(const smh_cnn *m, void *base, int N) {
     Work w{};
     const int n = N < 1 ? 1 : (N < kChunk ? N : kChunk);
     w.act_floats = m->max_act * (size_t)n;
-    size_t part = 0;
-    for (const Layer &L : m->layers)
-        if (L.op == kConv) {
-            const int M = n * L.OH * L.OW, Mplan = plan_images(m, n) * L.OH * L.OW;
-            const int bn = L.OC <= 64 ? 64 : 128;
-            const int s = choose_split((Mplan + BM - 1) / BM, (L.OC + bn - 1) / bn, L.Kp / BK);
-            if (s > 1) part = std::max(part, (size_t)s * M * L.OC);
-        }
-    if (N > kChunk && N % kChunk)  // the ragged last chunk may split K differently
-        for (const Layer &L : m->layers)
-            if (L.op == kConv) {
-                const int M = (N % kChunk) * L.OH * L.OW, Mplan = plan_images(m, N % kChunk) * L.OH * L.OW;
-                const int bn = L.OC <= 64 ? 64 : 128;
-                const int s = choose_split((Mplan + BM - 1) / BM, (L.OC + bn - 1) / bn, L.Kp / BK);
-                if (s > 1) part = std::max(part, (size_t)s * M * L.OC);
-            }
-    w.partial_floats = part;
+    w.partial_floats = forward_partial_floats(m->cfg.kind, m->layers, N);
     char *p = (char *)base;
     size_t off = 0;
     for (int i = 0; i < 2; ++i) {
@@ -828,9 +781,45 @@ Work carve(const smh_cnn *m, void *base, int N) {
         off += align256(w.act_floats * sizeof(float));
     }
     w.partial = p ? (float *)(p + off) : nullptr;
-    off += align256(part * sizeof(float));
+    off += align256(w.partial_floats * sizeof(float));
     w.bytes = off;
     return w;
+}
+
+// The geometry of layer L's own GEMM over n images (forward, weight gradient); the call site adds operands, epilogue and activation.
+// Every field is set for every launch, read or not: the f32 kernels never read Kp, and MODE 1 (which finds its pixels through rowinfo)
+// never reads sh / sw / pt / pl / vec4 / act / es / eb.
+ConvArgs conv_args(const smh_cnn *m, const Layer &L, int n) {
+    ConvArgs a{};
+    a.lut = m->d_lut + L.lut_off;
+    a.H = L.H, a.W = L.W, a.Cin = L.C, a.OH = L.OH, a.OW = L.OW, a.Cout = L.OC, a.K = L.K, a.Kp = L.Kp;
+    a.M = n * L.OH * L.OW;
+    a.sh = L.sh, a.sw = L.sw, a.pt = L.pt, a.pl = L.pl;
+    a.vec4 = (L.C % 4 == 0) ? 1 : 0;
+    return a;
+}
+
+// the ordered sum of a split GEMM's partials: MODE 0 with the epilogue into a.y, MODE 1 plain
+template <int MODE>
+void finish_split(const ConvArgs &a, const GemmPlan &p, hipStream_t st) {
+    if (p.ksplit == 1) return;
+    const size_t n = (size_t)(MODE == 0 ? a.M : a.K) * a.Cout;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if constexpr (MODE == 0)
+        hipLaunchKernelGGL(splitk_epilogue_kernel, grid, dim3(256), 0, st, (const float *)a.partial, p.ksplit, n, a.Cout, a.es, a.eb,
+                           a.act, a.y);
+    else
+        hipLaunchKernelGGL(partial_sum_kernel, grid, dim3(256), 0, st, (const float *)a.partial, p.ksplit, n, a.y);
+}
+// conv_gemm_kernel under plan p, and its split finish
+template <int MODE>
+void launch_conv_gemm(ConvArgs a, const GemmPlan &p, hipStream_t st) {
+    assert(p.mt >= 1 && p.nt >= 1 && p.ksplit >= 1 && (p.bn == 64 || p.bn == 128));  // a plan made by gemm_plan, not an empty one
+    a.ksplit = p.ksplit, a.ksteps = p.ksteps, a.ksteps_per = p.ksteps_per;
+    const dim3 grid(p.mt, p.nt, p.ksplit);
+    if (p.bn == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, MODE>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_gemm_kernel<128, MODE>), grid, dim3(256), 0, st, a);
+    finish_split<MODE>(a, p, st);
 }
 
 }  // namespace

@@ -18,8 +18,6 @@
 // The single-task kinds (lib/baseline_architectures.py:62-108, 147-175, 358-442; compiled at :114-117) take the head of the
 // single-task TCN trainer (smh_train_single.hip) in place of heads_train_kernel; Jang's single-task graph carries l1_l2() on its mel
 // kernels only (optimiser segment kind 4).
-#include <cstdlib>
-
 #include "smh_cnn_impl.h"
 #include "smh_model.h"
 
@@ -30,7 +28,6 @@ constexpr float kL1 = 0.01f;  // l1_l2(): the Keras defaults l1 = l2 = 0.01
 static_assert(kL1 == kL2, "l2_partial_kernel sums w^2 + |w| under one factor");
 constexpr float kBnMomentum = 0.99f;
 constexpr int kPS = smh_tcn::kPS;
-constexpr int kMaxRed = 1024;  // row chunks of a column reduction
 
 // ---- column reductions over a row-major (M x C) matrix ---------------------------------------------------------
 // F = 0: sum z           F = 1: sum (z - mean)^2          F = 2: g = relu'/dropout of dA; sums of g and g * xhat
@@ -370,7 +367,6 @@ __global__ void rowinfo_kernel(int H, int W, int C, int OH, int OW, int sh, int 
 // dW[K x 64-wide column block] for a shallow first layer (K = kh*kw*Cin <= 32, e.g. conv1: 20): the MFMA tile would be
 // 84 % padding, so this one runs on the VALU.  Workgroup = 64 output channels x 4 row groups; 64 output pixels at a time
 // have their K taps staged in LDS (broadcast reads), every lane owns one channel and K accumulators.
-constexpr int kSmallK = 32;
 __global__ void __launch_bounds__(256) wgrad_smallk_kernel(const float *__restrict__ x, const float *__restrict__ dz,
                                                            const int2 *__restrict__ lut, const int2 *__restrict__ rowinfo, int H,
                                                            int W, int K, int Cout, int M, int rows_per_block,
@@ -636,45 +632,15 @@ struct smh_cnn_trainer {
 
 namespace {
 
-int wgrad_split(int blocks, int ksteps, size_t out_floats, size_t cap_floats) {
-    int s = 1;
-    if (blocks < 1024 && ksteps >= 32) {
-        s = (1024 + blocks - 1) / blocks;
-        if (s > ksteps / 16) s = ksteps / 16;
-        if (s > 256) s = 256;
-        while (s > 1 && (size_t)s * out_floats > cap_floats) --s;
-        if (s < 1) s = 1;
-    }
-    return s;
-}
-
-template <int MODE>
-void launch_gemm(const ConvArgs &a, int rows, int bn, hipStream_t st) {
-    const dim3 grid((rows + BM - 1) / BM, (a.Cout + bn - 1) / bn, a.ksplit);
-    if (bn == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, MODE>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_gemm_kernel<128, MODE>), grid, dim3(256), 0, st, a);
-}
-
 // column sums of an (M x C) matrix into dst0 (and dst1): reduction + ordered finish
 template <int F>
 int col_reduce(smh_cnn_trainer *t, RedArgs r, int nv, float scale, int mode, float bessel, float *dst0, float *dst1,
                hipStream_t st) {
-    const int C = r.C;
-    const int cq = C >> 2;
-    const bool vec = (C & 3) == 0 && ((cq <= 256 && 256 % cq == 0) || cq % 256 == 0);  // the kernel's own test
-    const size_t rows_per_pass = vec ? (cq < 256 ? 256 / cq : 1) : 1;
-    const unsigned slabs = vec && cq > 256 ? cq / 256 : 1;
-    size_t rpb = vec ? rows_per_pass * 16 : 64;
-    size_t nb = (r.M + rpb - 1) / rpb;
-    if (nb > kMaxRed) {
-        rpb = (r.M + kMaxRed - 1) / kMaxRed;
-        rpb = (rpb + rows_per_pass - 1) / rows_per_pass * rows_per_pass;
-        nb = (r.M + rpb - 1) / rpb;
-    }
-    r.rows_per_block = (int)rpb;
-    hipLaunchKernelGGL(colred_kernel<F>, dim3((unsigned)nb, slabs), dim3(256), 0, st, r, t->d_red);
-    hipLaunchKernelGGL(colred_finish_kernel, dim3(nblk(C, 64)), dim3(1024), 0, st, (const float *)t->d_red, (int)nb, C, nv, scale,
-                       mode, bessel, r.mean, dst0, dst1);
+    const ColReducePlan p = plan_col_reduce(r.M, r.C);
+    r.rows_per_block = (int)p.rows_per_block;
+    hipLaunchKernelGGL(colred_kernel<F>, dim3((unsigned)p.blocks, p.slabs), dim3(256), 0, st, r, t->d_red);
+    hipLaunchKernelGGL(colred_finish_kernel, dim3(nblk(r.C, 64)), dim3(1024), 0, st, (const float *)t->d_red, (int)p.blocks, r.C, nv,
+                       scale, mode, bessel, r.mean, dst0, dst1);
     return smh::launch_status("colred_kernel");
 }
 
@@ -746,13 +712,7 @@ extern "C" int smh_cnn_trainer_create(smh_cnn *m, int max_batch, smh_cnn_trainer
     }
     t->head_bstat = bstat, bstat += kMaxHeads * 32;
     t->g_floats = maxg * NB;
-    t->partial_floats = (size_t)48 << 20;  // 192 MB of split partials
-    // forward split-K partials of the GEMMs at full batch also live in d_partial
-    for (const Layer &L : m->layers)
-        if (L.op == kConv) {
-            const size_t M = NB * L.OH * L.OW;
-            t->partial_floats = std::max(t->partial_floats, (size_t)16 * std::min<size_t>(M, 4096) * L.OC);
-        }
+    t->partial_floats = trainer_partial_floats(m->layers, max_batch);
     hipError_t e = hipMalloc((void **)&t->d_arena, std::max<size_t>(arena, 1) * sizeof(float));
     auto alloc = [&](float **p, size_t n) {
         if (e == hipSuccess) e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(float));
@@ -893,46 +853,30 @@ extern "C" int smh_cnn_trainer_dropout_info(const smh_cnn_trainer *t, int i, siz
     return smh::set_error(SMH_E_INVALID, "smh_cnn_trainer_dropout_info: index %d out of range", i);
 }
 
-extern "C" int smh_cnn_train_step_f32(smh_cnn_trainer *t, const float *d_x, const float *d_y, int N, const float *d_drop,
-                                      const float *d_drop_heads, const float *h_loss_weights, float *d_losses, void *stream) {
-    SMH_REQUIRE(t && d_x && d_y && d_losses, "smh_cnn_train_step_f32: null argument");
-    SMH_REQUIRE(N >= 2 && N <= t->max_batch, "smh_cnn_train_step_f32: batch %d outside [2, %d]", N, t->max_batch);
+namespace {
+
+// Forward in training mode: every layer's output stays in the arena for the backward; *feat = the (N, feat_dim) features.
+// masks[l] = layer l's (N, dim) block of d_drop, in graph order.
+int train_forward(smh_cnn_trainer *t, const float *d_x, int N, const float *d_drop, std::vector<const float *> &masks, hipStream_t st,
+                  const float **feat) {
     smh_cnn *m = t->m;
-    hipStream_t st = (hipStream_t)stream;
     const float *F = m->d_flat;
     const int nl = (int)m->layers.size();
     int rc;
-    // ---------------- forward, training mode ----------------
     const float *src = d_x;
-    size_t drop_base = 0;  // masks: per dropout layer one (N, dim) block, in graph order
-    std::vector<const float *> masks(nl, nullptr);
+    size_t drop_base = 0;
     for (int l = 0; l < nl; ++l) {
         const Layer &L = m->layers[l];
         LayerState &S = t->ls[l];
         S.in = src;
         if (L.op == kConv) {
-            ConvArgs a{};
+            const bool bn_layer = L.t_bn >= 0;
+            ConvArgs a = conv_args(m, L, N);
             a.x = src, a.w = F + m->tensors[L.t_kernel].off;
             a.es = t->d_ones, a.eb = L.t_bias >= 0 ? F + m->tensors[L.t_bias].off : t->d_zeros;
-            const bool bn_layer = L.t_bn >= 0;
-            float *gemm_out = bn_layer ? S.z : S.a;  // without a BatchNorm the activation rides in the GEMM epilogue
-            a.y = gemm_out, a.partial = t->d_partial, a.lut = m->d_lut + L.lut_off;
-            a.H = L.H, a.W = L.W, a.Cin = L.C, a.OH = L.OH, a.OW = L.OW, a.Cout = L.OC, a.K = L.K;
-            a.M = N * L.OH * L.OW;
-            a.sh = L.sh, a.sw = L.sw, a.pt = L.pt, a.pl = L.pl, a.act = bn_layer ? kNone : L.act;
-            a.ksteps = L.Kp / BK;
-            a.vec4 = (L.C % 4 == 0) ? 1 : 0;
-            const int bn = L.OC <= 64 ? 64 : 128;
-            const int mt = (a.M + BM - 1) / BM, nt = (L.OC + bn - 1) / bn;
-            a.ksplit = choose_split(mt, nt, a.ksteps);
-            while (a.ksplit > 1 && (size_t)a.ksplit * a.M * L.OC > t->partial_floats) --a.ksplit;
-            a.ksteps_per = (a.ksteps + a.ksplit - 1) / a.ksplit;
-            launch_gemm<0>(a, a.M, bn, st);
-            if (a.ksplit > 1) {
-                const size_t MN = (size_t)a.M * L.OC;
-                hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(nblk(MN)), dim3(256), 0, st, (const float *)t->d_partial, a.ksplit,
-                                   MN, L.OC, a.es, a.eb, a.act, gemm_out);
-            }
+            a.y = bn_layer ? S.z : S.a, a.act = bn_layer ? kNone : L.act;  // without a BatchNorm the activation rides in the GEMM epilogue
+            a.partial = t->d_partial;
+            launch_conv_gemm<0>(a, plan_train_forward(L, N, t->partial_floats), st);
             if (!bn_layer) {
                 src = S.a;
                 continue;
@@ -968,10 +912,15 @@ extern "C" int smh_cnn_train_step_f32(smh_cnn_trainer *t, const float *d_x, cons
         }
         src = S.a;
     }
-    rc = smh::launch_status("smh_cnn training forward");
-    if (rc) return rc;
-    // ---------------- heads: pre-activations, losses, d loss / d pre ----------------
-    const float *feat = src;
+    *feat = src;
+    return smh::launch_status("smh_cnn training forward");
+}
+
+// Heads: pre-activations, losses, d loss / d pre, the l2 terms, the heads' weight gradients; dfeat = d loss / d feat.
+int train_heads(smh_cnn_trainer *t, const float *feat, const float *d_y, int N, const float *d_drop_heads, const float *h_loss_weights,
+                float *d_losses, float *dfeat, hipStream_t st) {
+    smh_cnn *m = t->m;
+    const float *F = m->d_flat;
     HeadPtrs hp{};
     hp.c3k = m->tensors[m->t_c3].off, hp.c3b = m->tensors[m->t_c3 + 1].off;
     hp.D = m->feat_dim, hp.n_classes = m->cfg.n_classes, hp.n_heads = m->n_heads;
@@ -990,7 +939,7 @@ extern "C" int smh_cnn_train_step_f32(smh_cnn_trainer *t, const float *d_x, cons
     }
     ha.goff_c3b = hp.c3b;
     hipLaunchKernelGGL(heads_pre_kernel, dim3(N), dim3(256), 0, st, feat, F, hp, t->d_pre);
-    rc = smh::launch_status("heads_pre_kernel");
+    int rc = smh::launch_status("heads_pre_kernel");
     if (rc) return rc;
     if (m->n_heads == 0)  // single-task: softmax, the two-output bce or the categorical loss, accuracy, d loss / d logits
         rc = smh_tcn::launch_single_head_train(ha, t->d_pre, d_y, t->d_dpre, t->d_grad, d_losses, st);
@@ -1003,137 +952,146 @@ extern "C" int smh_cnn_train_step_f32(smh_cnn_trainer *t, const float *d_x, cons
     hipLaunchKernelGGL(l2_finish_kernel, dim3(1), dim3(1024), 0, st, (const double *)t->d_l2part, t->nseg, d_losses + m->n_heads + 3);
     hipLaunchKernelGGL(heads_dw_kernel, dim3(nblk((size_t)m->feat_dim * kHidden), 1 + m->n_heads), dim3(256), 0, st, feat,
                        (const float *)t->d_dpre, hp, N, t->d_grad);
-    int cur = 0;
     hipLaunchKernelGGL(heads_dfeat_kernel, dim3(nblk((size_t)N * m->feat_dim)), dim3(256), 0, st, (const float *)t->d_dpre, F, hp, N,
-                       t->d_g[cur]);
-    rc = smh::launch_status("smh_cnn heads backward");
-    if (rc) return rc;
-    // ---------------- backward through the layer list ----------------
-    for (int l = nl - 1; l >= 0; --l) {
-        const Layer &L = m->layers[l];
-        LayerState &S = t->ls[l];
-        float *G = t->d_g[cur], *Gn = t->d_g[cur ^ 1];
-        if (L.op == kPool) {
-            const size_t total = (size_t)N * L.H * L.W * L.C;
-            if (L.sh == L.kh && L.sw == L.kw && !getenv("SMH_CNN_POOL_GATHER")) {
-                if (L.OH * L.kh - L.pt < L.H || L.OW * L.kw - L.pl < L.W)  // rows / columns no window reaches
-                    SMH_CHECK_HIP(hipMemsetAsync(Gn, 0, total * sizeof(float), st));
-                const size_t nwin = (size_t)N * L.OH * L.OW * L.C;
-                hipLaunchKernelGGL(maxpool_bwd_tiles_kernel, dim3(nblk(nwin)), dim3(256), 0, st, S.in, (const float *)G, L.H, L.W, L.C,
-                                   L.OH, L.OW, L.kh, L.kw, L.pt, L.pl, nwin, Gn);
-            } else {
-                hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblk(total)), dim3(256), 0, st, S.in, (const float *)S.a, (const float *)G,
-                                   L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, total, Gn);
-            }
-            cur ^= 1;
-            continue;
+                       dfeat);
+    return smh::launch_status("smh_cnn heads backward");
+}
+
+// The backward of one layer: G = d loss / d output, Gn receives d loss / d input.
+int backward_pool(const Layer &L, const LayerState &S, int N, const CnnSwitches &sw, const float *G, float *Gn, hipStream_t st) {
+    const size_t total = (size_t)N * L.H * L.W * L.C;
+    if (L.sh == L.kh && L.sw == L.kw && !sw.pool_gather) {
+        if (L.OH * L.kh - L.pt < L.H || L.OW * L.kw - L.pl < L.W)  // rows / columns no window reaches
+            SMH_CHECK_HIP(hipMemsetAsync(Gn, 0, total * sizeof(float), st));
+        const size_t nwin = (size_t)N * L.OH * L.OW * L.C;
+        hipLaunchKernelGGL(maxpool_bwd_tiles_kernel, dim3(nblk(nwin)), dim3(256), 0, st, S.in, G, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw,
+                           L.pt, L.pl, nwin, Gn);
+    } else {
+        hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblk(total)), dim3(256), 0, st, S.in, (const float *)S.a, G, L.H, L.W, L.C, L.OH,
+                           L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, total, Gn);
+    }
+    return SMH_OK;
+}
+
+void backward_lrn(smh_cnn_trainer *t, const Layer &L, const LayerState &S, int N, float *G, float *Gn, hipStream_t st) {
+    const size_t total = (size_t)N * L.H * L.W * L.C;
+    hipLaunchKernelGGL(lrn_bwd1_kernel, dim3(nblk(total)), dim3(256), 0, st, S.in, (const float *)S.a, L.C, 5, 1e-4f, 0.75f, total, G,
+                       t->d_tmp);
+    hipLaunchKernelGGL(lrn_bwd2_kernel, dim3(nblk(total)), dim3(256), 0, st, S.in, (const float *)G, (const float *)t->d_tmp, L.C, 5,
+                       1e-4f, 0.75f, total, Gn);
+}
+
+// Conv2D / Dense: the BatchNorm (or bias + ReLU) gradient turns G into dz in place, then the weight gradient, then (behind the first
+// layer) the data gradient into Gn.
+int backward_conv(smh_cnn_trainer *t, int l, int N, const CnnSwitches &sw, const float *mask, float *G, float *Gn, hipStream_t st) {
+    smh_cnn *m = t->m;
+    const Layer &L = m->layers[l];
+    const LayerState &S = t->ls[l];
+    const float *F = m->d_flat;
+    const int M = N * L.OH * L.OW;
+    const size_t total = (size_t)M * L.OC;
+    float *gr = t->d_grad;
+    int rc;
+    if (L.t_bn < 0) {  // bias + optional ReLU in the GEMM epilogue: gate, then the bias gradient is a plain column sum
+        if (L.act == kRelu) hipLaunchKernelGGL(relu_bwd_kernel, dim3(nblk(total)), dim3(256), 0, st, (const float *)S.a, total, G);
+        if (L.t_bias >= 0) {
+            RedArgs rb{};
+            rb.z = G, rb.M = (size_t)M, rb.C = L.OC;
+            rc = col_reduce<0>(t, rb, 1, 1.0f, 0, 1.f, gr + m->tensors[L.t_bias].off, nullptr, st);
+            if (rc) return rc;
         }
-        if (L.op == kMelCl) {  // first layer: weight gradients only; G holds dA with 4 floats per pixel (3 channels + pad)
-            hipLaunchKernelGGL(melcl_bwd_kernel, dim3(L.OH), dim3(256), 0, st, S.in, (const float *)S.a, (const float *)G,
-                               (const MelCl *)m->d_mel, N, L.H, L.W, L.OH, L.kw, 4, t->d_grad);
-            continue;
-        }
-        if (L.op == kLrnRelu) {
-            const size_t total = (size_t)N * L.H * L.W * L.C;
-            hipLaunchKernelGGL(lrn_bwd1_kernel, dim3(nblk(total)), dim3(256), 0, st, S.in, (const float *)S.a, L.C, 5, 1e-4f, 0.75f,
-                               total, G, t->d_tmp);
-            hipLaunchKernelGGL(lrn_bwd2_kernel, dim3(nblk(total)), dim3(256), 0, st, S.in, (const float *)G, (const float *)t->d_tmp,
-                               L.C, 5, 1e-4f, 0.75f, total, Gn);
-            cur ^= 1;
-            continue;
-        }
-        const int M = N * L.OH * L.OW;
-        const size_t total = (size_t)M * L.OC;
-        float *gr = t->d_grad;
-        if (L.t_bn < 0) {  // bias + optional ReLU in the GEMM epilogue: gate, then the bias gradient is a plain column sum
-            if (L.act == kRelu) hipLaunchKernelGGL(relu_bwd_kernel, dim3(nblk(total)), dim3(256), 0, st, (const float *)S.a, total, G);
-            if (L.t_bias >= 0) {
-                RedArgs rb{};
-                rb.z = G, rb.M = (size_t)M, rb.C = L.OC;
-                rc = col_reduce<0>(t, rb, 1, 1.0f, 0, 1.f, gr + m->tensors[L.t_bias].off, nullptr, st);
-                if (rc) return rc;
-            }
-        } else {
+    } else {
         const float *g = F + m->tensors[L.t_bn].off;
         // BN backward: dbeta = sum g, dgamma = sum g * xhat, then dz in place
         RedArgs r{};
-        r.z = S.z, r.dA = G, r.mask = masks[l], r.mean = S.mean, r.rstd = S.rstd, r.gamma = g, r.beta = g + L.OC;
+        r.z = S.z, r.dA = G, r.mask = mask, r.mean = S.mean, r.rstd = S.rstd, r.gamma = g, r.beta = g + L.OC;
         r.M = (size_t)M, r.C = L.OC;
         rc = col_reduce<2>(t, r, 2, 1.0f, 0, 1.f, S.s12, S.s12 + L.OC, st);
         if (rc) return rc;
         SMH_CHECK_HIP(hipMemcpyAsync(gr + m->tensors[L.t_bn].off + L.OC, S.s12, L.OC * sizeof(float), hipMemcpyDeviceToDevice, st));  // beta
         SMH_CHECK_HIP(hipMemcpyAsync(gr + m->tensors[L.t_bn].off, S.s12 + L.OC, L.OC * sizeof(float), hipMemcpyDeviceToDevice, st));  // gamma
-        hipLaunchKernelGGL(bn_bwd_kernel, dim3(nblk(total / 4)), dim3(256), 0, st, (const float *)S.z, masks[l], total / 4, L.OC,
+        hipLaunchKernelGGL(bn_bwd_kernel, dim3(nblk(total / 4)), dim3(256), 0, st, (const float *)S.z, mask, total / 4, L.OC,
                            1.0f / (float)M, (const float *)S.mean, (const float *)S.rstd, g, g + L.OC, (const float *)S.s12, G);
         // d bias = column sums of dz: behind a BatchNorm that is exactly zero (sum_m dz = gamma*rstd*(s1 - s1 - s2*sum xhat),
         // sum xhat = 0); Keras accumulates rounding noise there, this step leaves the zero the memset wrote
         if (L.t_bias >= 0) SMH_CHECK_HIP(hipMemsetAsync(gr + m->tensors[L.t_bias].off, 0, L.OC * sizeof(float), st));
+    }
+    const WgradPlan wp = plan_wgrad(L, N, t->partial_floats, sw);
+    if (wp.smallk) {  // shallow first layer: VALU kernel
+        const size_t outf = (size_t)L.K * L.OC;
+        hipLaunchKernelGGL(wgrad_smallk_kernel, dim3(wp.nb, (L.OC + 63) / 64), dim3(256), 0, st, S.in, (const float *)G,
+                           (const int2 *)(m->d_lut + L.lut_off), (const int2 *)S.rowinfo, L.H, L.W, L.K, L.OC, M, wp.rows_per_block,
+                           t->d_partial);
+        hipLaunchKernelGGL(partial_sum_kernel, dim3(nblk(outf)), dim3(256), 0, st, (const float *)t->d_partial, wp.nb, outf,
+                           gr + m->tensors[L.t_kernel].off);
+    } else {  // wgrad on the matrix cores
+        ConvArgs a = conv_args(m, L, N);
+        a.x = S.in, a.w = G, a.rowinfo = S.rowinfo;
+        a.y = gr + m->tensors[L.t_kernel].off, a.partial = t->d_partial;
+        launch_conv_gemm<1>(a, wp.gemm, st);
+    }
+    if (l > 0) {  // dgrad: dZ is the image, mirrored taps, kernel transposed per tap
+        const int ldc = dgrad_cols(L);  // columns of the data-gradient GEMM: Cin padded to a multiple of 4
+        const size_t wn = (size_t)L.kh * L.kw * L.OC * ldc;
+        hipLaunchKernelGGL(transpose_taps_kernel, dim3(nblk(wn)), dim3(256), 0, st, F + m->tensors[L.t_kernel].off, L.C, L.OC, ldc,
+                           wn, t->d_wt);
+        const float *dzimg = G;
+        if (L.sh > 1 || L.sw > 1) {  // strided layer: zero-stuff dz, then it is a stride-1 data gradient
+            const size_t sn = (size_t)N * S.SH * S.SW * L.OC;
+            SMH_CHECK_HIP(hipMemsetAsync(t->d_tmp, 0, sn * sizeof(float), st));
+            hipLaunchKernelGGL(stuff_kernel, dim3(nblk(total)), dim3(256), 0, st, (const float *)G, L.OH, L.OW, L.OC, L.sh, L.sw,
+                               S.SH, S.SW, total, t->d_tmp);
+            dzimg = t->d_tmp;
         }
-        if (L.K <= kSmallK && !getenv("SMH_CNN_WGRAD_MFMA")) {  // shallow first layer: VALU kernel
-            const size_t outf = (size_t)L.K * L.OC;
-            int nb = std::max(1, std::min(1024, M / 512));
-            while (nb > 1 && (size_t)nb * outf > t->partial_floats) --nb;
-            const int rpb = ((M + nb - 1) / nb + 63) / 64 * 64;
-            nb = (M + rpb - 1) / rpb;
-            hipLaunchKernelGGL(wgrad_smallk_kernel, dim3(nb, (L.OC + 63) / 64), dim3(256), 0, st, S.in, (const float *)G,
-                               (const int2 *)(m->d_lut + L.lut_off), (const int2 *)S.rowinfo, L.H, L.W, L.K, L.OC, M, rpb, t->d_partial);
-            hipLaunchKernelGGL(partial_sum_kernel, dim3(nblk(outf)), dim3(256), 0, st, (const float *)t->d_partial, nb, outf,
-                               gr + m->tensors[L.t_kernel].off);
-        } else {  // wgrad on the matrix cores
-            ConvArgs a{};
-            a.x = S.in, a.w = G, a.lut = m->d_lut + L.lut_off, a.rowinfo = S.rowinfo;
-            a.H = L.H, a.W = L.W, a.Cin = L.C, a.OH = L.OH, a.OW = L.OW, a.Cout = L.OC, a.K = L.K, a.M = M;
-            a.ksteps = (M + BK - 1) / BK;
-            const int bn = L.OC <= 64 ? 64 : 128;
-            const int mt = (L.K + BM - 1) / BM, nt = (L.OC + bn - 1) / bn;
-            const size_t outf = (size_t)L.K * L.OC;
-            a.ksplit = wgrad_split(mt * nt, a.ksteps, outf, t->partial_floats);
-            if (const char *e = getenv("SMH_CNN_WSPLIT")) a.ksplit = std::max(1, std::min(atoi(e), a.ksteps));
-            while (a.ksplit > 1 && (size_t)a.ksplit * outf > t->partial_floats) --a.ksplit;  // a forced split too
-            a.ksteps_per = (a.ksteps + a.ksplit - 1) / a.ksplit;
-            a.ksplit = (a.ksteps + a.ksteps_per - 1) / a.ksteps_per;  // no empty slices
-            a.y = gr + m->tensors[L.t_kernel].off, a.partial = t->d_partial;
-            launch_gemm<1>(a, L.K, bn, st);
-            if (a.ksplit > 1)
-                hipLaunchKernelGGL(partial_sum_kernel, dim3(nblk(outf)), dim3(256), 0, st, (const float *)t->d_partial, a.ksplit, outf,
-                                   a.y);
-        }
-        if (l > 0) {  // dgrad: dZ is the image, mirrored taps, kernel transposed per tap
-            const int ldc = (L.C + 3) & ~3;  // columns of the data-gradient GEMM: Cin padded to a multiple of 4 (Jang conv1: 3 -> 4)
-            const size_t wn = (size_t)L.kh * L.kw * L.OC * ldc;
-            hipLaunchKernelGGL(transpose_taps_kernel, dim3(nblk(wn)), dim3(256), 0, st, F + m->tensors[L.t_kernel].off, L.C, L.OC, ldc,
-                               wn, t->d_wt);
-            const float *dzimg = G;
-            if (L.sh > 1 || L.sw > 1) {  // strided layer: zero-stuff dz, then it is a stride-1 data gradient
-                const size_t sn = (size_t)N * S.SH * S.SW * L.OC;
-                SMH_CHECK_HIP(hipMemsetAsync(t->d_tmp, 0, sn * sizeof(float), st));
-                hipLaunchKernelGGL(stuff_kernel, dim3(nblk(total)), dim3(256), 0, st, (const float *)G, L.OH, L.OW, L.OC, L.sh, L.sw,
-                                   S.SH, S.SW, total, t->d_tmp);
-                dzimg = t->d_tmp;
-            }
-            ConvArgs a{};
-            a.x = dzimg, a.w = t->d_wt, a.es = t->d_ones, a.eb = t->d_zeros, a.y = Gn, a.partial = t->d_partial, a.lut = S.dlut;
-            a.H = S.SH, a.W = S.SW, a.Cin = L.OC, a.OH = L.H, a.OW = L.W, a.Cout = ldc, a.K = S.dK;
-            a.M = N * L.H * L.W;
-            a.sh = a.sw = 1, a.pt = -L.pt, a.pl = -L.pl, a.act = kNone;
-            a.ksteps = S.dKp / BK;
-            a.vec4 = (L.OC % 4 == 0) ? 1 : 0;
-            const int bn = ldc <= 64 ? 64 : 128;
-            const int mt = (a.M + BM - 1) / BM, nt = (ldc + bn - 1) / bn;
-            a.ksplit = choose_split(mt, nt, a.ksteps);
-            if (const char *e = getenv("SMH_CNN_DSPLIT")) a.ksplit = std::max(1, std::min(atoi(e), a.ksteps));
-            while (a.ksplit > 1 && (size_t)a.ksplit * a.M * ldc > t->partial_floats) --a.ksplit;
-            a.ksteps_per = (a.ksteps + a.ksplit - 1) / a.ksplit;
-            launch_gemm<0>(a, a.M, bn, st);
-            if (a.ksplit > 1) {
-                const size_t MN = (size_t)a.M * ldc;
-                hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(nblk(MN)), dim3(256), 0, st, (const float *)t->d_partial, a.ksplit,
-                                   MN, ldc, a.es, a.eb, (int)kNone, Gn);
-            }
+        ConvArgs a = conv_args(m, L, N);
+        a.x = dzimg, a.w = t->d_wt, a.es = t->d_ones, a.eb = t->d_zeros, a.y = Gn, a.partial = t->d_partial, a.act = kNone;
+        // the swapped geometry: a stride-1 convolution of the (SH x SW x OC) image dZ into the layer's (H x W x ldc) input
+        a.lut = S.dlut;
+        a.H = S.SH, a.W = S.SW, a.Cin = L.OC, a.OH = L.H, a.OW = L.W, a.Cout = ldc, a.K = S.dK;
+        a.M = N * L.H * L.W;
+        a.sh = a.sw = 1, a.pt = -L.pt, a.pl = -L.pl;
+        a.vec4 = (L.OC % 4 == 0) ? 1 : 0;
+        launch_conv_gemm<0>(a, plan_dgrad(L, N, t->partial_floats, sw), st);
+    }
+    return smh::launch_status("smh_cnn backward");
+}
+
+}  // namespace
+
+extern "C" int smh_cnn_train_step_f32(smh_cnn_trainer *t, const float *d_x, const float *d_y, int N, const float *d_drop,
+                                      const float *d_drop_heads, const float *h_loss_weights, float *d_losses, void *stream) {
+    SMH_REQUIRE(t && d_x && d_y && d_losses, "smh_cnn_train_step_f32: null argument");
+    SMH_REQUIRE(N >= 2 && N <= t->max_batch, "smh_cnn_train_step_f32: batch %d outside [2, %d]", N, t->max_batch);
+    const CnnSwitches sw = read_cnn_switches();
+    smh_cnn *m = t->m;
+    hipStream_t st = (hipStream_t)stream;
+    const int nl = (int)m->layers.size();
+    std::vector<const float *> masks(nl, nullptr);
+    const float *feat = nullptr;
+    int rc = train_forward(t, d_x, N, d_drop, masks, st, &feat);
+    if (rc) return rc;
+    int cur = 0;  // t->d_g[cur] holds the gradient that flows down
+    rc = train_heads(t, feat, d_y, N, d_drop_heads, h_loss_weights, d_losses, t->d_g[cur], st);
+    if (rc) return rc;
+    for (int l = nl - 1; l >= 0; --l) {
+        const Layer &L = m->layers[l];
+        const LayerState &S = t->ls[l];
+        float *G = t->d_g[cur], *Gn = t->d_g[cur ^ 1];
+        if (L.op == kPool) {
+            rc = backward_pool(L, S, N, sw, G, Gn, st);
+            if (rc) return rc;
             cur ^= 1;
+        } else if (L.op == kLrnRelu) {
+            backward_lrn(t, L, S, N, G, Gn, st);
+            cur ^= 1;
+        } else if (L.op == kMelCl) {  // first layer: weight gradients only; G holds dA with 4 floats per pixel (3 channels + pad)
+            hipLaunchKernelGGL(melcl_bwd_kernel, dim3(L.OH), dim3(256), 0, st, S.in, (const float *)S.a, (const float *)G,
+                               (const MelCl *)m->d_mel, N, L.H, L.W, L.OH, L.kw, 4, t->d_grad);
+        } else {
+            rc = backward_conv(t, l, N, sw, masks[l], G, Gn, st);
+            if (rc) return rc;
+            if (l > 0) cur ^= 1;
         }
-        rc = smh::launch_status("smh_cnn backward");
-        if (rc) return rc;
     }
     return SMH_OK;
 }

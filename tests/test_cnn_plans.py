@@ -146,3 +146,28 @@ def test_forced_plans_reach_their_branch(case):
             assert P.wgrad_plan(layers[0], N, cap)["kind"] == "smallk" and p["ksplit"] > 1 and p["partial"] <= cap
         else:
             assert branch == "pool-gather" and var == "SMH_CNN_POOL_GATHER"
+
+
+def test_hand_computed_single_task_plans():
+    # Jang single-task 257 x 12: one mel layer of 64 rows, then 64 x 12 -> 32 x 6 -> 16 x 3 -> 8 x 1 through valid pools; no Dense
+    layers = P.graph("Jang", 257, 12, single=True)
+    assert [(L["name"], L["index"], L["OH"], L["OW"], L["K"]) for L in layers] == \
+        [("conv1", 1, 64, 12, 27), ("conv2", 3, 32, 6, 288), ("conv3", 5, 16, 3, 576)]
+    assert P.graph("Doukhan", 21, 68, single=True) == P.graph("Doukhan", 21, 68)
+    # Doukhan 64 x 80 conv4: 11 x 15 pixels, K = 9 * 128, 2 column tiles.  One image alone: 2 x 2 tiles -> 72 / 8 = 9 slices;
+    # planned as a full pass of 64 images: 83 x 2 tiles -> 512 / 166 -> 4 slices, on the rows of the one image
+    c4 = P.layer("Doukhan", 64, 80, "conv4")
+    assert (c4["OH"], c4["OW"], c4["K"]) == (11, 15, 1152) and P.plan_images(1, single=True) == 64
+    assert P.forward_plan(c4, 1) == dict(M=165, ksteps=72, ksplit=9, ksteps_per=8, empty=0)
+    assert P.forward_plan(c4, 1, single=True) == dict(M=165, ksteps=72, ksplit=4, ksteps_per=18, empty=0)
+    assert P.forward_plan(c4, 64, single=True) == P.forward_plan(c4, 64)
+    assert P.tiles(165, 256) == (128, 2, 2) and P.tiles(129, 64) == (64, 2, 1)
+    # Doukhan 30 x 68 fc1 at N = 8: 3 x 1 x 256 = 768 features, 48 k-steps -> 6 slices of 8 x 512 floats; a buffer of 10 000 holds 2
+    fc1 = P.layer("Doukhan", 30, 68, "fc1")
+    assert P.train_forward_plan(fc1, 8, 48 << 20) == dict(M=8, ksteps=48, ksplit=6, ksteps_per=8, partial=24576)
+    assert P.train_forward_plan(fc1, 8, 10000) == dict(M=8, ksteps=48, ksplit=2, ksteps_per=24, partial=8192)
+    # the workspace of that model at N = 5: activations of conv1 (27 x 64 x 64 floats per image); the largest partials are conv3's
+    # (9 x 28 pixels x 5 = 1260 rows in 10 tiles, 72 k-steps -> 9 slices of 1260 x 128), ahead of conv2's 4 x 1650 x 128
+    layers = P.graph("Doukhan", 30, 68)
+    assert P.forward_partial_floats(layers, 5) == 9 * 1260 * 128
+    assert P.workspace_bytes(layers, 30, 68, 5) == 2 * 4 * 27 * 64 * 64 * 5 + 4 * 9 * 1260 * 128
