@@ -305,6 +305,30 @@ int smh_scale_data_f64(const double *d_FV, int F, int T, const double *d_mean, c
                        void *stream);
 int smh_data_statistics_f64(const double *d_FV, int N, int F, int T, int stat, int axis, double *d_out, void *stream);
 
+/* ---- frame-level scaling on the device path (PARAMS['frame_level_scaling']): the moments get_data_stats needs
+ * (lib/preprocessing.py:461-586) and scale_data + extract_patches in one kernel.  Both work on B featuregrams that are already
+ * on the device: h_fv[b] is the DEVICE pointer of featuregram b, (rows, h_T[b]) float32, dense (rows of exactly h_T[b] floats),
+ * h_T[b] >= 1; h_fv and h_T themselves are host arrays.  The featuregrams may be separate allocations or views of one buffer.
+ * The per-clip table is uploaded through a staging slot of ctx (any front-end context; its configuration is not read), so the
+ * calls cannot be captured in a graph; more clips than one slot holds are split into several launches.
+ *
+ * smh_row_moments_f64: d_moments (B, rows, 2) float64 = {sum(x), M2 = sum((x - sum(x) / T)^2)} of every (clip, row), d_nonfinite
+ * (B, rows) int32 = how many of the row's values are NaN or +-inf (its moments are then not finite).  One f64 partial sum per
+ * lane over the frames lane, lane + 64, ... and a fixed xor tree over the 64 lanes: the summation order depends on T alone, so a
+ * clip's moments are bit-identical alone and in any batch.  Around any mean mu, sum((x - mu)^2) = M2 + T (sum(x) / T - mu)^2.
+ *
+ * smh_scaled_patches_f32: every patch element is (float)(((double)x - d_mean[r]) / (d_stdev[r] + 1e-10)) -- scale_data's float64
+ * arithmetic (tools.pyx:157-164) rounded once to float32 -- on the grid of smh_tiled_frames / smh_num_patches / smh_patch_start
+ * (T < W: tiled-if-short).  d_mean, d_stdev: (rows) float64 on the device.  Clip b's patches follow those of the clips before it:
+ * d_patches is (sum_b nP_b, W, rows) with patch_layout 1 (time-major) or (sum_b nP_b, rows, W) with 0 (image), where nP_b =
+ * smh_num_patches(smh_tiled_frames(h_T[b], W), W, shift); smh_scaled_patches_count returns the sum (< 0 on error) and, if
+ * h_patch_off is not null, the B + 1 running sums.                                                                       */
+int smh_row_moments_f64(const smh_ctx *ctx, const float *const *h_fv, const int *h_T, int B, int rows, double *d_moments,
+                        int32_t *d_nonfinite, void *stream);
+long long smh_scaled_patches_count(const int *h_T, int B, int W, int shift, long long *h_patch_off);
+int smh_scaled_patches_f32(const smh_ctx *ctx, const float *const *h_fv, const int *h_T, int B, int rows, const double *d_mean,
+                           const double *d_stdev, int W, int shift, int patch_layout, float *d_patches, void *stream);
+
 /* ---- a10-a12: B3_MTL = get_Lemaire_MTL_model (lib/proposed_architectures.py:85-170, 25-80) ---- */
 typedef struct smh_model_cfg {
     int32_t n_feat;     /* N_MELS argument = input_shape[1]: 240                       */

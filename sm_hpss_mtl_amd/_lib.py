@@ -106,6 +106,9 @@ SIGNATURES = {
     "smh_cnn_trainer_apply_f32": (_i, [_vp, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
     "smh_scale_data_f64": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "smh_data_statistics_f64": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "smh_row_moments_f64": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_int), _i, _i, _vp, _vp, _vp]),
+    "smh_scaled_patches_count": (C.c_longlong, [C.POINTER(C.c_int), _i, _i, _i, C.POINTER(C.c_longlong)]),
+    "smh_scaled_patches_f32": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_int), _i, _i, _vp, _vp, _i, _i, _i, _fp, _vp]),
     "smh_model_create": (_i, [C.POINTER(ModelCfg), C.POINTER(_vp)]),
     "smh_model_create_heads": (_i, [C.POINTER(ModelCfg), _i, C.POINTER(_vp)]),
     "smh_model_destroy": (None, [_vp]),

@@ -468,3 +468,50 @@ class Frontend:
             raise ValueError("FV should be of the shape (nFeatures, nFrames)")
         x = self.standardize_rows(fv)  # per row over the frames: the per-half scaler is row-wise, so halves need no split
         return self.extract_patches(x[None], W, shift, time_major=layout == "time_major")
+
+    # ---- frame-level scaling (PARAMS['frame_level_scaling']): featuregrams that are already on the device ----
+    @staticmethod
+    def _fv_table(fvs, who):
+        """(kept tensors, device-pointer array, frame-count array, rows) of a list of (rows, T_b) float32 device featuregrams."""
+        if len(fvs) == 0:
+            raise ValueError("%s: no featuregrams" % who)
+        keep = [_f32c(t, "%s: fvs[%d]" % (who, i)) for i, t in enumerate(fvs)]
+        rows = int(keep[0].shape[0]) if keep[0].dim() == 2 else -1
+        for i, t in enumerate(keep):
+            if t.dim() != 2 or int(t.shape[0]) != rows or int(t.shape[1]) < 1:
+                raise ValueError("%s: fvs[%d] has shape %s; every featuregram must be (rows = %d, T >= 1)" % (who, i, tuple(t.shape), rows))
+        B = len(keep)
+        return keep, (C.c_void_p * B)(*[t.data_ptr() for t in keep]), (C.c_int * B)(*[int(t.shape[1]) for t in keep]), rows
+
+    def row_moments(self, fvs):
+        """`smh_row_moments_f64`: fvs, a list of (rows, T_b) float32 device featuregrams (the HPSS pair's 2 * rows or the plain rows:
+        whatever the tensors have) -> (sum (B, rows) float64, m2 (B, rows) float64 = sum((x - sum / T_b)^2), nonfinite (B, rows) int32).
+        A clip's values are bit for bit the same alone and in any batch."""
+        keep, h_fv, h_T, rows = self._fv_table(fvs, "row_moments")
+        B, dev = len(keep), keep[0].device
+        mom = torch.empty((B, rows, 2), dtype=torch.float64, device=dev)
+        bad = torch.empty((B, rows), dtype=torch.int32, device=dev)
+        _lib.check(self.lib.smh_row_moments_f64(self._h, h_fv, h_T, B, rows, _ptr(mom), _ptr(bad), _stream()), "smh_row_moments_f64")
+        return mom[..., 0], mom[..., 1], bad
+
+    def scaled_patches(self, fvs, mean, stdev, W, shift, layout="time_major"):
+        """`smh_scaled_patches_f32`: scale_data + extract_patches of every featuregram in ONE launch.  fvs as for `row_moments`;
+        mean, stdev: one value per featuregram row (arrays or tensors; read as float64).  Every element is
+        float32((float64(x) - mean[r]) / (stdev[r] + 1e-10)).  Returns a list of per-clip views of one patch buffer, shaped as
+        `run_ragged`'s: (nP_b, W, rows) time-major, (nP_b, rows, W) with layout="image"."""
+        lay = _layout(layout)
+        keep, h_fv, h_T, rows = self._fv_table(fvs, "scaled_patches")
+        B, dev = len(keep), keep[0].device
+        stats = []
+        for name, v in (("mean", mean), ("stdev", stdev)):
+            t = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v), dtype=np.float64))
+            t = t.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+            if t.numel() != rows:
+                raise ValueError("scaled_patches: %s has %d values, the featuregrams have %d rows" % (name, t.numel(), rows))
+            stats.append(t)
+        p_off = (C.c_longlong * (B + 1))()
+        total = _lib.check(self.lib.smh_scaled_patches_count(h_T, B, int(W), int(shift), p_off), "smh_scaled_patches_count")
+        patches = torch.empty(_patch_shape(max(int(total), 1), int(W), rows, layout), dtype=torch.float32, device=dev)
+        _lib.check(self.lib.smh_scaled_patches_f32(self._h, h_fv, h_T, B, rows, _ptr(stats[0]), _ptr(stats[1]), int(W), int(shift), lay,
+                                                   _ptr(patches), _stream()), "smh_scaled_patches_f32")
+        return [patches[int(p_off[b]):int(p_off[b + 1])] for b in range(B)]

@@ -22,6 +22,12 @@ batch, row for row.  Ranks whose numpy state has drifted apart would silently tr
 state is compared across the ranks on the first batch and every `check_every` batches (one tiny all-reduce) and a mismatch
 raises.
 
+Frame-level scaling (`PARAMS['frame_level_scaling']`, Baseline_Results.py:91-93, 343-346, 608-621): every file's featuregram is scaled
+with the training fold's row statistics PARAMS['mean_fold<k>'] / PARAMS['stdev_fold<k>'] (`data_stats_for_fold` computes or loads
+them) instead of the per-file StandardScaler.  Device path: the ragged pass writes featuregrams only and ONE `Frontend.scaled_patches`
+launch cuts the scaled patches of every file of the batch, cached ones included; per-file callables: the float64 scaling runs on the
+host between `featuregram_fn` and `patches_fn`.
+
 `featuregram_fn` / `patches_fn` are injection points for tests (and for a CPU oracle): per-file callables with the
 signatures of `preproc.get_featuregram` / `preproc.get_feature_patches`.  When they are given, files are processed one
 by one through them, exactly like the reference's loop.
@@ -174,16 +180,16 @@ def _cached_featuregram(path, fresh=None):
     return t
 
 
-def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
-    """specs: list of (classname, sp_path, mu_path, target_dB).  Loads / conditions / mixes the signals (the 'next' row in
-    front of the path: lib.preprocessing.load_and_preprocess_signal, mix_signals), then ONE ragged pass of the front end.
-    Returns a list of float32 device tensors in the layout PARAMS['Model'] reads: (nP_i, W, 2F) for a Lemaire_et_al variant;
-    (nP_i, 2F, W, 1) for any other -- the Conv2D models' images, get_feature_patches' np.expand_dims(patches, axis=3),
-    Proposed_Work_Results.py:483-484 (a view: no copy).  The feature names without an H / P pair have F in place of 2F."""
-    import torch
+def _device_featuregrams_for(PARAMS, specs, featName, n_fft, n_mels, W=None, shift=None, layout="time_major"):
+    """specs: list of (classname, sp_path, mu_path, target_dB).  Loads / conditions / mixes the signals of the files whose
+    featuregram the reference's .npy cache does not hold (the 'next' row in front of the path:
+    lib.preprocessing.load_and_preprocess_signal, mix_signals), then ONE ragged pass of the front end for them -- with W, its
+    standardised patches too.  PARAMS['save_features'] (default on) writes the .npy cache as get_featuregram(save_feat=True) does
+    and keeps the featuregram on the device for the epochs to come.  Returns (fe, fvs, patches): the front end, every file's
+    featuregram as a float32 device tensor (a cached file's from the device cache), and per file the front end's patches or None
+    (no W, or a cached file)."""
     from . import frontend as _fe
     from .lib import preprocessing as pp
-    layout = "time_major" if 'Lemaire_et_al' in PARAMS['Model'] else "image"
     clips = []
     for classname, sp, mu, db in specs:
         cache = pp.feature_cache_path(PARAMS['feature_opDir'], classname, sp, mu, db)
@@ -201,12 +207,14 @@ def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
         clips.append(("audio", np.ascontiguousarray(x, dtype=np.float32), cache))
     cfg = _fe.FrontendConfig.from_params(PARAMS, n_fft, n_mels, featName)
     fe = pp._frontend_for(cfg)
-    out = [None] * len(clips)
+    fvs, patches = [None] * len(clips), [None] * len(clips)
     audio_idx = [i for i, c in enumerate(clips) if c[0] == "audio"]
     if audio_idx:
         res = fe.run_ragged([clips[i][1] for i in audio_idx], W=W, shift=shift, layout=layout)
         for k, i in enumerate(audio_idx):
-            out[i] = res["patches"][k]
+            fvs[i] = res["fv"][k]
+            if W:
+                patches[i] = res["patches"][k]
             if PARAMS.get('save_features', True):  # get_featuregram(save_feat=True): the reference's .npy cache
                 os.makedirs(os.path.dirname(clips[i][2]), exist_ok=True)
                 tmp = "%s.%d.tmp.npy" % (clips[i][2], os.getpid())  # (two ranks may compute the same file: whole files only)
@@ -214,9 +222,83 @@ def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
                 os.replace(tmp, clips[i][2])
                 _cached_featuregram(clips[i][2], fresh=res["fv"][k])  # ... and stays on the device for the epochs to come
     for i, c in enumerate(clips):
-        if c[0] == "fv":  # cached featuregram (device copy after its first use): standardise + patches only
-            out[i] = fe.patches_from_featuregram(_cached_featuregram(c[1]), W, shift, layout=layout)
+        if c[0] == "fv":  # cached featuregram (device copy after its first use)
+            fvs[i] = _cached_featuregram(c[1])
+    return fe, fvs, patches
+
+
+def fold_statistics(PARAMS, rows=None):
+    """(mean, stdev) of PARAMS['frame_level_scaling']: PARAMS['mean_fold<k>'] / PARAMS['stdev_fold<k>'] of the fold k = PARAMS['fold']
+    as float64 vectors (Baseline_Results.py:608-621 sets them; here `data_stats_for_fold`).  ValueError when the fold or an entry
+    is missing, or -- with `rows` -- when their length is not the featuregram's row count."""
+    if 'fold' not in PARAMS:
+        raise ValueError("frame_level_scaling needs PARAMS['fold'] and the fold's statistics (data_stats_for_fold sets them)")
+    keys = ['mean_fold' + str(PARAMS['fold']), 'stdev_fold' + str(PARAMS['fold'])]
+    for k in keys:
+        if PARAMS.get(k) is None:
+            raise ValueError("frame_level_scaling needs PARAMS[%r]: compute the fold's statistics first (data_stats_for_fold)" % k)
+    mean, stdev = (np.asarray(PARAMS[k], dtype=np.float64).reshape(-1) for k in keys)
+    if mean.size != stdev.size or (rows is not None and mean.size != int(rows)):
+        raise ValueError("frame_level_scaling: PARAMS[%r] / PARAMS[%r] hold %d / %d values, the featuregram has %s rows"
+                         % (keys[0], keys[1], mean.size, stdev.size, "?" if rows is None else int(rows)))
+    return mean, stdev
+
+
+def _host_scaled(PARAMS, fv):
+    """scale_data on the host for the per-file callables: float64 (fv - mean[:, None]) / (stdev[:, None] + 1e-10)
+    (lib/cython_impl/tools.pyx:157-164)."""
+    fv = np.asarray(fv)
+    if fv.ndim != 2:
+        raise ValueError("FV should be of the shape (nFeatures, nFrames)")
+    mean, stdev = fold_statistics(PARAMS, fv.shape[0])
+    return (fv.astype(np.float64) - mean[:, None]) / (stdev[:, None] + 1e-10)
+
+
+def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
+    """The patches of the files `specs` as a list of float32 device tensors in the layout PARAMS['Model'] reads: (nP_i, W, 2F) for a
+    Lemaire_et_al variant; (nP_i, 2F, W, 1) for any other -- the Conv2D models' images, get_feature_patches'
+    np.expand_dims(patches, axis=3), Proposed_Work_Results.py:483-484 (a view: no copy).  The feature names without an H / P pair
+    have F in place of 2F.  Standardised per file by the front end's own kernels (a cached featuregram: standardise + patches only);
+    with PARAMS['frame_level_scaling'] the front end writes no patches and ONE `scaled_patches` launch scales every file of the
+    batch, cached ones included, with the fold's statistics."""
+    layout = "time_major" if 'Lemaire_et_al' in PARAMS['Model'] else "image"
+    if PARAMS.get('frame_level_scaling'):
+        fe, fvs, _ = _device_featuregrams_for(PARAMS, specs, featName, n_fft, n_mels)
+        out = []
+        if fvs:
+            mean, stdev = fold_statistics(PARAMS, fvs[0].shape[0])
+            out = fe.scaled_patches(fvs, mean, stdev, W, shift, layout=layout)
+    else:
+        fe, fvs, out = _device_featuregrams_for(PARAMS, specs, featName, n_fft, n_mels, W, shift, layout)
+        for i, p in enumerate(out):
+            if p is None:
+                out[i] = fe.patches_from_featuregram(fvs[i], W, shift, layout=layout)
     return [t.unsqueeze(3) for t in out] if layout == "image" else out
+
+
+def data_stats_for_fold(PARAMS, train_files=None, **kwargs):
+    """Baseline_Results.py:608-621: the statistics of fold PARAMS['fold'] from <feature_opDir>/data_stats_fold<k>_<n>class_train.pkl
+    when it is there, else computed by lib.preprocessing.get_data_stats over `train_files` (default PARAMS['train_files']) and saved
+    under that name with the reference's keys {'mean', 'stdev', 'nFrames'}.  Sets PARAMS['mean_fold<k>'] / PARAMS['stdev_fold<k>']
+    and returns nFrames = [nMuFrames, nSpFrames, nSpMuFrames].  kwargs go to get_data_stats."""
+    import pickle
+    from .lib import preprocessing as pp
+    fold = str(PARAMS['fold'])
+    path = os.path.join(PARAMS['feature_opDir'], 'data_stats_fold' + fold + '_' + str(len(PARAMS['classes'])) + 'class_train.pkl')
+    if not os.path.exists(path):
+        mean, stdev, nMu, nSp, nSpMu = pp.get_data_stats(PARAMS, PARAMS['train_files'] if train_files is None else train_files, **kwargs)
+        stats = {'mean': mean, 'stdev': stdev, 'nFrames': [nMu, nSp, nSpMu]}
+        os.makedirs(PARAMS['feature_opDir'], exist_ok=True)
+        tmp = "%s.%d.tmp" % (path, os.getpid())
+        with open(tmp, 'wb') as f:  # misc.save_obj: pickle.dump(obj, f, pickle.HIGHEST_PROTOCOL)
+            pickle.dump(stats, f, pickle.HIGHEST_PROTOCOL)
+        os.replace(tmp, path)
+    else:
+        with open(path, 'rb') as f:
+            stats = pickle.load(f)
+    PARAMS['mean_fold' + fold] = stats['mean']
+    PARAMS['stdev_fold' + fold] = stats['stdev']
+    return stats['nFrames']
 
 
 def _n_patches_of_file(PARAMS, path, n_fft, W, shift, lengths_cache):
@@ -328,9 +410,12 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
     n_mels = PARAMS['n_mels'][PARAMS['Model']]
     featName = PARAMS['featName'][PARAMS['Model']]
     W, W_shift = PARAMS['W'], PARAMS['W_shift']
-    if PARAMS.get('frame_level_scaling') or PARAMS.get('skewness_vector'):
-        raise ValueError("frame_level_scaling / skewness_vector are off in every reference configuration of this path "
-                         "(Proposed_Work_Results.py:802-804) and are not wired into the generator")
+    if PARAMS.get('skewness_vector'):
+        raise ValueError("skewness_vector is off in every reference configuration of this path "
+                         "(Proposed_Work_Results.py:802-804) and is not wired into the generator")
+    scaling = bool(PARAMS.get('frame_level_scaling'))
+    if scaling:
+        fold_statistics(PARAMS)  # the fold's statistics must be there before anything is computed
     from .sharding import class_block_rows, shard_range
     rank, world, dist = _rank_world(rank, world)
     if world > int(batchSize):
@@ -351,6 +436,8 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
     def one_file(spec):
         classname, sp, mu, db = spec
         fv = featuregram_fn(PARAMS, classname, PARAMS['feature_opDir'], sp, mu, db, n_fft, n_mels, featName)
+        if scaling:  # cscale_data between get_featuregram and get_feature_patches (Baseline_Results.py:91-93)
+            fv = _host_scaled(PARAMS, fv)
         return patches_fn(PARAMS, fv, W, W_shift, featName)
 
     def fill(classname, next_spec):
@@ -503,8 +590,11 @@ def test_file_wise_generator(PARAMS, file_name_sp, file_name_mu, target_dB, feat
     n_fft = PARAMS['n_fft'][PARAMS['Model']]
     n_mels = PARAMS['n_mels'][PARAMS['Model']]
     featName = PARAMS['featName'][PARAMS['Model']]
-    if PARAMS.get('frame_level_scaling') or PARAMS.get('skewness_vector'):
-        raise ValueError("frame_level_scaling / skewness_vector are not wired into this path")
+    if PARAMS.get('skewness_vector'):
+        raise ValueError("skewness_vector is not wired into this path")
+    scaling = bool(PARAMS.get('frame_level_scaling'))
+    if scaling:
+        fold_statistics(PARAMS)
     if file_name_mu == '':
         spec, label = ('speech', file_name_sp, '', None), 1
     elif file_name_sp == '':
@@ -515,6 +605,8 @@ def test_file_wise_generator(PARAMS, file_name_sp, file_name_mu, target_dB, feat
         from .lib import preprocessing as pp
         fv = (featuregram_fn or pp.get_featuregram)(PARAMS, spec[0], PARAMS['feature_opDir'], spec[1], spec[2], spec[3], n_fft,
                                                      n_mels, featName, save_feat=False)
+        if scaling:  # Baseline_Results.py:343-344
+            fv = _host_scaled(PARAMS, fv)
         batchData = (patches_fn or pp.get_feature_patches)(PARAMS, fv, PARAMS['W'], HARDCODED_TEST_SHIFT, featName)
         if 'Lemaire_et_al' in PARAMS['Model']:
             batchData = np.transpose(batchData, axes=(0, 2, 1))

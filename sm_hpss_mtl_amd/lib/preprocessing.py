@@ -5,6 +5,8 @@ return types as the reference, computed by the HIP library.
   get_feature_patches  (preprocessing.py:137-292)
   normalize_signal     (preprocessing.py:114-132)
   mix_signals          (preprocessing.py:297-325)
+  get_data_stats       (preprocessing.py:461-586)  one pass: the device's per-file row moments, combined on the host
+  scale_data           (preprocessing.py:590-614)
 plus the batched, device-resident fast path the reference does not have:
   featuregram_batch / feature_patches_batch.
 
@@ -229,3 +231,98 @@ def get_feature_patches(PARAMS, FV, patch_size, patch_shift, featName):
     if 'Lemaire_et_al' not in PARAMS['Model']:
         patches = np.expand_dims(patches, axis=3)
     return patches
+
+
+# ---- frame-level scaling: the statistics of a training fold ------------------------------------------------------
+def stats_file_specs(PARAMS, files):
+    """The files get_data_stats visits, in its order (preprocessing.py:476-503): the classes in PARAMS['classes'] order,
+    'speech_music' read from files['speech+music'] -> [(classname, sp_path, mu_path, target_dB)], paths under PARAMS['folder'] as
+    the generators build them (the listed name as it is; the reference rewrites a speech / music name's extension to .wav, the same
+    file in its .wav corpora)."""
+    folder = PARAMS['folder']
+    specs = []
+    for clNum in PARAMS['classes'].keys():
+        class_name = PARAMS['classes'][clNum]
+        for fl in (files['speech+music'] if class_name == 'speech_music' else files[class_name]):
+            if class_name == 'speech_music':
+                specs.append(('speech_music', folder + '/speech/' + fl['speech'], folder + '/music/' + fl['music'], fl['SMR']))
+            elif class_name == 'music':
+                specs.append(('music', '', folder + '/music/' + fl, None))
+            elif class_name == 'speech':
+                specs.append(('speech', folder + '/speech/' + fl, '', None))
+            else:
+                raise ValueError("get_data_stats: unknown class %r" % (class_name,))
+    return specs
+
+
+def device_row_moments(PARAMS, specs):
+    """[(sum (rows,) float64, m2 (rows,) float64, nonfinite (rows,) int, T)] of the files `specs`: ONE ragged front-end pass for the
+    files the reference's .npy cache does not hold (written to it and kept on the device as the generators do) and ONE
+    `Frontend.row_moments` launch for all of them."""
+    from .. import generators as _gen
+    model = PARAMS['Model']
+    fe, fvs, _ = _gen._device_featuregrams_for(PARAMS, specs, PARAMS['featName'][model], PARAMS['n_fft'][model], PARAMS['n_mels'][model])
+    if not fvs:
+        return []
+    s, m2, bad = (t.cpu().numpy() for t in fe.row_moments(fvs))
+    return [(s[i], m2[i], bad[i], int(fv.shape[1])) for i, fv in enumerate(fvs)]
+
+
+def get_data_stats(PARAMS, files, moments_fn=None, batch_files=256):
+    """preprocessing.py:461-586 -> (overall_mean float32, stdev float32, nMuFrames, nSpFrames, nSpMuFrames): per feature row, the
+    unweighted average of the class means and the standard deviation around it (divisor nFrames - 1) over every file of `files`.
+
+    The reference walks its featuregram cache twice (the class sums, then the squared deviations from the overall mean).  Here each
+    file is read ONCE, on the device: its row sums and M2 = sum((x - m)^2) around its own row mean m (`moments_fn(specs)`, default
+    `device_row_moments`, `batch_files` files per ragged batch), and the host combines them in np.longdouble in file order -- around
+    the overall mean mu, sum((x - mu)^2) = M2 + T (m - mu)^2 holds exactly.  A file with a NaN or an inf raises ValueError and is
+    named: the reference drops such feature ROWS, which changes the row count and cannot feed a model."""
+    ld = np.longdouble
+    specs = stats_file_specs(PARAMS, files)
+    moments_fn = moments_fn or (lambda chunk: device_row_moments(PARAMS, chunk))
+    per_file = []  # (classname, sum, m2, T)
+    for b0 in range(0, len(specs), int(batch_files)):
+        chunk = specs[b0:b0 + int(batch_files)]
+        got = moments_fn(chunk)
+        if len(got) != len(chunk):
+            raise RuntimeError("get_data_stats: %d files gave %d sets of moments" % (len(chunk), len(got)))
+        for spec, (s, m2, bad, T) in zip(chunk, got):
+            s, m2 = np.asarray(s, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+            if np.any(np.asarray(bad) != 0) or not (np.all(np.isfinite(s)) and np.all(np.isfinite(m2))):
+                raise ValueError("get_data_stats: the featuregram of %s holds NaN or inf values"
+                                 % " + ".join(repr(x) for x in spec[1:3] if x))
+            per_file.append((spec[0], s.astype(ld), m2.astype(ld), int(T)))
+    if not per_file:
+        raise ValueError("get_data_stats: no files")
+    rows = per_file[0][1].size
+    sums = {c: np.zeros(rows, dtype=ld) for c in ('music', 'speech', 'speech_music')}
+    frames = {'music': 0, 'speech': 0, 'speech_music': 0}
+    for c, s, _, T in per_file:
+        if s.size != rows:
+            raise ValueError("get_data_stats: featuregrams of %d and of %d rows" % (rows, s.size))
+        sums[c] = sums[c] + s
+        frames[c] += T
+    means = {c: sums[c] / (ld(frames[c]) + ld(1e-10)) for c in sums}  # :530-532
+    n_classes = len(PARAMS['classes'])
+    if n_classes == 2:
+        overall_mean = (means['music'] + means['speech']) / ld(2)
+    elif n_classes == 3:
+        overall_mean = ((means['music'] + means['speech']) + means['speech_music']) / ld(3)
+    else:
+        raise ValueError("get_data_stats: 2 or 3 classes, got %d" % n_classes)
+    var, nFrames = np.zeros(rows, dtype=ld), 0
+    for _, s, m2, T in per_file:
+        d = s / ld(T) - overall_mean
+        var = var + (m2 + ld(T) * d * d)
+        nFrames += T
+    stdev = np.sqrt(var / ld(nFrames - 1))
+    return (overall_mean.astype(np.float32), stdev.astype(np.float32), frames['music'], frames['speech'], frames['speech_music'])
+
+
+def scale_data(FV, mean, stdev):
+    """preprocessing.py:590-614: (FV - mean[:, None]) / stdev[:, None] on the host -- stdev itself, no epsilon (the generators
+    use tools.scale_data, which adds 1e-10)."""
+    FV = np.asarray(FV)
+    M = np.repeat(np.array(mean, ndmin=2).T, np.shape(FV)[1], axis=1)
+    S = np.repeat(np.array(stdev, ndmin=2).T, np.shape(FV)[1], axis=1)
+    return np.divide(np.subtract(FV, M), S)
