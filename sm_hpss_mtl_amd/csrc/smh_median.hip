@@ -232,10 +232,20 @@ int launch_routed(const Route &r, const float *S, int B, int K, int T, float *ha
     if (r.family == kFamSplit) {
         const Plan &q = r.plan;
         SMH_CHECK_HIP(hipFuncSetAttribute((const void *)r.se->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds));
+        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)r.se->fn_dma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds));
         dim3 grid(q.ntiles, B), block((q.nwh + q.nwp) * 64);
         const bool probe_noload = smh::probe_env("SMH_MEDIAN_PROBE_NOLOAD") != nullptr;  // timing experiment, outputs invalid
-        hipLaunchKernelGGL(r.se->fn, grid, block, q.lds, st, S, harm, perc, K, T, q.TT, q.stride, q.nsh, q.nsp, q.nwh,
-                           r.layout, probe_noload ? 1.f : -__builtin_inff(), __builtin_inff(), nullptr, nullptr, 0);
+        // Whole clip per tile: staged by LDS-DMA as the flat K x T image (row stride T) when that image is conflict-free for the
+        // harmonic lanes (gcd(T, 64) <= 2, as for the persistent kernel) and the copy, which starts at the 16-byte boundary below
+        // the clip and ends at the one above it, fits the tile the plan allocates.  SMH_MEDIAN_DMA_STAGE=0: the register staging.
+        const char *ev = getenv("SMH_MEDIAN_DMA_STAGE");
+        const size_t clip_bytes = (size_t)K * T * sizeof(float);
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(S);
+        const size_t align = (s0 % 16 == 0 && clip_bytes % 16 == 0) ? 16 : (s0 % 8 == 0 && clip_bytes % 8 == 0) ? 8 : 4;
+        const bool dma = !(ev && atoi(ev) == 0) && !probe_noload && q.ntiles == 1 && q.TT >= T && s0 % 4 == 0 &&
+                         ((T & 1) || ((T & 63) % 4 == 2)) && dma_stage_bytes(clip_bytes, align) <= q.lds;
+        hipLaunchKernelGGL(dma ? r.se->fn_dma : r.se->fn, grid, block, q.lds, st, S, harm, perc, K, T, q.TT, dma ? T : q.stride, q.nsh,
+                           q.nsp, q.nwh, r.layout, probe_noload ? 1.f : -__builtin_inff(), __builtin_inff(), nullptr, nullptr, 0);
         return smh::launch_status("hpss_median_split_kernel");
     }
     const Plan &p = r.plan;

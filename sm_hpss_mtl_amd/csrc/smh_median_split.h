@@ -283,6 +283,26 @@ __device__ __forceinline__ void split_median_walk_blocked(const float *line, int
     }
 }
 
+// Whole-clip staging by LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write, no index arithmetic): the `bytes` bytes at `src`
+// are copied in 16-byte chunks from the aligned address below `src`, 1 KB per wave and turn, linearly to `dst` (16-byte aligned).
+// Returns the misalignment `mis` in bytes: the image starts at dst + mis and up to mis + 15 bytes around it are copied with it.
+// The copy has landed for the workgroup after `s_waitcnt vmcnt(0)` in every wave and a barrier.
+__device__ __forceinline__ int stage_clip_dma(const char *src, int bytes, char *dst, int wave, int nwaves, int lane) {
+    const int mis = (int)(reinterpret_cast<uintptr_t>(src) & 15);
+    src -= mis;
+    const int nchunks = (bytes + mis + 15) >> 4;
+    for (int i = wave; i * 64 < nchunks; i += nwaves) {
+        const int c = i * 64 + lane;
+        if (c < nchunks)
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) void *)(src + (size_t)c * 16),
+                (__attribute__((address_space(3))) void *)(dst + i * 1024), 16, 0, 0);
+    }
+    return mis;
+}
+// LDS bytes the copy may write for a clip of `bytes` bytes whose start is only known to lie on a multiple of `align` bytes
+__host__ __device__ constexpr size_t dma_stage_bytes(size_t bytes, size_t align) { return (bytes + (16 - align) + 15) & ~(size_t)15; }
+
 // Register budget: the history is H*(H+1)-1 registers (80 for W = 17, 120 for W = 21), so the workgroup size is
 // chosen for 4 waves per SIMD (128 VGPRs) up to W = 17 and 3 waves per SIMD (168 VGPRs) above; two workgroups share
 // a CU (LDS: 2 x 80 KB), one staging its tile while the other computes.
@@ -299,14 +319,17 @@ struct SplitCfg {
 // rag != nullptr (smh_rag.h): clips of DIFFERENT lengths in one launch -- n_items (clip, frame tile) items, in clip-major order cut
 // into 8 contiguous ranges (one per XCD: neighbouring tiles share their halo columns in that L2), per-clip T and buffer offsets from
 // the descriptor table, harm in the 16-frame blocked layout.  Selection only: a clip's medians do not depend on how it was tiled.
-template <int LH, int LP>
+// DMA (equal-length launch, the tile is the whole clip, stride == T; smh_median.hip decides): the clip is staged by LDS-DMA as the
+// flat K x T image the persistent kernel below computes on, instead of through VGPRs into the odd-stride tile.
+template <int LH, int LP, bool DMA = false>
 __global__ void __launch_bounds__((SplitCfg<LH, LP>::kThreads), (SplitCfg<LH, LP>::kWavesPerSimd))
 hpss_median_split_kernel(const float *__restrict__ S, float *__restrict__ harm, float *__restrict__ perc, int K, int T,
                          int TT, int stride, int nsh, int nsp, int nwh, int harm_tmajor, float probe, float,
                          const smh_rag::Clip *__restrict__ rag, const smh_rag::Item *__restrict__ items, int n_items) {
     // probe > 0 (tools/gpu/r2_fusion_bound.sh, SMH_MEDIAN_PROBE_NOLOAD): the tile is NOT staged -- what the medians cost when
     // their input is already in LDS, i.e. the upper bound of fusing this kernel behind the STFT; the outputs are garbage
-    extern __shared__ __attribute__((aligned(16))) float tile[];
+    extern __shared__ __attribute__((aligned(16))) float tile_lds[];
+    const float *tile = tile_lds;  // (moved up by the clip's misalignment when it is staged by DMA)
     constexpr int HH = LH / 2;
     int b = blockIdx.y, tile_i = blockIdx.x;
     size_t spec_off, harm_off;
@@ -334,8 +357,12 @@ hpss_median_split_kernel(const float *__restrict__ S, float *__restrict__ harm, 
     // as one flat float2 stream with every load of a lane in flight at once (a single HBM round trip per workgroup)
     // and scattered to the odd-stride tile: element g = k*T + t lands at g + k*(stride - T).
     constexpr int kFlatBatch = SplitCfg<LH, LP>::kFlatBatch;
-    if (probe > 0.f) {
-        for (int i = threadIdx.x; i < K * stride; i += blockDim.x) tile[i] = (float)((i * 2654435761u) >> 8) * (1.0f / 16777216.f);
+    if constexpr (DMA) {
+        const int mis = stage_clip_dma(reinterpret_cast<const char *>(Sb), K * T * 4, reinterpret_cast<char *>(tile_lds), wave, nwaves, lane);
+        tile = reinterpret_cast<const float *>(reinterpret_cast<const char *>(tile_lds) + mis);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // each wave drains its own DMAs; the barrier below does the rest
+    } else if (probe > 0.f) {
+        for (int i = threadIdx.x; i < K * stride; i += blockDim.x) tile_lds[i] = (float)((i * 2654435761u) >> 8) * (1.0f / 16777216.f);
     } else if (TT >= T && ((K * T) & 1) == 0 && K * T <= kFlatBatch * 2 * (int)blockDim.x) {
         const int n2 = (K * T) >> 1;
         const float2v *src = reinterpret_cast<const float2v *>(Sb);
@@ -353,8 +380,8 @@ hpss_median_split_kernel(const float *__restrict__ S, float *__restrict__ harm, 
             if (idx < n2) {
                 const unsigned g = 2u * (unsigned)idx;
                 const unsigned k0 = __umulhi(g, magic), k1 = __umulhi(g + 1u, magic);
-                tile[g + k0 * extra] = v[r].x;
-                tile[g + 1u + k1 * extra] = v[r].y;
+                tile_lds[g + k0 * extra] = v[r].x;
+                tile_lds[g + 1u + k1 * extra] = v[r].y;
             }
         }
     } else if (((T | c0 | ncols) & 1) == 0 && ncols <= 128) {
@@ -372,8 +399,8 @@ hpss_median_split_kernel(const float *__restrict__ S, float *__restrict__ harm, 
             for (int r = 0; r < kRowBatch; ++r) {
                 const int k = k0 + r * nwaves;
                 if (k < K && lane < n2) {
-                    tile[k * stride + 2 * lane] = v[r].x;
-                    tile[k * stride + 2 * lane + 1] = v[r].y;
+                    tile_lds[k * stride + 2 * lane] = v[r].x;
+                    tile_lds[k * stride + 2 * lane + 1] = v[r].y;
                 }
             }
         }
@@ -391,7 +418,7 @@ hpss_median_split_kernel(const float *__restrict__ S, float *__restrict__ harm, 
 #pragma unroll
                 for (int r = 0; r < kRowBatch; ++r) {
                     const int k = k0 + r * nwaves;
-                    if (k < K && c < ncols) tile[k * stride + c] = v[r];
+                    if (k < K && c < ncols) tile_lds[k * stride + c] = v[r];
                 }
             }
         }
@@ -463,18 +490,7 @@ hpss_median_persist_kernel(const float *__restrict__ S, float *__restrict__ harm
     const size_t clip_bytes = (size_t)K * T * 4;
 
     auto issue_load = [&](int b, int buf) {
-        const char *src = reinterpret_cast<const char *>(S) + (size_t)b * clip_bytes;
-        const int mis = (int)(reinterpret_cast<uintptr_t>(src) & 15);
-        src -= mis;
-        const int nchunks = ((int)clip_bytes + mis + 15) >> 4;
-        char *dst = lds + buf * tile_bytes;
-        for (int i = wave; i * 64 < nchunks; i += nwaves) {
-            const int c = i * 64 + lane;
-            if (c < nchunks)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *)(src + (size_t)c * 16),
-                    (__attribute__((address_space(3))) void *)(dst + i * 1024), 16, 0, 0);
-        }
+        stage_clip_dma(reinterpret_cast<const char *>(S) + (size_t)b * clip_bytes, (int)clip_bytes, lds + buf * tile_bytes, wave, nwaves, lane);
     };
 
     int b = blockIdx.x;
@@ -539,7 +555,7 @@ using SplitFn = void (*)(const float *, float *, float *, int, int, int, int, in
                          const smh_rag::Clip *, const smh_rag::Item *, int);
 struct SplitEntry {
     int lh, lp, threads;
-    SplitFn fn;
+    SplitFn fn, fn_dma;  // fn_dma: the whole clip staged by LDS-DMA (stride == T)
 };
 const SplitEntry *find_split_kernel(int lh, int lp);  // smh_median_split.hip
 

@@ -3,7 +3,7 @@
 
 namespace smh_median {
 
-#define SMH_SPLIT_E2(a, b) {a, b, SplitCfg<a, b>::kThreads, hpss_median_split_kernel<a, b>},
+#define SMH_SPLIT_E2(a, b) {a, b, SplitCfg<a, b>::kThreads, hpss_median_split_kernel<a, b>, hpss_median_split_kernel<a, b, true>},
 #define SMH_SPLIT_SINGLE(w) SMH_SPLIT_E2(w, 0) SMH_SPLIT_E2(0, w)
 
 const SplitEntry kSplit[] = {

@@ -242,6 +242,9 @@ stft_mag_kernel(StftArgs a, const float *__restrict__ audio, const float *__rest
 //            n2 of Y[k1][.], store Z[k1 + 8 k2];
 //   phase 3  item (k <= 100, frame): |X[k]| and |X[200 - k]| from the pair Z[k], Z[200 - k]; frames fastest, so the
 //            (K, T) stores are contiguous along t.
+// Where the tile allows, phase 1 keeps one column n2 per thread (its window and twiddles in registers instead of LDS tables)
+// and phase 3 takes two neighbouring frames per item (one 8-byte store per bin): same operations in the same order per
+// element, see the kernel.
 // ~225 wave-instructions per frame instead of ~510 in the generic kernel.  Frame stride 201 float2 (odd) keeps the
 // frame-strided phase-3 reads and the 25-strided phase-2 reads conflict-free.
 constexpr int kF400 = 32;    // upper bound of frames per workgroup: phase 2 has 8 items per frame
@@ -372,7 +375,9 @@ template <int ROW>  // float2 pitch of a phase-1 table row: 25, or 40 = the 25 e
 __global__ void __launch_bounds__(512, 4)
 stft400_kernel(const float *__restrict__ audio, const float *__restrict__ window, const float2 *__restrict__ twM,
                const float2 *__restrict__ tw2M, float *__restrict__ S, int n_samples, int hop, int T, int F, int probe, int B,
-               int ntiles, const smh_rag::Clip *__restrict__ rag, const smh_rag::Item *__restrict__ items) {
+               int ntiles, int pairs, const smh_rag::Clip *__restrict__ rag, const smh_rag::Item *__restrict__ items) {
+    // pairs (SMH_STFT_PAIRS, default 1): phase 1 with a fixed column per thread and phase 3 in frame pairs where the tile allows; 0: the
+    // round-robin phase 1 with its LDS tables and one frame per phase-3 item on every tile (A/B runs, the bit-equality test)
     // probe (SMH_STFT_PROBE_NOSTORE, tools/gpu/r2_fusion_bound.sh): magnitudes computed but not stored -- the cost of S's trip to HBM
     constexpr int M = 200, K = 201;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
@@ -412,17 +417,49 @@ stft400_kernel(const float *__restrict__ audio, const float *__restrict__ window
     }
     const int t0 = tile * F, tid = threadIdx.x;
     const int nf = min(F, T - t0);
-    const int nthr = blockDim.x;
+    const int nthr = blockDim.x;  // 256 or 512
     const float *clip = audio + clip_off + (size_t)t0 * hop;
+    float *Sb = S + spec_off + t0;
     const int dq1 = nthr / 25, dr1 = nthr - dq1 * 25;
-    // Phase 1's audio is requested FIRST, for all of this thread's items at once (up to kRounds1 rounds of (frame, n2) items,
+    // Phase 3 in FRAME PAIRS (below) wants the two frames of a pair in two conflict-free sets of LDS slots: frame f of the tile
+    // lives in slot (f >> 1) + (f & 1) * (nf / 2).  Phases 1 and 2 only ever need the slot number.  A tile takes the pair form
+    // when its two magnitudes are one aligned 8-byte store: nf, t0 and T even and the clip's S on an 8-byte boundary; any other
+    // tile (odd T in a ragged call, T = 1, an odd tile under SMH_STFT_FRAMES) keeps slot = frame and one frame per item.
+    const int nh = nf >> 1;
+    const bool pair3 = pairs && ((nf | t0 | T) & 1) == 0 && (reinterpret_cast<uintptr_t>(Sb) & 7) == 0;
+    auto slot_frame = [&](int s) { return pair3 ? (s < nh ? 2 * s : 2 * (s - nh) + 1) : s; };
+    auto frame_slot = [&](int f) { return pair3 ? (f >> 1) + (f & 1) * nh : f; };
+    // Phase 1, FIXED COLUMN form (pairs != 0 and the tile's slots fit kRounds1 rounds of nthr / 25 frame groups: nf <= 30 at 256
+    // threads): thread tid owns column n2 = tid % 25 and frame group fg = tid / 25 and transforms the slots fg + r * (nthr / 25).
+    // Its column of the window (8 pairs) and of the twiddles W_200^(n2 k1) (7) is the same in every round, so it comes straight
+    // from memory into registers, requested together with the audio: no table in LDS, no staging loop, no barrier in front of
+    // phase 1, and none of the 15 ds_read per item.  (The round-robin item map below gives a thread another column every round.)
+    // Banks of the Z writes (ds_write_b64: groups of 16 lanes over 16 bank pairs, float2 offset 201 s + 25 k1 + n2): a group inside
+    // one frame group holds 16 consecutive n2; one that straddles two holds n2 = a .. 24 of slot s and 0 .. a - 10 of slot s + 1,
+    // i.e. a .. 24 and 201 + (0 .. a - 10) = 9 .. a - 1 (mod 16): 16 distinct pairs again.
+    // Otherwise the audio is requested FIRST, for all of this thread's items at once (up to kRounds1 rounds of (frame, n2) items,
     // 8 float2 each), then the twiddle / window tables travel to LDS: one trip to memory per workgroup where there were
     // one for the tables and one per round (a round's loads used to be issued when the previous round's butterflies were done).
     constexpr int kRounds1 = 3;
-    const bool ahead = 25 * nf <= kRounds1 * nthr;
+    const bool fixed = pairs && nf <= kRounds1 * dq1;
+    const bool ahead = !fixed && 25 * nf <= kRounds1 * nthr;
     v2 au[kRounds1][8];
     int fr_[kRounds1], n2_[kRounds1], col_[kRounds1];
-    if (ahead) {
+    v2 wr[8], tr[8];
+    if (fixed) {
+        const int fg = tid / 25, n2 = tid - fg * 25;  // (fg == nthr / 25: the threads past the last whole group, idle in phase 1)
+#pragma unroll
+        for (int r = 0; r < kRounds1; ++r) {
+            const int f = slot_frame(min(fg + r * dq1, nf - 1));
+            const v2 *fr = reinterpret_cast<const v2 *>(clip + (unsigned)(f * hop));
+#pragma unroll
+            for (int n1 = 0; n1 < 8; ++n1) au[r][n1] = fr[25 * n1 + n2];
+        }
+#pragma unroll
+        for (int n1 = 0; n1 < 8; ++n1) wr[n1] = reinterpret_cast<const v2 *>(window)[25 * n1 + n2];
+#pragma unroll
+        for (int k1 = 1; k1 < 8; ++k1) tr[k1] = reinterpret_cast<const v2 *>(twM)[n2 * k1];
+    } else if (ahead) {
         int f = tid / 25, n2 = tid - (tid / 25) * 25;
 #pragma unroll
         for (int r = 0; r < kRounds1; ++r) {
@@ -436,50 +473,66 @@ stft400_kernel(const float *__restrict__ audio, const float *__restrict__ window
             f += dq1 + carry;
         }
     }
-    // tw is stored by output index: tw[25 * k1 + n2] = W_200^(n2 k1), so that phase 1's lanes (n2 fastest) read consecutive
-    // entries (indexed n2 * k1 the reads were strided by k1: up to 4 lanes per bank)
-    // ROW == 40: a row holds its 25 entries and the first 15 again.  The table reads are ds_read2_b64, served in groups of 16 lanes
-    // over 32 banks, and a group in which the frame changes (n2 = a .. 24, 0 .. a - 10) meets itself in up to 7 banks -- 270 of the
-    // kernel's 720 conflict cycles per workgroup (simulated per phase; matches SQ_LDS_BANK_CONFLICT / 5120); with the longer rows
-    // such a group reads entries a .. a + 15.
-    for (int i = tid; i < 8 * ROW; i += nthr) {
-        const int k1 = i / ROW, j = i - ROW * k1, n2 = j < 25 ? j : j - 25;
-        tw[i] = reinterpret_cast<const v2 *>(twM)[n2 * k1];
-        win2[i] = reinterpret_cast<const v2 *>(window)[25 * k1 + n2];
-    }
-    for (int i = tid; i <= M; i += nthr) tw2[i] = reinterpret_cast<const v2 *>(tw2M)[i];
-    __syncthreads();
-
-    // phase 1
-    auto butterfly1 = [&](v2 (&v)[8], int f, int n2, int j) {  // j: the item's table column
+    // the untangle twiddles are first read in phase 3: one entry per thread (M + 1 <= nthr), written behind phase 1
+    const v2 t2 = reinterpret_cast<const v2 *>(tw2M)[min(tid, M)];
+    if (fixed) {
 #pragma unroll
-        for (int n1 = 0; n1 < 8; ++n1) v[n1] = v[n1] * win2[ROW * n1 + j];
-        pk_dft8(v);
-        v2 *zf = Z + f * kMP400 + n2;
-        zf[0] = v[0];
+        for (int r = 0; r < kRounds1; ++r) {
+            const int fg = tid / 25, s = fg + r * dq1;
+            if (fg < dq1 && s < nf) {
 #pragma unroll
-        for (int k1 = 1; k1 < 8; ++k1) zf[k1 * 25] = cmulp(v[k1], tw[ROW * k1 + j]);
-    };
-    if (ahead) {
+                for (int n1 = 0; n1 < 8; ++n1) au[r][n1] = au[r][n1] * wr[n1];
+                pk_dft8(au[r]);
+                v2 *zf = Z + s * kMP400 + (tid - fg * 25);
+                zf[0] = au[r][0];
 #pragma unroll
-        for (int r = 0; r < kRounds1; ++r)
-            if (fr_[r] < nf) butterfly1(au[r], fr_[r], n2_[r], col_[r]);
+                for (int k1 = 1; k1 < 8; ++k1) zf[k1 * 25] = cmulp(au[r][k1], tr[k1]);
+            }
+        }
     } else {
-        int it = tid;
-        for (int f = tid / 25, n2 = tid - (tid / 25) * 25; f < nf; it += nthr) {
-            const v2 *fr = reinterpret_cast<const v2 *>(clip + (unsigned)(f * hop));
-            v2 v[8];
+        // tw is stored by output index: tw[25 * k1 + n2] = W_200^(n2 k1), so that phase 1's lanes (n2 fastest) read consecutive
+        // entries (indexed n2 * k1 the reads were strided by k1: up to 4 lanes per bank)
+        // ROW == 40: a row holds its 25 entries and the first 15 again.  The table reads are ds_read2_b64, served in groups of 16
+        // lanes over 32 banks, and a group in which the frame changes (n2 = a .. 24, 0 .. a - 10) meets itself in up to 7 banks --
+        // 270 of the kernel's 720 conflict cycles per workgroup (simulated per phase; matches SQ_LDS_BANK_CONFLICT / 5120); with the
+        // longer rows such a group reads entries a .. a + 15.
+        for (int i = tid; i < 8 * ROW; i += nthr) {
+            const int k1 = i / ROW, j = i - ROW * k1, n2 = j < 25 ? j : j - 25;
+            tw[i] = reinterpret_cast<const v2 *>(twM)[n2 * k1];
+            win2[i] = reinterpret_cast<const v2 *>(window)[25 * k1 + n2];
+        }
+        __syncthreads();
+        auto butterfly1 = [&](v2 (&v)[8], int f, int n2, int j) {  // j: the item's table column
 #pragma unroll
-            for (int n1 = 0; n1 < 8; ++n1) v[n1] = fr[25 * n1 + n2];
-            butterfly1(v, f, n2, column(it, f, n2));
-            n2 += dr1;
-            const int carry = n2 >= 25 ? 1 : 0;
-            n2 -= 25 * carry;
-            f += dq1 + carry;
+            for (int n1 = 0; n1 < 8; ++n1) v[n1] = v[n1] * win2[ROW * n1 + j];
+            pk_dft8(v);
+            v2 *zf = Z + frame_slot(f) * kMP400 + n2;
+            zf[0] = v[0];
+#pragma unroll
+            for (int k1 = 1; k1 < 8; ++k1) zf[k1 * 25] = cmulp(v[k1], tw[ROW * k1 + j]);
+        };
+        if (ahead) {
+#pragma unroll
+            for (int r = 0; r < kRounds1; ++r)
+                if (fr_[r] < nf) butterfly1(au[r], fr_[r], n2_[r], col_[r]);
+        } else {
+            int it = tid;
+            for (int f = tid / 25, n2 = tid - (tid / 25) * 25; f < nf; it += nthr) {
+                const v2 *fr = reinterpret_cast<const v2 *>(clip + (unsigned)(f * hop));
+                v2 v[8];
+#pragma unroll
+                for (int n1 = 0; n1 < 8; ++n1) v[n1] = fr[25 * n1 + n2];
+                butterfly1(v, f, n2, column(it, f, n2));
+                n2 += dr1;
+                const int carry = n2 >= 25 ? 1 : 0;
+                n2 -= 25 * carry;
+                f += dq1 + carry;
+            }
         }
     }
+    if (tid <= M) tw2[tid] = t2;
     __syncthreads();
-    // phase 2: read, barrier, compute, write in place (natural order); 8 * F <= blockDim.x items.
+    // phase 2: read, barrier, compute, write in place (natural order); 8 * F <= blockDim.x items, one per (k1, SLOT).
     // Banks: the 25 reads of an item compile to ds_read2_b64, which LDS serves in groups of 16 consecutive lanes over 32
     // dword banks.  Items are laid out FRAMES FASTEST (item = k1 * nf + f): a 16-lane group then holds 16 frames of one k1, float2
     // offsets 201 f + 25 k1 + n2, and 201 = 9 (mod 16) is odd -- 16 distinct bank pairs.  (Round 2 had k1 fastest: 2 frames x 8 k1
@@ -504,29 +557,50 @@ stft400_kernel(const float *__restrict__ audio, const float *__restrict__ window
         }
     }
     __syncthreads();
-    // phase 3: untangle + magnitude, one pair (k, M - k) per item.  Item it = k * nf + f, frames fastest (contiguous stores);
+    // phase 3: untangle + magnitude, one pair of bins (k, M - k) per item.
+    // X[k] = (e - i g) / 2 and X[M-k] = conj(e + i g) / 2 with e = A + conj(B), g = tw2[k] (A - conj(B)):
+    // one twiddle product serves both bins of the pair; the halving is exact, so it is taken on the magnitude
+    auto untangle = [](v2 A, v2 Bz, v2 w, float &lo, float &hi) {
+        const v2 e = add_conj(A, Bz), d = sub_conj(A, Bz);
+        const v2 g = cmulp(d, w);
+        const v2 x = sub_i(e, g);  // (e.x + g.y, e.y - g.x)
+        lo = 0.5f * mag(x.x, x.y);
+        const v2 y = add_i(e, g);  // (e.x - g.y, e.y + g.x)
+        hi = 0.5f * mag(y.x, y.y);
+    };
+    if (pair3) {
+        // Item it = k * (nf / 2) + fp: the frames 2 fp and 2 fp + 1 (slots fp and fp + nf / 2, both at the odd stride 201) share
+        // the (k, fp) carry arithmetic, the tw2[k] read and the store offsets, and their magnitudes leave as one 8-byte store
+        // per bin.  Frame pairs fastest, so the (K, T) stores stay contiguous along t.
+        const int dq = nthr / nh, dr = nthr - dq * nh;
+        int k = tid / nh, fp = tid - k * nh;
+        for (; k <= M / 2;) {
+            const v2 *z0 = Z + fp * kMP400, *z1 = z0 + nh * kMP400;
+            const int kb = k == 0 ? 0 : M - k;
+            const v2 w = tw2[k];
+            float2 lo, hi;
+            untangle(z0[k], z0[kb], w, lo.x, hi.x);
+            untangle(z1[k], z1[kb], w, lo.y, hi.y);
+            if (!probe || lo.x == -1.f) *reinterpret_cast<float2 *>(Sb + (unsigned)(k * T + 2 * fp)) = lo;
+            if (k != M / 2 && (!probe || hi.x == -1.f)) *reinterpret_cast<float2 *>(Sb + (unsigned)((M - k) * T + 2 * fp)) = hi;
+            fp += dr;
+            const int carry = fp >= nh ? 1 : 0;
+            fp -= carry * nh;
+            k += dq + carry;
+        }
+        return;
+    }
+    // One frame per item, it = k * nf + f, frames fastest (contiguous stores);
     // (k, f) advance by (nthr / nf, nthr % nf) with a carry instead of a division per item, and every address is a 32-bit
     // offset from a uniform base: the item used to spend more instructions on 64-bit index arithmetic than on the butterfly.
-    float *Sb = S + spec_off + t0;
     const int dq = nthr / nf, dr = nthr - dq * nf;
     int k = tid / nf, f = tid - k * nf;
     for (; k <= M / 2; ) {
         const v2 *zf = Z + f * kMP400;
-        const v2 A = zf[k], Bz = zf[k == 0 ? 0 : M - k];
-        // X[k] = (e - i g) / 2 and X[M-k] = conj(e + i g) / 2 with e = A + conj(B), g = tw2[k] (A - conj(B)):
-        // one twiddle product serves both bins of the pair; the halving is exact, so it is taken on the magnitude
-        const v2 e = add_conj(A, Bz), d = sub_conj(A, Bz);
-        const v2 g = cmulp(d, tw2[k]);
-        {
-            const v2 x = sub_i(e, g);  // (e.x + g.y, e.y - g.x)
-            const float v = 0.5f * mag(x.x, x.y);
-            if (!probe || v == -1.f) Sb[(unsigned)(k * T + f)] = v;
-        }
-        if (k != M / 2) {
-            const v2 x = add_i(e, g);  // (e.x - g.y, e.y + g.x)
-            const float v = 0.5f * mag(x.x, x.y);
-            if (!probe || v == -1.f) Sb[(unsigned)((M - k) * T + f)] = v;
-        }
+        float lo, hi;
+        untangle(zf[k], zf[k == 0 ? 0 : M - k], tw2[k], lo, hi);
+        if (!probe || lo == -1.f) Sb[(unsigned)(k * T + f)] = lo;
+        if (k != M / 2 && (!probe || hi == -1.f)) Sb[(unsigned)((M - k) * T + f)] = hi;
         f += dr;
         const int carry = f >= nf ? 1 : 0;
         f -= carry * nf;
@@ -540,6 +614,11 @@ namespace {
 // the specialised 8 x 25 kernel serves n_fft = 400 with an even hop (frames start on 8-byte boundaries when the clip does)
 bool stft400_ok(const smh_ctx *ctx) {
     return ctx->cfg.n_fft == 400 && ctx->M == 200 && ctx->cfg.win_length <= 400 && (ctx->cfg.hop % 2) == 0 && !getenv("SMH_STFT_GENERIC");
+}
+// SMH_STFT_PAIRS=0: stft400_kernel's round-robin phase 1 and one-frame phase 3 on every tile (A/B runs, tests); same bits either way
+int stft400_pairs() {
+    const char *ev = getenv("SMH_STFT_PAIRS");
+    return ev && atoi(ev) == 0 ? 0 : 1;
 }
 void generic_args(const smh_ctx *ctx, StftArgs &a) {
     a.n_fft = ctx->cfg.n_fft, a.hop = ctx->cfg.hop, a.M = ctx->M, a.K = ctx->K;
@@ -588,7 +667,7 @@ int launch_rag(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_r
         const size_t lds = sizeof(float2) * (8 * 25 + 202 + 8 * 25 + (size_t)F * kMP400);
         SMH_CHECK_HIP(hipFuncSetAttribute((const void *)stft400_kernel<25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(stft400_kernel<25>, dim3(grid), dim3(256), lds, st, d_audio, ctx->d_window, ctx->d_twM, ctx->d_tw2M, d_S, 0,
-                           ctx->cfg.hop, 0, F, 0, n_items, 0, d_clips, d_items);
+                           ctx->cfg.hop, 0, F, 0, n_items, 0, stft400_pairs(), d_clips, d_items);
         return smh::launch_status("stft400_kernel (ragged)");
     }
     StftArgs a;
@@ -624,7 +703,9 @@ extern "C" int smh_stft_mag_f32(const smh_ctx *ctx, const float *d_audio, int B,
         if (maxf < 1) maxf = 1;
         if (maxf > nthreads / 8) maxf = nthreads / 8;
         const int ntiles = (T + maxf - 1) / maxf;
-        const int F = (T + ntiles - 1) / ntiles;
+        int F = (T + ntiles - 1) / ntiles;
+        const int pairs = stft400_pairs();
+        if (pairs && T % 2 == 0 && F % 2 != 0 && F < maxf) ++F;  // even tiles for an even T: every tile can take phase 3 in frame pairs
         int row = 25;
         if (const char *ev = smh::probe_env("SMH_STFT_ROW")) row = atoi(ev) == 40 ? 40 : 25;
         const size_t lds = sizeof(float2) * (8 * row + 202 + 8 * row + (size_t)F * kMP400);
@@ -638,7 +719,7 @@ extern "C" int smh_stft_mag_f32(const smh_ctx *ctx, const float *d_audio, int B,
         if (by_xcd) grid = dim3((unsigned)(8 * (((long long)B * nt + 7) / 8)), 1);
         const int probe = smh::probe_env("SMH_STFT_PROBE_NOSTORE") ? 1 : 0;  // timing experiment, S is not written
         hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, d_audio, ctx->d_window, ctx->d_twM,
-                           ctx->d_tw2M, d_S, n_samples, ctx->cfg.hop, T, F, probe, B, by_xcd ? nt : 0, nullptr, nullptr);
+                           ctx->d_tw2M, d_S, n_samples, ctx->cfg.hop, T, F, probe, B, by_xcd ? nt : 0, pairs, nullptr, nullptr);
         return smh::launch_status("stft400_kernel");
     }
     StftArgs a;
