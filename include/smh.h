@@ -710,6 +710,10 @@ int smh_trainer_apply_f32(smh_trainer *t, int optimizer, float lr, float beta1, 
  * (launch_hp_feat + launch_std_patch: window pairs without a block-split median kernel, clips too short for the tiled medians or
  * too long for the streaming kernels' 32-bit offsets).  -1 for a null context or T < 1. */
 int smh_internal_frontend_route(const smh_ctx *ctx, int T);
+/* The bin-walk plan smh_ctx_create built for this context's filterbank (host values, nothing is launched):
+ * out = {feat_walk_ok, feat_pend, segments of plan 0 (hp_feat_walk_kernel), segments of plan 1 (the LDS-image kernels)}.
+ * feat_pend, the most filters pending at any bin, selects features_half_kernel<2, ...> (<= 2) or <4, ...>. */
+int smh_internal_feat_plan(const smh_ctx *ctx, int out[4]);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,7 @@ SIGNATURES = {
     "smh_plain_frontend_ragged_layout_f32": (_i, [_vp, _fp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), _i, _i, _i, _i, _fp, _fp, _vp,
                                                   _sz, _vp]),
     "smh_internal_frontend_route": (_i, [_vp, _i]),
+    "smh_internal_feat_plan": (_i, [_vp, C.POINTER(C.c_int)]),
     "smh_normalize_workspace_bytes": (_sz, [_i, _i]),
     "smh_silence_workspace_bytes": (_sz, [_i, _i, _i]),
     "smh_normalize_f32": (_i, [_fp, _i, _i, _fp, _vp, _sz, _vp]),

@@ -415,6 +415,20 @@ hp_feat_walk_kernel(FeatPlan fp, int log_db, const float *__restrict__ S, const 
     }
 }
 
+// A row whose deviation is below 1 / FLT_MAX has no f32 reciprocal scale: (float)(1.0 / scale) is inf and the standardised row inf or
+// NaN where sklearn, which divides in f64, returns finite values.  Only linear features reach it, with rows of f32 denormals (the dB
+// features' steps are ~1e-6).  By the time the scaler runs the featuregram has left for HBM and the LDS image serves the scaler alone,
+// so such a row is replaced in place by its centred values -- x - mean rounded to f32 as sklearn's `X -= mean` rounds it, on the
+// denormal grid -- taken up by 2^64 (exact: a non-constant row this narrow lies below 1e-23), its mean becomes 0 and its scale
+// 2^64 times itself: every consumer of s_mean / s_lo / s_inv standardises it unchanged.  One f64 compare per row otherwise.
+constexpr double kMinF32Scale = 1.0 / 3.4028234663852886e38;
+constexpr float kLift = 18446744073709551616.0f;  // 2^64
+__device__ __forceinline__ bool centre_denormal_row(float *row, int T, double mean, double scale) {
+    if (scale >= kMinF32Scale) return false;
+    for (int t = 0; t < T; ++t) row[t] = (float)((double)row[t] - mean) * kLift;
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // fused fast path, kernel 2: one workgroup per (clip, half): top_db clip (written back: the final
 // featuregram) -> StandardScaler per row -> time-major patches (B*nP, W, 2*rows) for the TCN, or, IMAGE, the Conv2D models'
@@ -498,10 +512,13 @@ std_patch_kernel(int log_db, float *__restrict__ fv, const int *__restrict__ max
         const bool constant = var <= (double)T * eps * var + nm * nm;  // sklearn _is_constant_feature
         double scale = sqrt(var);
         if (constant || scale == 0.0) scale = 1.0;
-        s_mean[r] = (float)mean;
+        const bool lifted = centre_denormal_row(tile + r * ld, T, mean, scale);
+        const double mean_s = lifted ? 0.0 : mean;
+        if (lifted) scale *= (double)kLift;
+        s_mean[r] = (float)mean_s;
         // keep the f64 mean exactly: store the low part too (mean = hi + lo)
         s_inv[r] = (float)(1.0 / scale);
-        s_mean[rows + rows + r] = (float)(mean - (double)(float)mean);
+        s_mean[rows + rows + r] = (float)(mean_s - (double)(float)mean_s);
     }
     __syncthreads();
     const float *s_lo = s_mean + 2 * rows;
@@ -743,9 +760,12 @@ features_clip_kernel(FeatPlan fp, int log_db, int stop_after /* tuning: phase pr
         const bool constant = var <= (double)T * eps * var + nm * nm;
         double scale = sqrt(var);
         if (constant || scale == 0.0) scale = 1.0;
-        s_mean[r] = (float)mean;
+        const bool lifted = centre_denormal_row(img + r * ld, T, mean, scale);  // (the row's other three lanes are done with it)
+        const double mean_s = lifted ? 0.0 : mean;
+        if (lifted) scale *= (double)kLift;
+        s_mean[r] = (float)mean_s;
         s_inv[r] = (float)(1.0 / scale);
-        s_lo[r] = (float)(mean - (double)(float)mean);
+        s_lo[r] = (float)(mean_s - (double)(float)mean_s);
     }
     __syncthreads();
     if (stop_after == 3) return;
@@ -1067,9 +1087,12 @@ features_half_kernel(FeatPlan fp, int log_db, int stop_after, const float *__res
         const bool constant = var <= (double)T * eps * var + nm * nm;
         double scale = sqrt(var);
         if (constant || scale == 0.0) scale = 1.0;
-        s_mean[r] = (float)mean;
+        const bool lifted = centre_denormal_row(img + r * ld, T, mean, scale);  // (the row's other three lanes are done with it)
+        const double mean_s = lifted ? 0.0 : mean;
+        if (lifted) scale *= (double)kLift;
+        s_mean[r] = (float)mean_s;
         s_inv[r] = (float)(1.0 / scale);
-        s_lo[r] = (float)(mean - (double)(float)mean);
+        s_lo[r] = (float)(mean_s - (double)(float)mean_s);
     }
     stamp(3);  // statistics
     __syncthreads();
@@ -1229,6 +1252,9 @@ using HalfKernel = decltype(&features_half_kernel<2>);
 using ClipKernel = decltype(&features_clip_kernel<false>);
 using StdPatchKernel = decltype(&std_patch_kernel<false>);
 
+// pend2 = (feat_pend <= 2).  No Slaney bank reaches the <4, ...> instantiations: smh_ctx_create finds feat_pend <= 2 for every n_mels in
+// 1 .. 256 with n_fft 400 / 512 and mel_sr 16000 / 22050 (a frequency lies in at most two triangles; tests/test_feature_edges_gpu.py
+// sweeps it through smh_internal_feat_plan).  They are therefore UNTESTED; removing them is a follow-up ("Feature routes").
 HalfKernel pick_half_kernel(bool pend2, bool rag, bool image, HalfTool tool) {
     if (rag) {
         if (image) return pend2 ? features_half_kernel<2, false, false, true, true> : features_half_kernel<4, false, false, true, true>;
@@ -1260,6 +1286,14 @@ extern "C" int smh_internal_feat_residency(int rows, int T) {
     int nb = -1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 512, ldh) != hipSuccess) return -1;
     return nb;
+}
+
+// What pick_half_kernel's `pend2` and the walk kernels' segment loops are decided by (tests/test_feature_edges_gpu.py sweeps the
+// Slaney banks with it): host values of the context, nothing is launched.
+extern "C" int smh_internal_feat_plan(const smh_ctx *c, int out[4]) {
+    SMH_REQUIRE(c && out, "smh_internal_feat_plan: null argument");
+    out[0] = c->feat_walk_ok, out[1] = c->feat_pend, out[2] = c->feat_nseg[0], out[3] = c->feat_nseg[1];
+    return SMH_OK;
 }
 
 namespace smh_feat {
