@@ -329,6 +329,23 @@ long long smh_scaled_patches_count(const int *h_T, int B, int W, int shift, long
 int smh_scaled_patches_f32(const smh_ctx *ctx, const float *const *h_fv, const int *h_T, int B, int rows, const double *d_mean,
                            const double *d_stdev, int W, int shift, int patch_layout, float *d_patches, void *stream);
 
+/* ---- the skewness-vector feed (PARAMS['skewness_vector'] = 'Row' / 'Col'): get_data_statistics of every patch, taken straight
+ * from featuregrams on the device -- h_fv, h_T, B, rows, W, shift, the per-clip table and the patch grid exactly as for
+ * smh_scaled_patches_f32 (patch counts and offsets: smh_scaled_patches_count); no patch is written.  stat: 0 mean, 1 variance,
+ * 2 skew, 3 kurtosis as smh_data_statistics_f64 numbers them.  axis 1 reduces over the W frames of a patch: d_out is
+ * (sum_b nP_b, rows); axis 0 over the rows of a frame: (sum_b nP_b, W).  d_out is float64 (out_f32 = 0) or float32 rounded once from
+ * the float64 result.  The value under the statistic is the patch element the existing entries write, bit for bit: with d_mean =
+ * d_stdev = NULL smh_standardize_rows_f32's per-file StandardScaler value (statistics over the file's own h_T[b] frames), with both
+ * given ((rows) float64 on the device) smh_scaled_patches_f32's.  The statistic is float64 and two-pass (the mean, then the central
+ * moments of x - mean, sums in index order); a window with m2 == 0 has skew 0 and kurtosis -3.  The order of every addition depends
+ * on W (axis 1) or rows (axis 0) alone: a file's vectors are bit-identical alone and in any batch.  A clip without a patch writes
+ * nothing.  axis 1 takes W <= 8192.  d_work: smh_patch_statistics_workspace_bytes(B, rows, axis, with_stats) bytes, 8-byte aligned
+ * (0 bytes, and d_work may be NULL, for axis 1 or with statistics).                                                               */
+size_t smh_patch_statistics_workspace_bytes(int B, int rows, int axis, int with_stats);
+int smh_patch_statistics(const smh_ctx *ctx, const float *const *h_fv, const int *h_T, int B, int rows, const double *d_mean,
+                         const double *d_stdev, int W, int shift, int stat, int axis, int out_f32, void *d_out, void *d_work,
+                         size_t work_bytes, void *stream);
+
 /* ---- a10-a12: B3_MTL = get_Lemaire_MTL_model (lib/proposed_architectures.py:85-170, 25-80) ---- */
 typedef struct smh_model_cfg {
     int32_t n_feat;     /* N_MELS argument = input_shape[1]: 240                       */

@@ -110,6 +110,8 @@ SIGNATURES = {
     "smh_row_moments_f64": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_int), _i, _i, _vp, _vp, _vp]),
     "smh_scaled_patches_count": (C.c_longlong, [C.POINTER(C.c_int), _i, _i, _i, C.POINTER(C.c_longlong)]),
     "smh_scaled_patches_f32": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_int), _i, _i, _vp, _vp, _i, _i, _i, _fp, _vp]),
+    "smh_patch_statistics_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smh_patch_statistics": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_int), _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "smh_model_create": (_i, [C.POINTER(ModelCfg), C.POINTER(_vp)]),
     "smh_model_create_heads": (_i, [C.POINTER(ModelCfg), _i, C.POINTER(_vp)]),
     "smh_model_destroy": (None, [_vp]),

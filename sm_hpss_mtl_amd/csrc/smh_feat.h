@@ -146,6 +146,39 @@ __device__ __forceinline__ void patch_range(int u, int W, int shift, int nP, int
     p_lo = u - W + 1 <= 0 ? 0 : (u - W + shift) / shift;  // ceil((u - W + 1) / shift)
 }
 
+// ---- the per-file StandardScaler of smh_standardize_rows_f32, shared with the patch statistics (smh_skew.hip): ONE definition, so
+// that a value standardised there is bit for bit the patch element written here ------------------------------------------------------
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// sklearn StandardScaler statistics of one row held by one wave: float64 mean / population variance,
+// (near-)constant rows are left unscaled (sklearn _is_constant_feature / _handle_zeros_in_scale).
+template <typename Load>
+__device__ __forceinline__ void row_stats(int T, int lane, Load &&load, double &mean, double &scale) {
+    double s = 0.0;
+    for (int t = lane; t < T; t += 64) s += (double)load(t);
+    mean = wave_sum(s) / (double)T;
+    double q = 0.0;
+    for (int t = lane; t < T; t += 64) {
+        const double d = (double)load(t) - mean;
+        q += d * d;
+    }
+    const double var = wave_sum(q) / (double)T;
+    const double eps = 2.220446049250313e-16;
+    const double nm = (double)T * mean * eps;
+    const bool constant = var <= (double)T * eps * var + nm * nm;
+    scale = sqrt(var);
+    if (constant || scale == 0.0) scale = 1.0;
+}
+
+// `X -= mean; X /= scale` applied to a float32 array with float64 statistics: two roundings.
+__device__ __forceinline__ float standardize(float x, double mean, double scale) {
+    const float c = (float)((double)x - mean);
+    return (float)((double)c / scale);
+}
+
 }  // namespace smh_feat
 
 namespace smh_median {

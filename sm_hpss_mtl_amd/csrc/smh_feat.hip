@@ -114,36 +114,9 @@ __global__ void power_to_db_kernel(const float *__restrict__ X, int elems, float
     for (int i = threadIdx.x; i < elems; i += blockDim.x) y[i] = fmaxf(y[i], thr);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// sklearn StandardScaler statistics of one row held by one wave: float64 mean / population variance,
-// (near-)constant rows are left unscaled (sklearn _is_constant_feature / _handle_zeros_in_scale).
-template <typename Load>
-__device__ __forceinline__ void row_stats(int T, int lane, Load &&load, double &mean, double &scale) {
-    double s = 0.0;
-    for (int t = lane; t < T; t += 64) s += (double)load(t);
-    mean = wave_sum(s) / (double)T;
-    double q = 0.0;
-    for (int t = lane; t < T; t += 64) {
-        const double d = (double)load(t) - mean;
-        q += d * d;
-    }
-    const double var = wave_sum(q) / (double)T;
-    const double eps = 2.220446049250313e-16;
-    const double nm = (double)T * mean * eps;
-    const bool constant = var <= (double)T * eps * var + nm * nm;
-    scale = sqrt(var);
-    if (constant || scale == 0.0) scale = 1.0;
-}
-
-// `X -= mean; X /= scale` applied to a float32 array with float64 statistics: two roundings.
-__device__ __forceinline__ float standardize(float x, double mean, double scale) {
-    const float c = (float)((double)x - mean);
-    return (float)((double)c / scale);
-}
+// the per-file StandardScaler of one row (float64 statistics, two roundings): smh_feat.h, shared with the patch statistics
+using smh_feat::row_stats;
+using smh_feat::standardize;
 
 __global__ void standardize_rows_kernel(const float *__restrict__ X, int n_rows, int T, float *__restrict__ Y) {
     const int lane = threadIdx.x & 63;

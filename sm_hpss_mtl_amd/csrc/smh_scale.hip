@@ -32,6 +32,7 @@
 
 #include "smh_common.h"
 #include "smh_feat.h"
+#include "smh_fvtable.h"
 #include "smh_rag.h"
 
 namespace {
@@ -42,16 +43,10 @@ constexpr int kTile = 64;       // frames per chunk: one lane per frame
 constexpr int kRowBlock = 32;   // rows per patch workgroup: 128-byte runs in the time-major patches
 constexpr int kRowsPerWave = kRowBlock / kWaves;
 constexpr int kSegFrames = 4 * kTile;  // frames per patch workgroup
-constexpr size_t kTableBytes = 64 * 1024;  // one launch's table: what a staging slot holds without growing
 
-// one featuregram of a call (32 bytes)
-struct FvClip {
-    const float *fv;      // (rows, T), dense
-    long long patch_off;  // patches in front of this clip's
-    int T, Ttiled, nP, pad_;
-};
-static_assert(sizeof(FvClip) == 32, "FvClip is a 32-byte table entry");
-constexpr int kMaxClips = (int)(kTableBytes / sizeof(FvClip));
+using smh_fvtable::fill_table;
+using smh_fvtable::FvClip;
+using smh_fvtable::kMaxClips;
 
 __device__ __forceinline__ double wave_sum(double a) {
     for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
@@ -161,25 +156,6 @@ scaled_patches_kernel(const FvClip *__restrict__ clips, int rows, int nrb, const
             __syncthreads();
         }
     }
-}
-
-// the table of clips [b0, b0 + n); W < 1: no patch geometry (the moments).  patch_off runs on over the whole call.
-int fill_table(const char *who, const float *const *h_fv, const int *h_T, int b0, int n, int W, int shift, long long &patch_off,
-               int &max_T, std::vector<FvClip> &t) {
-    t.resize(n);
-    for (int i = 0; i < n; ++i) {
-        const int b = b0 + i, T = h_T[b];
-        SMH_REQUIRE(h_fv[b] && T >= 1, "%s: featuregram %d is null or has T=%d frames", who, b, T);
-        SMH_REQUIRE((reinterpret_cast<uintptr_t>(h_fv[b]) % 4) == 0, "%s: featuregram %d is not float-aligned", who, b);
-        FvClip &c = t[i];
-        c.fv = h_fv[b], c.T = T, c.pad_ = 0;
-        c.Ttiled = W >= 1 ? smh_tiled_frames(T, W) : T;
-        c.nP = W >= 1 ? smh_num_patches(c.Ttiled, W, shift) : 0;
-        c.patch_off = patch_off;
-        patch_off += c.nP;
-        max_T = std::max(max_T, T);
-    }
-    return SMH_OK;
 }
 
 }  // namespace

@@ -515,3 +515,45 @@ class Frontend:
         _lib.check(self.lib.smh_scaled_patches_f32(self._h, h_fv, h_T, B, rows, _ptr(stats[0]), _ptr(stats[1]), int(W), int(shift), lay,
                                                    _ptr(patches), _stream()), "smh_scaled_patches_f32")
         return [patches[int(p_off[b]):int(p_off[b + 1])] for b in range(B)]
+
+    # ---- the skewness-vector feed (PARAMS['skewness_vector']): statistics of every patch, no patch written ----
+    _STATS = {"mean": 0, "variance": 1, "skew": 2, "kurtosis": 3}
+
+    def patch_statistics(self, fvs, W, shift, axis, stat="skew", mean=None, stdev=None, dtype=torch.float32):
+        """`smh_patch_statistics`: tools.get_data_statistics(patches, stat, axis) of every patch of every featuregram in ONE call,
+        straight from the featuregrams.  fvs as for `row_moments`.  The value under the statistic is the patch element
+        `patches_from_featuregram` writes (per-file StandardScaler) or, with mean / stdev (one value per row, read as float64),
+        `scaled_patches`'.  axis=1: over a patch's W frames -> (nP_b, rows); axis=0: over its rows -> (nP_b, W).  The statistic is
+        float64; dtype=torch.float32 rounds it once.  Returns a list of per-clip views of one buffer.  Argument errors are
+        ValueErrors raised before anything is launched."""
+        if axis not in (0, 1):
+            raise ValueError("patch_statistics: axis must be 0 (over the rows) or 1 (over the frames), got %r" % (axis,))
+        if stat not in self._STATS:
+            raise ValueError("patch_statistics: stat must be one of %s, got %r" % (sorted(self._STATS), stat))
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("patch_statistics: dtype must be torch.float32 or torch.float64, got %r" % (dtype,))
+        W, shift = int(W), int(shift)
+        if W < 1 or shift < 1:
+            raise ValueError("patch_statistics: bad patch geometry W=%d shift=%d" % (W, shift))
+        if (mean is None) != (stdev is None):
+            raise ValueError("patch_statistics: mean and stdev come together or not at all")
+        keep, h_fv, h_T, rows = self._fv_table(fvs, "patch_statistics")
+        B, dev = len(keep), keep[0].device
+        stats = [None, None]
+        if mean is not None:
+            for k, (name, v) in enumerate((("mean", mean), ("stdev", stdev))):
+                t = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v), dtype=np.float64))
+                t = t.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+                if t.numel() != rows:
+                    raise ValueError("patch_statistics: %s has %d values, the featuregrams have %d rows" % (name, t.numel(), rows))
+                stats[k] = t
+        p_off = (C.c_longlong * (B + 1))()
+        total = _lib.check(self.lib.smh_scaled_patches_count(h_T, B, W, shift, p_off), "smh_scaled_patches_count")
+        out = torch.empty((max(int(total), 1), rows if axis == 1 else W), dtype=dtype, device=dev)
+        need = int(self.lib.smh_patch_statistics_workspace_bytes(B, rows, axis, int(mean is not None)))
+        work = torch.empty(need // 8, dtype=torch.float64, device=dev) if need else None
+        _lib.check(self.lib.smh_patch_statistics(self._h, h_fv, h_T, B, rows, _ptr(stats[0]), _ptr(stats[1]), W, shift,
+                                                 self._STATS[stat], axis, int(dtype == torch.float32), _ptr(out), _ptr(work), need,
+                                                 _stream()),
+                   "smh_patch_statistics")
+        return [out[int(p_off[b]):int(p_off[b + 1])] for b in range(B)]

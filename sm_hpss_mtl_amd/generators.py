@@ -28,6 +28,14 @@ them) instead of the per-file StandardScaler.  Device path: the ragged pass writ
 launch cuts the scaled patches of every file of the batch, cached ones included; per-file callables: the float64 scaling runs on the
 host between `featuregram_fn` and `patches_fn`.
 
+Skewness vectors (`PARAMS['skewness_vector']` = 'Row' / 'Col', Proposed_Work_Results.py:97-113, 475-481, 861-866; Lemaire_et_al models
+only): the network is fed ONE skewness vector per patch instead of the patch -- 'Row': tools.get_data_statistics(patches, axis=1), the
+skew of every feature row over the patch's W frames, (N, 1, 2F) for a model built with patch_size = 1; 'Col': axis=0, the skew of every
+frame over the rows, (N, W, 1) for a model built with N_MELS = 1.  Device path: the ragged pass writes featuregrams only and ONE
+`Frontend.patch_statistics` launch per batch takes the vectors of every file straight from them (with frame_level_scaling: under the
+fold's statistics); no patch is written.  Per-file callables: the reference's composition on the host.  A file yields as many vectors
+as it has patches, so batch composition, labels and the data-parallel row sharing are the same.
+
 `featuregram_fn` / `patches_fn` are injection points for tests (and for a CPU oracle): per-file callables with the
 signatures of `preproc.get_featuregram` / `preproc.get_feature_patches`.  When they are given, files are processed one
 by one through them, exactly like the reference's loop.
@@ -254,14 +262,54 @@ def _host_scaled(PARAMS, fv):
     return (fv.astype(np.float64) - mean[:, None]) / (stdev[:, None] + 1e-10)
 
 
+def skewness_mode(PARAMS):
+    """PARAMS['skewness_vector'] as None, 'Row' or 'Col'.  ValueError for any other value ('RowCol' included: the reference has no code
+    for it) and for a model that is not a Lemaire_et_al variant: the reference's (1, W, 1) / (2F, 1, 1) Conv2D input shapes do not
+    match the (N, 2F, 1) / (N, 1, W) data it would produce."""
+    v = PARAMS.get('skewness_vector')
+    if not v:
+        return None
+    if v not in ('Row', 'Col'):
+        raise ValueError("skewness_vector must be None, 'Row' or 'Col' (Proposed_Work_Results.py:97-113), got %r" % (v,))
+    if 'Lemaire_et_al' not in PARAMS['Model']:
+        raise ValueError("skewness_vector = %r feeds the Lemaire_et_al models only; PARAMS['Model'] = %r" % (v, PARAMS['Model']))
+    return v
+
+
+def _host_skewness_vectors(patches, mode):
+    """The reference's composition for the per-file callables: get_data_statistics(patches (nP, F, W), 'skew', axis) in float64 (the
+    mean, then the central moments of x - mean; a constant vector has skew 0) and np.expand_dims -> (nP, F, 1) for 'Row', (nP, 1, W)
+    for 'Col'; the Lemaire transpose that follows makes them (nP, 1, F) / (nP, W, 1)."""
+    x = np.asarray(patches, dtype=np.float64)
+    if x.ndim == 4 and x.shape[3] == 1:
+        x = x[..., 0]
+    if x.ndim != 3:
+        raise ValueError("skewness_vector: patches should be (nP, F, W), got %s" % (x.shape,))
+    ax = 2 if mode == 'Row' else 1  # get_data_statistics' axis 1 / 0 of every patch
+    d = x - x.mean(axis=ax, keepdims=True)
+    m2, m3 = (d ** 2).mean(axis=ax), (d ** 3).mean(axis=ax)
+    zero = m2 == 0
+    skew = np.where(zero, 0.0, m3 / np.where(zero, 1.0, m2) ** 1.5)
+    return np.expand_dims(skew, 2 if mode == 'Row' else 1)
+
+
 def _device_patches_for(PARAMS, specs, featName, n_fft, n_mels, W, shift):
     """The patches of the files `specs` as a list of float32 device tensors in the layout PARAMS['Model'] reads: (nP_i, W, 2F) for a
     Lemaire_et_al variant; (nP_i, 2F, W, 1) for any other -- the Conv2D models' images, get_feature_patches'
     np.expand_dims(patches, axis=3), Proposed_Work_Results.py:483-484 (a view: no copy).  The feature names without an H / P pair
     have F in place of 2F.  Standardised per file by the front end's own kernels (a cached featuregram: standardise + patches only);
     with PARAMS['frame_level_scaling'] the front end writes no patches and ONE `scaled_patches` launch scales every file of the
-    batch, cached ones included, with the fold's statistics."""
+    batch, cached ones included, with the fold's statistics.  With PARAMS['skewness_vector'] no patches either: ONE `patch_statistics`
+    launch, and the list holds the files' skewness vectors, (nP_i, 1, 2F) for 'Row' and (nP_i, W, 1) for 'Col' (views: no transpose)."""
     layout = "time_major" if 'Lemaire_et_al' in PARAMS['Model'] else "image"
+    mode = skewness_mode(PARAMS)
+    if mode:
+        fe, fvs, _ = _device_featuregrams_for(PARAMS, specs, featName, n_fft, n_mels)
+        if not fvs:
+            return []
+        mean, stdev = fold_statistics(PARAMS, fvs[0].shape[0]) if PARAMS.get('frame_level_scaling') else (None, None)
+        out = fe.patch_statistics(fvs, W, shift, axis=1 if mode == 'Row' else 0, stat="skew", mean=mean, stdev=stdev)
+        return [t.unsqueeze(1 if mode == 'Row' else 2) for t in out]
     if PARAMS.get('frame_level_scaling'):
         fe, fvs, _ = _device_featuregrams_for(PARAMS, specs, featName, n_fft, n_mels)
         out = []
@@ -393,7 +441,8 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
     the patches of a list of files as one batch) -- defaults: the integer contracts of libsmh and ONE ragged front-end pass.
 
     batchData: [batchSize music | batchSize speech | batchSize speech+music] patches, (3*batchSize, W, 2F) for the TCN
-    models, (.., 2F, W, 1) for the Conv2D ones (device path and injected per-file callables alike); labels: {'R', 'S', 'M', '3C'} for
+    models, (.., 2F, W, 1) for the Conv2D ones (device path and injected per-file callables alike); with PARAMS['skewness_vector'] one
+    skewness vector per patch instead, (.., 1, 2F) for 'Row' and (.., W, 1) for 'Col'; labels: {'R', 'S', 'M', '3C'} for
     the MTL models (the S = M = 0 rule for mixtures included, Proposed_Work_Results.py:249-260), else the one-hot matrix."""
     batch_count = 0
     np.random.shuffle(file_list['speech'])
@@ -410,9 +459,7 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
     n_mels = PARAMS['n_mels'][PARAMS['Model']]
     featName = PARAMS['featName'][PARAMS['Model']]
     W, W_shift = PARAMS['W'], PARAMS['W_shift']
-    if PARAMS.get('skewness_vector'):
-        raise ValueError("skewness_vector is off in every reference configuration of this path "
-                         "(Proposed_Work_Results.py:802-804) and is not wired into the generator")
+    skew_mode = skewness_mode(PARAMS)
     scaling = bool(PARAMS.get('frame_level_scaling'))
     if scaling:
         fold_statistics(PARAMS)  # the fold's statistics must be there before anything is computed
@@ -438,7 +485,8 @@ def generator(PARAMS, folder, file_list, batchSize, featuregram_fn=None, patches
         fv = featuregram_fn(PARAMS, classname, PARAMS['feature_opDir'], sp, mu, db, n_fft, n_mels, featName)
         if scaling:  # cscale_data between get_featuregram and get_feature_patches (Baseline_Results.py:91-93)
             fv = _host_scaled(PARAMS, fv)
-        return patches_fn(PARAMS, fv, W, W_shift, featName)
+        patches = patches_fn(PARAMS, fv, W, W_shift, featName)
+        return _host_skewness_vectors(patches, skew_mode) if skew_mode else patches  # Proposed_Work_Results.py:97-113
 
     def fill(classname, next_spec):
         """Pop files until the class queue holds a batch (the reference's `while balance < batchSize` loops).  With the per-file
@@ -565,6 +613,8 @@ def fusion_generator(PARAMS, folder, file_list, batchSize, **kwargs):
     model = PARAMS['Model']
     if 'MTL' not in model:
         raise ValueError("fusion_generator: the intermediate-fusion model is an MTL model (PARAMS['Model'] = %r)" % (model,))
+    if PARAMS.get('skewness_vector'):
+        raise ValueError("skewness_vector is not wired into the fusion generator")
     inner = dict(PARAMS)
     inner['featName'] = dict(PARAMS['featName'])
     inner['featName'][model] = harm_perc_sibling(PARAMS['featName'][model])
@@ -586,12 +636,12 @@ def fusion_generator(PARAMS, folder, file_list, batchSize, **kwargs):
 def test_file_wise_generator(PARAMS, file_name_sp, file_name_mu, target_dB, featuregram_fn=None, patches_fn=None):
     """All patches of ONE test file + their one-hot labels (Proposed_Work_Results.py:459-496).  The patch shift is the
     reference's hard-coded 68, not PARAMS['W_shift'].  Device path: float32 tensor (nP, W, 2F) for the TCN models, (nP, 2F, W, 1)
-    for the Conv2D ones; with the per-file callables injected: what they return, transposed to (nP, W, F) for the TCN models."""
+    for the Conv2D ones; with the per-file callables injected: what they return, transposed to (nP, W, F) for the TCN models.  With
+    PARAMS['skewness_vector']: the patches' skewness vectors, (nP, 1, 2F) for 'Row' and (nP, W, 1) for 'Col'."""
     n_fft = PARAMS['n_fft'][PARAMS['Model']]
     n_mels = PARAMS['n_mels'][PARAMS['Model']]
     featName = PARAMS['featName'][PARAMS['Model']]
-    if PARAMS.get('skewness_vector'):
-        raise ValueError("skewness_vector is not wired into this path")
+    skew_mode = skewness_mode(PARAMS)
     scaling = bool(PARAMS.get('frame_level_scaling'))
     if scaling:
         fold_statistics(PARAMS)
@@ -608,6 +658,8 @@ def test_file_wise_generator(PARAMS, file_name_sp, file_name_mu, target_dB, feat
         if scaling:  # Baseline_Results.py:343-344
             fv = _host_scaled(PARAMS, fv)
         batchData = (patches_fn or pp.get_feature_patches)(PARAMS, fv, PARAMS['W'], HARDCODED_TEST_SHIFT, featName)
+        if skew_mode:  # Proposed_Work_Results.py:475-481
+            batchData = _host_skewness_vectors(batchData, skew_mode)
         if 'Lemaire_et_al' in PARAMS['Model']:
             batchData = np.transpose(batchData, axes=(0, 2, 1))
     else:
