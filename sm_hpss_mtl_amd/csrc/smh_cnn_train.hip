@@ -20,6 +20,7 @@
 // kernels only (optimiser segment kind 4).
 #include "smh_cnn_impl.h"
 #include "smh_model.h"
+#include "smh_train_plan.h"
 
 namespace {
 
@@ -938,14 +939,16 @@ int train_heads(smh_cnn_trainer *t, const float *feat, const float *d_y, int N, 
         ha.hp_off[h] = m->tensors[th + 2].off;  // gamma, beta, mean, var, out kernel, out bias: contiguous in the table
     }
     ha.goff_c3b = hp.c3b;
+    const smh_tcn::TrainSwitches hsw = smh_tcn::read_train_switches();  // (SMH_HEADS_GLOBAL, SMH_HEADS_STAMPS: the TCN models' heads kernel)
+    ha.stamps = hsw.heads_stamps;
     hipLaunchKernelGGL(heads_pre_kernel, dim3(N), dim3(256), 0, st, feat, F, hp, t->d_pre);
     int rc = smh::launch_status("heads_pre_kernel");
     if (rc) return rc;
     if (m->n_heads == 0)  // single-task: softmax, the two-output bce or the categorical loss, accuracy, d loss / d logits
         rc = smh_tcn::launch_single_head_train(ha, t->d_pre, d_y, t->d_dpre, t->d_grad, d_losses, st);
     else
-        rc = smh_tcn::launch_heads_train(ha, t->d_pre, d_y, F, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad,
-                                         t->d_bstat + t->head_bstat, d_losses,
+        rc = smh_tcn::launch_heads_train(ha, smh_tcn::plan_heads(SMH_HEADS_MTL, ha.n_classes, ha.n_heads, ha.out_dim, N, hsw), t->d_pre, d_y,
+                                         F, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bstat + t->head_bstat, d_losses,
                                          reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
     if (rc) return rc;
     hipLaunchKernelGGL(l2_partial_kernel, dim3(t->nseg), dim3(256), 0, st, (const Seg *)t->d_segs, F, t->d_l2part);

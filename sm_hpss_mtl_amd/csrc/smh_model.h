@@ -84,13 +84,16 @@ struct HeadsArgs {
     int ext_losses;               // 1: `losses` has 3 n_heads + 4 floats and gets the per-head binary accuracies at [2 nh + 4 + h]
     int stamps;                   // tools only (SMH_HEADS_STAMPS): thread 0 prints the phase durations (100 MHz ticks)
 };
+// p: the kernel form, grid and LDS of this batch (smh_train_plan.h: plan_heads), which the heads launchers execute.
 // ticket: one zero-initialised device word the kernel's workgroups count themselves on (left at zero again)
-int launch_heads_train(const HeadsArgs &a, const float *pre, const float *y, const float *hp, const float *drop, float *dpre,
-                       float *dxh, float *grad, float *bnstat, float *losses, unsigned *ticket, hipStream_t st);
+struct HeadsPlan;
+int launch_heads_train(const HeadsArgs &a, const HeadsPlan &p, const float *pre, const float *y, const float *hp, const float *drop,
+                       float *dpre, float *dxh, float *grad, float *bnstat, float *losses, unsigned *ticket, hipStream_t st);
 // The same for the cascaded heads (smh_train_cascade.hip; a.n_heads = 3: S, M, R[2]).  dr: (2, N, 2) scratch for d loss / d r of
 // S and M; bnstat also receives the BN18 batch statistics of S and M at kMaxHeads * 32 + h * 2 * kCat (means, then variances).
-int launch_cascade_heads_train(const HeadsArgs &a, const float *pre, const float *y, const float *hp, const float *drop,
-                               float *dpre, float *dxh, float *dr, float *grad, float *bnstat, float *losses, hipStream_t st);
+int launch_cascade_heads_train(const HeadsArgs &a, const HeadsPlan &p, const float *pre, const float *y, const float *hp,
+                               const float *drop, float *dpre, float *dxh, float *dr, float *grad, float *bnstat, float *losses,
+                               hipStream_t st);
 // The head of the single-task baseline (smh_train_single.hip; a.n_heads = 0): softmax, the loss (binary cross-entropy over the two
 // outputs for n_classes == 2, else categorical cross-entropy), the accuracy, d loss / d logits (-> dpre) and the Dense bias gradient.
 // losses: [loss, lw[0] * loss, accuracy, 0]
@@ -185,7 +188,6 @@ int dense_entry_ok(const char *name, const smh_model *m, const float *d_fv, int 
                    size_t need_bytes, const float *d_out, int feat_multiple, const char *short_clip_entry);
 int repack(smh_model *m, hipStream_t st);  // d_flat -> packed operand buffers
 int launch_forward_bf16_train(smh_model *m, const float *d_x, int N, const TrainIO *tio, hipStream_t st);  // smh_tcn_bf16.hip
-bool backward_bf16_supported(int T, int n_dil);  // smh_train_bf16.hip: the patch geometry fits the split-bf16 backward's LDS plan
 int forward_bf16_supported(const smh_model *m);  // smh_tcn_bf16.hip: SMH_OK, or why the split-bf16 training forward refuses m
 // what launch_forward reads and where it ends (the TcnArgs members of the same names); the defaults: patches in, heads out
 struct ForwardOpts {

@@ -19,6 +19,7 @@
 
 #include "smh_model.h"
 #include "smh_train_bwd.h"
+#include "smh_train_plan.h"
 #include "smh_wave.h"
 
 using namespace smh_tcn;
@@ -28,9 +29,10 @@ namespace {
 constexpr float kKerasEps = 1e-7f;
 constexpr float kBnMomentum = 0.99f;
 constexpr float kL2 = 0.01f;
-constexpr int kBG = 1;        // patches per workgroup in the backward kernel
-constexpr int kBS = 33;       // LDS row stride (floats) of the backward buffers
-constexpr int kBThreads = 1024;
+// smh_train_plan.h restates these for its HIP-free arithmetic
+static_assert(Dims::C == C && Dims::SX == SX && Dims::PS == kPS && Dims::Hidden == kHidden && Dims::MaxHeads == kMaxHeads &&
+                  Dims::LdsPerCU == (size_t)smh::kLdsBytesPerCU && Dims::NetLdsLimit == kNetLdsLimit,
+              "smh_train_plan.h: Dims");
 
 using smh_tcn::HeadsArgs;
 
@@ -559,13 +561,7 @@ tcn_backward_kernel(BwdArgs a, const float *__restrict__ X, const float *__restr
 // A operands come from LDS copies of the block's canonical kernels (rows = the lane's channel, stride kWS).
 // The Dense-on-trunk weight gradient (a rank-N update of a D x 51 matrix) is its own kernel without atomics.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int kMG = 1;
-constexpr int kWS = 36;  // row stride of the weight copies in LDS (tcn_backward_mfma_kernel)
-constexpr int kMThreads = 512;
-constexpr int kZW = 3 * SX + 4;  // zero words behind the images (tile_jobs)
-constexpr int kMfmaMaxT = 128;   // two float4 of saved activations per thread in the register prefetch
-constexpr int kMfmaLongT = 256;  // four; kernels read from global memory (no LDS left)
-
+// (kMG, kWS, kMThreads, kZW, kMfmaMaxT, kMfmaLongT: smh_train_plan.h)
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -983,12 +979,12 @@ tcn_backward_mfma_kernel(BwdArgs a, const float *__restrict__ X, const float *__
 // tools / tests: workgroups of the MFMA backward kernel (T <= 128 instantiation) that fit one CU at patch size T -- two at the
 // reference's T = 68 (126 VGPRs, 79 KB of LDS); one register class more and it is one, 345 -> 445 us per 510-patch step
 extern "C" int smh_internal_bwd_residency(int T) {
-    const int RPm = ((kMG * T + 15) / 16) * 16;
-    const size_t lds_m = sizeof(float) * ((size_t)4 * RPm * SX + 4 * C * kWS + kMG * kPS + C + kZW);
+    const MfmaPlan p = plan_mfma(T);
+    if (p.route != kBwdMfmaShort) return -1;  // (beyond kMfmaMaxT frames the step does not launch this instantiation)
     auto kern = tcn_backward_mfma_kernel<true, kMfmaMaxT>;
-    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m) != hipSuccess) return -1;
+    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) return -1;
     int nb = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, kMThreads, lds_m) != hipSuccess) return -1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, kMThreads, p.lds) != hipSuccess) return -1;
     return nb;
 }
 
@@ -997,7 +993,6 @@ namespace {
 // dWh[k][o] = sum_b relu(x_b)[k] dpre[b][o] for the '3C' kernel (grid.z = 0) and the Dense(16) kernel of every head
 // (grid.z = 1 + h): one thread per element (k, o), o fastest, so the float atomics that combine the batch slices
 // (grid.y, kDwhSlice patches each) hit contiguous addresses -- one lane per row of the matrix was 17x slower.
-constexpr int kDwhSlice = 16;
 __global__ void dwh_kernel(BwdArgs a, const float *__restrict__ acts, const float *__restrict__ dpre,
                            float *__restrict__ grad, int slice) {
     const int grp = blockIdx.z;
@@ -1021,7 +1016,6 @@ __global__ void dwh_kernel(BwdArgs a, const float *__restrict__ acts, const floa
 // A[i = k][kk = patch] are 64-byte runs of the saved trunk, B[kk = patch][j = output] 64-byte runs of dpre; eight product steps
 // (32 patches) per iteration with their sixteen loads in flight together; batch slices combined by float atomics as above.
 // 36 us -> see DESIGN 7 (the one-thread-per-element kernel is a dependent chain of N / slice loads + FMAs per thread).
-constexpr int kDwhSplit = 8;  // batch slices (grid.z)
 __global__ void __launch_bounds__(256) dwh_mfma_kernel(BwdArgs a, const float *__restrict__ acts, const float *__restrict__ dpre,
                                                        float *__restrict__ grad) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1179,32 +1173,21 @@ __global__ void seg_opt_kernel(const Segment *__restrict__ segs, OptArgs o, floa
 
 }  // namespace
 
-int smh_tcn::launch_heads_train(const HeadsArgs &a, const float *pre, const float *y, const float *hp, const float *drop,
-                                float *dpre, float *dxh, float *grad, float *bnstat, float *losses, unsigned *ticket,
-                                hipStream_t st) {
-    HeadsArgs ad = a;
-    ad.stamps = getenv("SMH_HEADS_STAMPS") ? 1 : 0;
-    const int NHc = a.n_classes + a.n_heads * kHidden;
-    const size_t lds = sizeof(float) * ((size_t)a.N * (NHc | 1) + (size_t)a.N * (a.out_dim | 1));
-    // 160 KB of LDS per CU minus the kernel's static 37 KB (per-wave accumulator rows): 3-class batches up to 538 patches, 5-class
-    // up to 390 (232 and 320 bytes per patch; tests/heads_plans.py restates this, tests/test_heads_plans.py pins it)
-    const bool staged = lds <= 122 * 1024 && !getenv("SMH_HEADS_GLOBAL");
-#define SMH_LAUNCH_HEADS(ST, TH)                                                                                        \
-    do {                                                                                                                \
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)heads_train_kernel<ST, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                          (int)(ST ? lds : 0)));                                                        \
-        hipLaunchKernelGGL((heads_train_kernel<ST, TH>), dim3(a.n_heads + 1), dim3(TH), ST ? lds : 0, st, ad, pre, y, hp, drop, \
-                           dpre, dxh, grad, bnstat, losses, ticket);                                                    \
-    } while (0)
-    if (a.N <= 512) {
-        if (staged) SMH_LAUNCH_HEADS(true, 512);
-        else SMH_LAUNCH_HEADS(false, 512);
-    } else {
-        if (staged) SMH_LAUNCH_HEADS(true, 1024);
-        else SMH_LAUNCH_HEADS(false, 1024);
-    }
-#undef SMH_LAUNCH_HEADS
-    return smh::launch_status("heads_train_kernel");
+// the staged tile beside heads_train_kernel's static arrays (smh_train_plan.h: kHeadsStageBytes)
+static_assert(sizeof(float) * (17 * kQ + 2 * 64) + sizeof(unsigned long long) * 64 + kHeadsStageBytes <= (size_t)smh::kLdsBytesPerCU,
+              "heads_train_kernel: static and staged LDS together exceed the CU");
+
+static auto pick_heads_kernel(bool staged, int threads) {
+    if (threads == 512) return staged ? heads_train_kernel<true, 512> : heads_train_kernel<false, 512>;
+    return staged ? heads_train_kernel<true, 1024> : heads_train_kernel<false, 1024>;
+}
+
+int smh_tcn::launch_heads_train(const HeadsArgs &a, const HeadsPlan &p, const float *pre, const float *y, const float *hp,
+                                const float *drop, float *dpre, float *dxh, float *grad, float *bnstat, float *losses,
+                                unsigned *ticket, hipStream_t st) {
+    const HeadsLaunch &k = p.k[0];
+    return smh::launch_lds(pick_heads_kernel(k.staged, k.threads), "heads_train_kernel", dim3(k.grid), dim3(k.threads), k.lds, k.lds,
+                           st, a, pre, y, hp, drop, dpre, dxh, grad, bnstat, losses, ticket);
 }
 
 struct smh_trainer {
@@ -1379,29 +1362,7 @@ extern "C" int smh_trainer_set_dtype(smh_trainer *t, int dtype) {
     return SMH_OK;
 }
 
-// The implementation switches of the training step (A/B and tests), one getenv each.  Read at the top of every step rather than
-// once in smh_trainer_create: tests flip SMH_BWD_BF16 and SMH_BWD_SPLIT between the steps of one trainer.
-struct StepSwitches {
-    bool valu;      // SMH_TRAIN_VALU set: the scalar backward kernel (tcn_backward_kernel)
-    bool bf16_bwd;  // SMH_BWD_BF16, default on: dtype 1's split-bf16 backward (0: the exact-f32 backward behind the bf16 forward)
-    int split3;     // SMH_BWD_SPLIT, default 1: BwdArgs::split3
-    int stamps;     // SMH_BWD_STAMPS set: BwdArgs::stamps
-    bool dwh_valu;  // SMH_DWH_VALU set: dwh_kernel instead of dwh_mfma_kernel
-};
-
-static StepSwitches read_switches() {
-    StepSwitches s;
-    s.valu = getenv("SMH_TRAIN_VALU") != nullptr;
-    const char *ev = getenv("SMH_BWD_BF16");
-    s.bf16_bwd = !(ev && atoi(ev) == 0);
-    ev = getenv("SMH_BWD_SPLIT");
-    s.split3 = ev ? atoi(ev) != 0 : 1;
-    s.stamps = getenv("SMH_BWD_STAMPS") ? 1 : 0;
-    s.dwh_valu = getenv("SMH_DWH_VALU") != nullptr;
-    return s;
-}
-
-static HeadsArgs heads_args(const smh_model *m, const Offsets &off, int N, const float *h_loss_weights) {
+static HeadsArgs heads_args(const smh_model *m, const Offsets &off, int N, const float *h_loss_weights, int stamps) {
     HeadsArgs ha;
     ha.N = N, ha.D = m->D, ha.NH = m->NH, ha.n_classes = m->cfg.n_classes, ha.n_heads = m->n_heads, ha.out_dim = m->out_dim;
     for (int i = 0; i < kMaxHeads; ++i) {
@@ -1413,6 +1374,7 @@ static HeadsArgs heads_args(const smh_model *m, const Offsets &off, int N, const
         for (int i = 0; i <= m->n_heads; ++i) ha.lw[i] = h_loss_weights[i];
     ha.goff_c3b = off.c3_b;
     ha.ext_losses = 1;
+    ha.stamps = stamps;
     size_t hpo = 0;
     for (int i = 0; i < m->n_heads; ++i) {  // d_hp: per head [gamma, beta, mean, var, (cat BN,) out kernel, out bias], packed
         ha.hp_off[i] = hpo;
@@ -1421,154 +1383,162 @@ static HeadsArgs heads_args(const smh_model *m, const Offsets &off, int N, const
     return ha;
 }
 
-static BwdArgs bwd_args(const smh_trainer *t, const Offsets &off, int N, int split3, int stamps) {
+static BwdArgs bwd_args(const smh_trainer *t, const Offsets &off, int N, int split3, int stamps, int use_wt) {
     const smh_model *m = t->m;
     BwdArgs ba;
     ba.gq = t->d_gq;  // nullptr unless smh_trainer_set_deterministic(t, 1)
     ba.split3 = split3;
     ba.N = N, ba.T = m->cfg.patch_size, ba.F = m->cfg.n_feat, ba.n_blocks = m->n_blocks, ba.n_dil = m->cfg.n_dilations;
-    ba.use_wt = 1;
+    ba.use_wt = use_wt;
     ba.stamps = stamps;
     ba.D = m->D, ba.NH = m->NH, ba.n_classes = m->cfg.n_classes, ba.n_heads = m->n_heads, ba.off = off;
     return ba;
 }
 
-// LDS plan of the f32 MFMA trunk backward at patch length T: the short form parks the block kernels in LDS, the long one reads them
-// from the weight vector
-struct MfmaPlan {
-    int RPm;
-    size_t lds_m, lds_long;
-    bool short_ok, long_ok;
-};
+// The step's plan (smh_train_plan.h) for this model, and SMH_OK or the refusal of a patch too long for every backward kernel -- asked
+// by train_step before it launches anything, and by the test query
+static TrainPlan train_plan(const smh_model *m, int N, int dtype, const TrainSwitches &sw) {
+    return plan_train(TrainShape{m->heads, m->cfg.patch_size, m->n_blocks, m->cfg.n_classes, m->n_heads, m->out_dim}, N, dtype, sw);
+}
+static int train_plan_status(const smh_model *m, const TrainPlan &p) {
+    if (m->heads == SMH_HEADS_FUSION)
+        SMH_REQUIRE(p.backward.route != kBwdRefused,
+                    "smh_fusion_train_step_f32: patch_size %d too long for the trunk backward (at most %d frames)", m->cfg.patch_size,
+                    kMfmaLongT);
+    SMH_REQUIRE(p.backward.route != kBwdRefused, "patch_size %d too long for the backward kernel (at most 264 frames)",
+                m->cfg.patch_size);
+    return SMH_OK;
+}
 
-static MfmaPlan mfma_plan(int T) {
-    MfmaPlan p;
-    p.RPm = ((kMG * T + 15) / 16) * 16;
-    p.lds_m = sizeof(float) * ((size_t)4 * p.RPm * SX + 4 * C * kWS + kMG * kPS + C + kZW);
-    p.lds_long = sizeof(float) * ((size_t)4 * p.RPm * SX + kMG * kPS + C + kZW);  // kernels stay in global memory
-    p.short_ok = p.lds_m <= kNetLdsLimit && T <= kMfmaMaxT, p.long_ok = p.lds_long <= kNetLdsLimit && T <= kMfmaLongT;
-    return p;
+// what one step is called with.  x: the trunk inputs, one (B3_MTL, cascaded, single-task) or two (intermediate fusion: trunk H, then P)
+struct StepIO {
+    const float *const *x;
+    int nx;
+    const float *d_y;
+    int N;
+    const float *d_drop_tcn, *d_drop_heads, *h_loss_weights;
+    float *d_losses;
+    hipStream_t st;
+};
+// trunk b's own part of the saved activations, the gates and the dropout masks
+struct TrunkBufs {
+    float *acts, *upre;
+    const float *drop;
+};
+static TrunkBufs trunk_bufs(const smh_trainer *t, const StepIO &io, int b) {
+    const smh_model *m = t->m;
+    const size_t half = (size_t)m->cfg.patch_size * C;
+    const size_t nact = (size_t)t->max_batch * (m->n_blocks + 1) * half, nupre = (size_t)t->max_batch * m->n_blocks * half;
+    const size_t ndrop = (size_t)io.N * m->n_blocks * C;
+    return TrunkBufs{t->d_acts + b * nact, t->d_upre + b * nupre, io.d_drop_tcn ? io.d_drop_tcn + b * ndrop : nullptr};
+}
+
+// The training forward of every trunk.  dtype 1: on the bf16 matrix pipe (split operands: f32-grade products, smh_tcn_bf16.hip); it
+// saves the same activations and gates in f32 -- all of them unless the bf16 backward follows, which rebuilds every block's input.
+// The fusion model's trunk forwards are the B3_MTL forward kernel, trunk only; its Dense layers and the fused BatchNorm
+// (smh_fusion.hip, phase 0) follow.
+static int train_forward(smh_trainer *t, const StepIO &io, const TrainPlan &p) {
+    smh_model *m = t->m;
+    ForwardOpts fo;
+    fo.trunk_only = p.forward == kTrainForwardTrunkPair;
+    for (int b = 0; b < io.nx; ++b) {
+        const TrunkBufs tb = trunk_bufs(t, io, b);
+        TrainIO tio{tb.acts, tb.drop, t->d_pre, tb.upre, p.backward.acts_last_only};
+        const int rc = p.forward == kTrainForwardBf16
+                           ? launch_forward_bf16_train(m, io.x[b], io.N, &tio, io.st)
+                           : launch_forward(fo.trunk_only ? m->trunk[b] : m, io.x[b], io.N, t->d_scratch_out, nullptr, &tio, io.st, fo);
+        if (rc) return rc;
+    }
+    if (p.forward != kTrainForwardTrunkPair) return SMH_OK;
+    return launch_fusion_train(m, io.N, t->max_batch, t->d_acts, trunk_bufs(t, io, 1).acts, t->d_fusion, t->d_bnstat + kBnStatFloats,
+                               t->d_pre, t->d_grad, 0, io.st);
+}
+
+// The heads of the model's kind (losses, d loss / d pre), the l2 penalty of the regularised kernels, and the fusion model's phase 1
+// (its Dense and BatchNorm gradients, d loss / d trunk output of both trunks)
+static int train_heads(smh_trainer *t, const StepIO &io, const TrainPlan &p, const HeadsArgs &ha, const BwdArgs &ba) {
+    smh_model *m = t->m;
+    int rc;
+    if (p.heads.family == kHeadsFamilySingle)  // no heads: heads_train_kernel's grid of n_heads + 1 workgroups has nothing to run here
+        rc = launch_single_head_train(ha, t->d_pre, io.d_y, t->d_dpre, t->d_grad, io.d_losses, io.st);
+    else if (p.heads.family == kHeadsFamilyCascaded)
+        rc = launch_cascade_heads_train(ha, p.heads, t->d_pre, io.d_y, m->d_hp, io.d_drop_heads, t->d_dpre, t->d_dxh, t->d_dr, t->d_grad,
+                                        t->d_bnstat, io.d_losses, io.st);
+    else
+        rc = launch_heads_train(ha, p.heads, t->d_pre, io.d_y, m->d_hp, io.d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bnstat,
+                                io.d_losses, reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), io.st);
+    if (rc) return rc;
+    if (m->n_heads > 0) {  // (a model without heads has no regularised kernel: its head kernel wrote the zero penalty itself)
+        hipLaunchKernelGGL(l2_penalty_kernel, dim3(m->n_heads * kL2Chunks), dim3(256), 0, io.st, ba, m->d_flat,
+                           io.d_losses + m->n_heads + 3, t->d_l2part, reinterpret_cast<unsigned *>(t->d_l2part + kMaxHeads * kL2Chunks));
+        rc = smh::launch_status("l2_penalty_kernel");
+        if (rc) return rc;
+    }
+    if (p.forward != kTrainForwardTrunkPair) return SMH_OK;
+    return launch_fusion_train(m, io.N, t->max_batch, t->d_acts, trunk_bufs(t, io, 1).acts, t->d_fusion, t->d_bnstat + kBnStatFloats,
+                               t->d_dpre, t->d_grad, 1, io.st);
 }
 
 // the f32 MFMA backward of one trunk (input x, its saved acts / upre / dropout masks), fed with gt = d loss / d (trunk output);
 // a.off: where that trunk's weights are in the flat weights and gradient
-static int launch_backward_mfma(const smh_trainer *t, const BwdArgs &a, const float *x, const float *acts, const float *drop,
-                                const float *upre, const float *gt, hipStream_t st) {
-    const MfmaPlan p = mfma_plan(a.T);
-    const dim3 grid((a.N + kMG - 1) / kMG);
-    if (p.short_ok) {
-        auto kern = tcn_backward_mfma_kernel<true, kMfmaMaxT>;
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_m));
-        hipLaunchKernelGGL(kern, grid, dim3(kMThreads), p.lds_m, st, a, x, t->m->d_flat, acts, drop, t->d_dpre, t->d_grad, p.RPm,
-                           upre, gt);
-    } else {
-        auto kern = tcn_backward_mfma_kernel<false, kMfmaLongT>;
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_long));
-        hipLaunchKernelGGL(kern, grid, dim3(kMThreads), p.lds_long, st, a, x, t->m->d_flat, acts, drop, t->d_dpre, t->d_grad, p.RPm,
-                           upre, gt);
-    }
-    return smh::launch_status("tcn_backward_mfma_kernel");
+static int launch_backward_mfma(const smh_trainer *t, const BwdArgs &a, const BackwardPlan &p, const float *x, const TrunkBufs &tb,
+                                const float *gt, hipStream_t st) {
+    auto kern = p.route == kBwdMfmaShort ? tcn_backward_mfma_kernel<true, kMfmaMaxT> : tcn_backward_mfma_kernel<false, kMfmaLongT>;
+    return smh::launch_lds(kern, "tcn_backward_mfma_kernel", dim3(p.grid), dim3(p.threads), p.lds, p.lds, st, a, x, t->m->d_flat, tb.acts,
+                           tb.drop, t->d_dpre, t->d_grad, p.RPm, tb.upre, gt);
 }
 
-// One training step of a TCN model, after the entry point's checks.  x: the trunk inputs, one (B3_MTL, cascaded) or two (intermediate
-// fusion: trunk H, then trunk P; trunk b has its own part b of the saved activations, the gates and the dropout masks).  The fusion
-// model's trunk forwards are the B3_MTL forward kernel, trunk only; its Dense layers and the fused BatchNorm run in smh_fusion.hip,
-// which also hands each trunk backward its d loss / d (trunk output).
-static int train_step(smh_trainer *t, const float *const *x, int nx, const float *d_y, int N, const float *d_drop_tcn,
-                      const float *d_drop_heads, const float *h_loss_weights, float *d_losses, hipStream_t st) {
-    const StepSwitches sw = read_switches();
-    smh_model *m = t->m;
-    const bool fusion = nx == 2;
-    const int half = m->cfg.patch_size * C;
-    const size_t nact = (size_t)t->max_batch * (m->n_blocks + 1) * half, nupre = (size_t)t->max_batch * m->n_blocks * half;
-    const size_t ndrop = (size_t)N * m->n_blocks * C;
-    const auto drop = [&](int b) { return d_drop_tcn ? d_drop_tcn + b * ndrop : nullptr; };
-    SMH_CHECK_HIP(hipMemsetAsync(t->d_grad, 0, m->n_params * sizeof(float), st));
-    // dtype 1: the residual blocks' backward on the bf16 matrix pipe (smh_train_bf16.hip); patch geometries outside its LDS plan, and
-    // SMH_BWD_BF16=0 (A/B and tests), keep the exact-f32 kernel behind the bf16 forward -- which then has to save every block's input
-    const bool bf16_bwd = t->dtype == 1 && !sw.valu && sw.bf16_bwd && backward_bf16_supported(m->cfg.patch_size, m->cfg.n_dilations);
-    ForwardOpts fo;
-    fo.trunk_only = fusion;
-    for (int b = 0; b < nx; ++b) {
-        TrainIO tio{t->d_acts + b * nact, drop(b), t->d_pre, t->d_upre + b * nupre, bf16_bwd ? 1 : 0};
-        // dtype 1: the training forward on the bf16 matrix pipe (split operands: f32-grade products, smh_tcn_bf16.hip); it saves the
-        // same activations and gates in f32, so the backward pass below is unchanged
-        const int rc = t->dtype == 1 ? launch_forward_bf16_train(m, x[b], N, &tio, st)
-                                     : launch_forward(fusion ? m->trunk[b] : m, x[b], N, t->d_scratch_out, nullptr, &tio, st, fo);
-        if (rc) return rc;
-    }
-    int rc = fusion ? launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats,
-                                          t->d_pre, t->d_grad, 0, st)
-                    : SMH_OK;
-    if (rc) return rc;
-    const Offsets off = offsets(m);
-    const HeadsArgs ha = heads_args(m, off, N, h_loss_weights);
-    if (m->heads == SMH_HEADS_SINGLE)  // no heads: heads_train_kernel's grid of n_heads + 1 workgroups has nothing to run here
-        rc = launch_single_head_train(ha, t->d_pre, d_y, t->d_dpre, t->d_grad, d_losses, st);
-    else if (m->heads == SMH_HEADS_CASCADED)
-        rc = launch_cascade_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_dr, t->d_grad,
-                                        t->d_bnstat, d_losses, st);
-    else
-        rc = launch_heads_train(ha, t->d_pre, d_y, m->d_hp, d_drop_heads, t->d_dpre, t->d_dxh, t->d_grad, t->d_bnstat, d_losses,
-                                reinterpret_cast<unsigned *>(t->d_dxh + (size_t)t->max_batch * kPS), st);
-    if (rc) return rc;
-    BwdArgs ba = bwd_args(t, off, N, sw.split3, fusion ? 0 : sw.stamps);
-    if (m->n_heads > 0) {  // (a model without heads has no regularised kernel: its head kernel wrote the zero penalty itself)
-        hipLaunchKernelGGL(l2_penalty_kernel, dim3(m->n_heads * kL2Chunks), dim3(256), 0, st, ba, m->d_flat, d_losses + m->n_heads + 3,
-                           t->d_l2part, reinterpret_cast<unsigned *>(t->d_l2part + kMaxHeads * kL2Chunks));
-        rc = smh::launch_status("l2_penalty_kernel");
-        if (rc) return rc;
-    }
-    if (fusion) {
-        rc = launch_fusion_train(m, N, t->max_batch, t->d_acts, t->d_acts + nact, t->d_fusion, t->d_bnstat + kBnStatFloats, t->d_dpre,
-                                 t->d_grad, 1, st);
-        if (rc) return rc;
-    }
-    // the trunk backward of each trunk.  The bf16 and the MFMA backward of a one-input model leave the gradient of the Dense layers
-    // on the trunk to dwh_*_kernel; the scalar kernel computes it itself, the fusion model's Dense layers are smh_fusion.hip's.
-    const MfmaPlan plan = mfma_plan(ba.T);
-    bool dwh = false;
-    if (fusion) {
+// The trunk backward of each trunk on the plan's route, then the gradient of the Dense layers on the trunk where the route leaves
+// it to dwh_*_kernel (the scalar kernel computes it itself, the fusion model's Dense layers are smh_fusion.hip's)
+static int train_backward(smh_trainer *t, const StepIO &io, const TrainPlan &tp, const BwdArgs &ba) {
+    const smh_model *m = t->m;
+    const BackwardPlan &p = tp.backward;
+    const TrunkBufs tb = trunk_bufs(t, io, 0);
+    int rc = SMH_OK;
+    if (tp.forward == kTrainForwardTrunkPair) {
         for (int b = 0; b < 2 && !rc; ++b) {
             BwdArgs bb = ba;
-            bb.D = half;
-            if (b == 1) bb.off.w0_k += off.trunk_p, bb.off.w0_b += off.trunk_p, bb.off.blk0 += off.trunk_p;
-            rc = launch_backward_mfma(t, bb, x[b], t->d_acts + b * nact, drop(b), t->d_upre + b * nupre,
-                                      fusion_gt(m, t->max_batch, t->d_fusion, N, b), st);
+            bb.D = m->cfg.patch_size * C;
+            if (b == 1) bb.off.w0_k += ba.off.trunk_p, bb.off.w0_b += ba.off.trunk_p, bb.off.blk0 += ba.off.trunk_p;
+            rc = launch_backward_mfma(t, bb, p, io.x[b], trunk_bufs(t, io, b), fusion_gt(m, t->max_batch, t->d_fusion, io.N, b), io.st);
         }
-    } else if (bf16_bwd) {
-        rc = launch_backward_bf16(ba, &t->d_bwd_pack, &t->bwd_pack_cap, x[0], m->d_flat, t->d_acts, d_drop_tcn, t->d_dpre, t->d_grad,
-                                  (const float *)t->d_upre, st);
-        dwh = true;
-    } else if ((plan.short_ok || plan.long_ok) && !sw.valu) {  // the MFMA backward (default); SMH_TRAIN_VALU keeps the scalar kernel
-        if (!t->d_gt) SMH_CHECK_HIP(hipMalloc((void **)&t->d_gt, (size_t)t->max_batch * ba.D * sizeof(float)));
-        rc = launch_dtrunk(ba, m->d_flat, t->d_acts, t->d_dpre, t->d_gt, st);
-        if (!rc) rc = launch_backward_mfma(t, ba, x[0], t->d_acts, d_drop_tcn, t->d_upre, t->d_gt, st);
-        dwh = true;
-    } else {
-        const int RP = kBG * ba.T;
-        size_t lds = sizeof(float) * ((size_t)4 * RP * kBS + 2 * (3 * C * C + C * C) + C + 3 * RP + kBG * kPS);
-        if (lds > kNetLdsLimit) {  // long patches (the reference's W = 249): no room for the transposed kernel copies
-            ba.use_wt = 0;
-            lds -= sizeof(float) * (3 * C * C + C * C);
-        }
-        SMH_REQUIRE(lds <= kNetLdsLimit, "patch_size %d too long for the backward kernel (at most 264 frames)", ba.T);
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)tcn_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(tcn_backward_kernel, dim3((N + kBG - 1) / kBG), dim3(kBThreads), lds, st, ba, x[0], m->d_flat, t->d_acts,
-                           d_drop_tcn, t->d_dpre, t->d_grad);
-        rc = smh::launch_status("tcn_backward_kernel");
+    } else if (p.route == kBwdBf16) {
+        rc = launch_backward_bf16(ba, p, &t->d_bwd_pack, &t->bwd_pack_cap, io.x[0], m->d_flat, tb.acts, tb.drop, t->d_dpre, t->d_grad,
+                                  (const float *)tb.upre, io.st);
+    } else if (p.route == kBwdScalar) {
+        rc = smh::launch_lds(tcn_backward_kernel, "tcn_backward_kernel", dim3(p.grid), dim3(p.threads), p.lds, p.lds, io.st, ba, io.x[0],
+                             m->d_flat, tb.acts, tb.drop, t->d_dpre, t->d_grad);
+    } else {  // the MFMA backward (default)
+        if (!t->d_gt) SMH_CHECK_HIP(hipMalloc((void **)&t->d_gt, (size_t)t->max_batch * p.gt_patch_floats * sizeof(float)));
+        rc = launch_dtrunk(ba, p, m->d_flat, tb.acts, t->d_dpre, t->d_gt, io.st);
+        if (!rc) rc = launch_backward_mfma(t, ba, p, io.x[0], tb, t->d_gt, io.st);
     }
+    if (rc || p.dwh == kDwhNone) return rc;
+    const dim3 grid(p.dwh_grid.x, p.dwh_grid.y, p.dwh_grid.z);
+    if (p.dwh == kDwhValu) {  // the one-thread-per-element kernel (a second implementation for the tests)
+        hipLaunchKernelGGL(dwh_kernel, grid, dim3(256), 0, io.st, ba, tb.acts, t->d_dpre, t->d_grad, kDwhSlice);
+        return smh::launch_status("dwh_kernel");
+    }
+    hipLaunchKernelGGL(dwh_mfma_kernel, grid, dim3(256), 0, io.st, ba, tb.acts, t->d_dpre, t->d_grad);
+    return smh::launch_status("dwh_mfma_kernel");
+}
+
+// One training step of a TCN model, after the entry point's checks: the plan, once, then its four parts.  The switches are read at
+// the top of every step rather than once in smh_trainer_create: tests flip them between the steps of one trainer.
+static int train_step(smh_trainer *t, const StepIO &io) {
+    const TrainSwitches sw = read_train_switches();
+    smh_model *m = t->m;
+    const TrainPlan p = train_plan(m, io.N, t->dtype, sw);
+    int rc = train_plan_status(m, p);
     if (rc) return rc;
-    if (dwh && sw.dwh_valu) {  // the one-thread-per-element kernel (a second implementation for the tests)
-        hipLaunchKernelGGL(dwh_kernel, dim3((ba.D * kHidden + 255) / 256, (N + kDwhSlice - 1) / kDwhSlice, 1 + ba.n_heads), dim3(256), 0,
-                           st, ba, t->d_acts, t->d_dpre, t->d_grad, kDwhSlice);
-        rc = smh::launch_status("dwh_kernel");
-    } else if (dwh) {
-        hipLaunchKernelGGL(dwh_mfma_kernel, dim3((ba.D / 16 + 3) / 4, 1 + ba.n_heads, kDwhSplit), dim3(256), 0, st, ba, t->d_acts,
-                           t->d_dpre, t->d_grad);
-        rc = smh::launch_status("dwh_mfma_kernel");
-    }
-    return rc ? rc : det_finalize(t, st);
+    SMH_CHECK_HIP(hipMemsetAsync(t->d_grad, 0, m->n_params * sizeof(float), io.st));
+    const Offsets off = offsets(m);
+    const HeadsArgs ha = heads_args(m, off, io.N, io.h_loss_weights, sw.heads_stamps);
+    const BwdArgs ba = bwd_args(t, off, io.N, sw.split3, p.forward == kTrainForwardTrunkPair ? 0 : sw.stamps, p.backward.use_wt);
+    rc = train_forward(t, io, p);
+    if (!rc) rc = train_heads(t, io, p, ha, ba);
+    if (!rc) rc = train_backward(t, io, p, ba);
+    return rc ? rc : det_finalize(t, io.st);
 }
 
 extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float *d_y, int N, const float *d_drop_tcn,
@@ -1577,7 +1547,7 @@ extern "C" int smh_train_step_f32(smh_trainer *t, const float *d_x, const float 
     SMH_REQUIRE(N >= 1 && N <= t->max_batch, "smh_train_step_f32: batch %d outside [1, %d]", N, t->max_batch);
     SMH_REQUIRE(t->m->heads != SMH_HEADS_FUSION, "smh_train_step_f32: an intermediate-fusion model has two inputs; use "
                 "smh_fusion_train_step_f32");
-    return train_step(t, &d_x, 1, d_y, N, d_drop_tcn, d_drop_heads, h_loss_weights, d_losses, (hipStream_t)stream);
+    return train_step(t, StepIO{&d_x, 1, d_y, N, d_drop_tcn, d_drop_heads, h_loss_weights, d_losses, (hipStream_t)stream});
 }
 
 extern "C" size_t smh_trainer_bucket_floats(const smh_trainer *t) { return t ? t->m->n_params + t->bn_floats : 0; }
@@ -1648,10 +1618,20 @@ extern "C" int smh_fusion_train_step_f32(smh_trainer *t, const float *d_xH, cons
     SMH_REQUIRE(t->m->heads == SMH_HEADS_FUSION, "smh_fusion_train_step_f32: the model is not an intermediate-fusion model");
     SMH_REQUIRE(N >= 1 && N <= t->max_batch, "smh_fusion_train_step_f32: batch %d outside [1, %d]", N, t->max_batch);
     SMH_REQUIRE(t->dtype == 0, "smh_fusion_train_step_f32: the intermediate-fusion model trains in f32 (dtype 0) only");
-    const int T = t->m->cfg.patch_size;
-    const MfmaPlan plan = mfma_plan(T);
-    SMH_REQUIRE(plan.short_ok || plan.long_ok, "smh_fusion_train_step_f32: patch_size %d too long for the trunk backward (at most %d frames)",
-                T, kMfmaLongT);
-    const float *x[2] = {d_xH, d_xP};
-    return train_step(t, x, 2, d_y, N, d_drop_tcn, d_drop_heads, h_loss_weights, d_losses, (hipStream_t)stream);
+    const float *x[2] = {d_xH, d_xP};  // (train_step refuses a patch too long for the trunk backward before it launches anything)
+    return train_step(t, StepIO{x, 2, d_y, N, d_drop_tcn, d_drop_heads, h_loss_weights, d_losses, (hipStream_t)stream});
+}
+
+// tests: the plan a step of N patches at `dtype` would run, under the switches set now, as the kTrainPlanInts ints of
+// smh_train_plan.h (train_plan_ints).  Launches nothing, allocates nothing, needs no trainer.  Returns SMH_OK or the error the step
+// (or smh_trainer_set_dtype before it) would return.  Not in include/smh.h.
+extern "C" int smh_internal_train_plan(const smh_model *m, int N, int dtype, int *out) {
+    SMH_REQUIRE(m && out && N >= 1, "smh_internal_train_plan: bad argument");
+    int rc = smh_model_check_train_dtype(m, dtype);
+    if (rc) return rc;
+    const TrainPlan p = train_plan(m, N, dtype, read_train_switches());
+    rc = train_plan_status(m, p);
+    if (rc) return rc;
+    train_plan_ints(p, out);
+    return SMH_OK;
 }

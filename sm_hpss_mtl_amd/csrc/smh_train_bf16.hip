@@ -88,26 +88,7 @@ __device__ __forceinline__ float quad_reduce(float v, F f) {
     return f(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
 }
 
-constexpr int kDuRow = 80;       // bytes per row of the du images: 32 bf16 + 16 bytes of padding (smh_tcn_bf16.hip: kRS)
-// The block's operand slot (and its image in the packed buffer), in pieces of 1 KiB = 64 lanes x 16 bytes: hi units 0..9, the 1x1
-// bias b2 as 32 raw floats, lo units 0..9.  Units: 0, 1 = W2 [mt] for dyn (canonical rows), 2..7 = W1 [tap][mt], 8, 9 = W2 [mt] in the
-// forward's orientation (rows = output channel), for x_b = x_b+1 - W2 . y_b - b2.
-constexpr int kUnitsPerBlk = 10;
-constexpr int kBiasPiece = kUnitsPerBlk, kLoPiece = kUnitsPerBlk + 1, kSlotPieces = 2 * kUnitsPerBlk + 1;
-constexpr int kSlotLo = kLoPiece * 1024;          // byte offset of the lo units
-constexpr int kSlotBytes = kSlotPieces * 1024;
-
-// LDS plan (host: bwd_geo)
-struct BwdGeo {
-    int G;        // patches per workgroup
-    int units;    // 16-frame tiles per patch (<= 8: one per wave)
-    int K32;      // k steps of 32 frames in the weight-gradient products
-    int halo;     // zero frames in front of / behind the xT rows: 8 -- only dilations below 8 read across a chunk boundary
-    int sxt, st;  // row strides in bytes of xT and of yT / gT / duT (16 x odd)
-    int o_x, o_y, o_g, o_du_t, o_du;  // byte offsets of the image pairs inside a patch's region (hi, then lo at + the pair's half)
-    int h_x, h_t, h_du;               // the halves: 32 * sxt, 32 * st, (T + 1) * kDuRow
-    int per_patch;                    // bytes per patch
-};
+// (kDuRow, the slot constants kUnitsPerBlk .. kSlotBytes and the LDS plan BwdGeo / bwd_geo: smh_train_plan.h)
 
 // the part of the plan that follows from K32 alone, as compile-time constants (as kernel arguments every image offset became a
 // per-lane address register of its own, hoisted out of the block loop and spilled)
@@ -606,86 +587,51 @@ tcn_backward_bf16_kernel(BwdArgs a, BwdGeo geo, const float *__restrict__ X, con
                wave, a.n_blocks, tph[0], tph[1], tph[2], tph[3], tph[4], tph[5], tph[6]);
 }
 
-bool bwd_geo(int T, int n_dil, BwdGeo *g) {
-    if (T < 1 || T > 128) return false;
-    g->units = (T + 15) / 16;
-    g->K32 = (16 * g->units + 31) / 32;
-    (void)n_dil;
-    g->halo = 8;
-    g->sxt = 2 * (2 * g->halo + 32 * g->K32) + 16;  // 16 x (3 + 4 K32): an odd multiple of 16 bytes
-    g->st = 2 * 32 * g->K32 + 16;
-    g->h_x = 32 * g->sxt, g->h_t = 32 * g->st, g->h_du = (T + 1) * kDuRow;
-    g->o_x = 0;
-    g->o_y = g->o_x + 2 * g->h_x;
-    g->o_g = g->o_y + 2 * g->h_t;
-    g->o_du_t = g->o_g + 2 * g->h_t;
-    g->o_du = g->o_du_t + 2 * g->h_t;
-    g->per_patch = g->o_du + 2 * g->h_du;
-    g->per_patch = (g->per_patch + 15) / 16 * 16;
-    if ((size_t)16 * g->units * SX * sizeof(float) > (size_t)g->per_patch) return false;  // the tail's f32 rows live on the patch's images
-    g->G = (size_t)2 * g->per_patch + kSlotBytes <= (size_t)smh::kLdsBytesPerCU ? 2 : 1;
-    return (size_t)g->G * g->per_patch + kSlotBytes <= (size_t)smh::kLdsBytesPerCU;
-}
-
 }  // namespace
 
 namespace smh_tcn {
 
-bool backward_bf16_supported(int T, int n_dil) {
-    BwdGeo geo;
-    return bwd_geo(T, n_dil, &geo) && ((geo.G == 2 && geo.K32 <= 3) || (geo.G == 1 && geo.K32 == 4));
-}
-
-int launch_dtrunk(const BwdArgs &ba, const float *d_flat, const float *d_acts, const float *d_dpre, float *d_gt, hipStream_t st) {
+int launch_dtrunk(const BwdArgs &ba, const BackwardPlan &p, const float *d_flat, const float *d_acts, const float *d_dpre, float *d_gt,
+                  hipStream_t st) {
     SMH_REQUIRE(ba.NH <= kPS && ba.n_classes <= 8 && ba.n_heads <= kMaxHeads, "launch_dtrunk: %d Dense-on-trunk outputs", ba.NH);
-    const int tiles = (ba.N + 15) / 16;
-    hipLaunchKernelGGL(dtrunk_kernel, dim3(ba.T * C / 16, std::max(1, std::min(8, tiles / 16))), dim3(256), 0, st, ba, d_flat, d_acts, d_dpre, d_gt);
+    hipLaunchKernelGGL(dtrunk_kernel, dim3(p.dtrunk.x, p.dtrunk.y), dim3(256), 0, st, ba, d_flat, d_acts, d_dpre, d_gt);
     return smh::launch_status("dtrunk_kernel");
 }
 
-int launch_backward_bf16(const BwdArgs &ba, void **d_pack, size_t *pack_cap, const float *d_x, const float *d_flat,
-                         const float *d_acts, const float *d_drop_tcn, const float *d_dpre, float *d_grad, const float *d_upre,
-                         hipStream_t st) {
-    BwdGeo geo;
-    if (!bwd_geo(ba.T, ba.n_dil, &geo)) return kBwdBf16Unsupported;
+// the instantiation for the plan's K32 and patches per workgroup (bwd_geo gives no other pair); the phase stamps exist at the
+// reference's geometry (K32 = 3) only
+static auto pick_bf16_kernel(int K32, bool stamps) {
+    if (K32 == 3) return stamps ? tcn_backward_bf16_kernel<3, 2, true> : tcn_backward_bf16_kernel<3, 2, false>;
+    if (K32 == 1) return tcn_backward_bf16_kernel<1, 2, false>;
+    if (K32 == 2) return tcn_backward_bf16_kernel<2, 2, false>;
+    return tcn_backward_bf16_kernel<4, 1, false>;
+}
+
+int launch_backward_bf16(const BwdArgs &ba, const BackwardPlan &p, void **d_pack, size_t *pack_cap, const float *d_x,
+                         const float *d_flat, const float *d_acts, const float *d_drop_tcn, const float *d_dpre, float *d_grad,
+                         const float *d_upre, hipStream_t st) {
+    SMH_REQUIRE(p.route == kBwdBf16, "launch_backward_bf16: the plan's route is %d", (int)p.route);
     BwdArgs bp = ba;
-    bp.split3 = 0;  // this kernel's timing-probe mask (results invalid): 1 no atomics, 2 no phase B, 4 no phase A, 8 no phase C
+    bp.split3 = 0;  // (smh_train_bwd.h: BwdArgs::split3)
     if (const char *ev = smh::probe_env("SMH_BWD_PROBE")) bp.split3 = atoi(ev);
-    // workspace: [the blocks' kernels as split A operands | gt (N, T, 32)]
-    const size_t pack_bytes = (size_t)ba.n_blocks * kSlotBytes;
-    const size_t need = pack_bytes + (size_t)ba.N * ba.T * C * sizeof(float);
-    if (*pack_cap < need) {
+    if (*pack_cap < p.pack_bytes) {
         if (*d_pack) SMH_CHECK_HIP(hipFree(*d_pack));
         *d_pack = nullptr, *pack_cap = 0;
-        SMH_CHECK_HIP(hipMalloc(d_pack, need));
-        *pack_cap = need;
+        SMH_CHECK_HIP(hipMalloc(d_pack, p.pack_bytes));
+        *pack_cap = p.pack_bytes;
     }
-    float *d_gt = reinterpret_cast<float *>(static_cast<char *>(*d_pack) + pack_bytes);
+    float *d_gt = reinterpret_cast<float *>(static_cast<char *>(*d_pack) + p.pack_slot_bytes);
     if (ba.n_blocks > 0) {
         const int n = ba.n_blocks * (kUnitsPerBlk + 1) * 64;
         hipLaunchKernelGGL(pack_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_flat, ba.off, ba.n_blocks, (bf16x8 *)*d_pack);
-        int rc = smh::launch_status("pack_bwd_kernel");
+        const int rc = smh::launch_status("pack_bwd_kernel");
         if (rc) return rc;
     }
-    {
-        int rc = launch_dtrunk(ba, d_flat, d_acts, d_dpre, d_gt, st);
-        if (rc) return rc;
-    }
-    const size_t lds = (size_t)geo.G * geo.per_patch + kSlotBytes;
-    auto go = [&](auto kern) -> int {
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3((ba.N + geo.G - 1) / geo.G), dim3(512 * geo.G), lds, st, bp, geo, d_x, d_flat, (const bf16x8 *)*d_pack,
-                           d_acts, d_drop_tcn, (const float *)d_gt, d_grad, d_upre);
-        return SMH_OK;
-    };
-    int rc;
-    if (geo.K32 == 3 && geo.G == 2) rc = ba.stamps ? go(tcn_backward_bf16_kernel<3, 2, true>) : go(tcn_backward_bf16_kernel<3, 2, false>);
-    else if (geo.K32 == 1 && geo.G == 2) rc = go(tcn_backward_bf16_kernel<1, 2, false>);
-    else if (geo.K32 == 2 && geo.G == 2) rc = go(tcn_backward_bf16_kernel<2, 2, false>);
-    else if (geo.K32 == 4 && geo.G == 1) rc = go(tcn_backward_bf16_kernel<4, 1, false>);
-    else return kBwdBf16Unsupported;
+    const int rc = launch_dtrunk(ba, p, d_flat, d_acts, d_dpre, d_gt, st);
     if (rc) return rc;
-    return smh::launch_status("tcn_backward_bf16_kernel");
+    return smh::launch_lds(pick_bf16_kernel(p.geo.K32, ba.stamps != 0), "tcn_backward_bf16_kernel", dim3(p.grid), dim3(p.threads), p.lds,
+                           p.lds, st, bp, p.geo, d_x, d_flat, (const bf16x8 *)*d_pack, d_acts, d_drop_tcn, (const float *)d_gt, d_grad,
+                           d_upre);
 }
 
 }  // namespace smh_tcn

@@ -16,6 +16,7 @@
 // Every sum over the batch is a wave sum (lanes = samples) added into per-wave rows that are totalled in wave order: no
 // atomics, so the heads are bit-reproducible whatever smh_trainer_set_deterministic says.
 #include "smh_model.h"
+#include "smh_train_plan.h"
 #include "smh_wave.h"
 
 using namespace smh_tcn;
@@ -416,25 +417,18 @@ cascade_r_kernel(HeadsArgs a, const float *__restrict__ pre, const float *__rest
 
 }  // namespace
 
-int smh_tcn::launch_cascade_heads_train(const HeadsArgs &a, const float *pre, const float *y, const float *hp, const float *drop,
-                                        float *dpre, float *dxh, float *dr, float *grad, float *bnstat, float *losses, hipStream_t st) {
+static_assert(kTh == kSmallHeadThreads, "smh_train_plan.h plans these kernels' workgroups");
+static auto pick_cascade_sm_kernel(bool staged) { return staged ? cascade_sm_kernel<true> : cascade_sm_kernel<false>; }
+static auto pick_cascade_r_kernel(bool staged) { return staged ? cascade_r_kernel<true> : cascade_r_kernel<false>; }
+
+int smh_tcn::launch_cascade_heads_train(const HeadsArgs &a, const HeadsPlan &p, const float *pre, const float *y, const float *hp,
+                                        const float *drop, float *dpre, float *dxh, float *dr, float *grad, float *bnstat,
+                                        float *losses, hipStream_t st) {
     SMH_REQUIRE(a.n_heads == 3 && a.head_odim[2] == 2, "cascaded heads: expected S, M, R[2]");
-    // LDS: the staged columns of `pre` and the targets; 160 KB per CU minus the kernels' static accumulator rows
-    const size_t lds_sm = sizeof(float) * ((size_t)a.N * (2 * kHidden + 1) + a.N);
-    const size_t lds_r = sizeof(float) * ((size_t)a.N * (kHidden + 1) + 2 * (size_t)a.N);
-    const bool st_sm = lds_sm <= 120 * 1024, st_r = lds_r <= 120 * 1024;
-#define SMH_LAUNCH_CASC(KERN, ST, GRID, LDS)                                                                                      \
-    do {                                                                                                                          \
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)KERN<ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ST ? LDS : 0))); \
-        hipLaunchKernelGGL((KERN<ST>), dim3(GRID), dim3(kTh), ST ? LDS : 0, st, a, pre, y, hp, drop, dpre, dxh, dr, grad, bnstat, \
-                           losses);                                                                                               \
-    } while (0)
-    if (st_sm) SMH_LAUNCH_CASC(cascade_sm_kernel, true, 3, lds_sm);
-    else SMH_LAUNCH_CASC(cascade_sm_kernel, false, 3, lds_sm);
-    int rc = smh::launch_status("cascade_sm_kernel");
+    const HeadsLaunch &sm = p.k[0], &r = p.k[1];
+    const int rc = smh::launch_lds(pick_cascade_sm_kernel(sm.staged), "cascade_sm_kernel", dim3(sm.grid), dim3(sm.threads), sm.lds, sm.lds,
+                                   st, a, pre, y, hp, drop, dpre, dxh, dr, grad, bnstat, losses);
     if (rc) return rc;
-    if (st_r) SMH_LAUNCH_CASC(cascade_r_kernel, true, 1, lds_r);
-    else SMH_LAUNCH_CASC(cascade_r_kernel, false, 1, lds_r);
-#undef SMH_LAUNCH_CASC
-    return smh::launch_status("cascade_r_kernel");
+    return smh::launch_lds(pick_cascade_r_kernel(r.staged), "cascade_r_kernel", dim3(r.grid), dim3(r.threads), r.lds, r.lds, st, a, pre, y,
+                           hp, drop, dpre, dxh, dr, grad, bnstat, losses);
 }

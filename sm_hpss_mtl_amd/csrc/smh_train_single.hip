@@ -17,6 +17,7 @@
 // = samples) into per-wave rows, totalled in wave order -- no atomics, so this head is bit-reproducible whatever
 // smh_trainer_set_deterministic says.  One workgroup; batches beyond kTh samples take further passes over the same rows.
 #include "smh_model.h"
+#include "smh_train_plan.h"
 #include "smh_wave.h"
 
 using namespace smh_tcn;
@@ -111,6 +112,7 @@ int smh_tcn::launch_single_head_train(const HeadsArgs &a, const float *pre, cons
                                       hipStream_t st) {
     SMH_REQUIRE(a.n_heads == 0 && a.n_classes >= 2 && a.n_classes <= kMaxC && a.out_dim == a.n_classes,
                 "single-task head: expected no heads and 2 .. %d classes", kMaxC);
+    static_assert(kTh == kSmallHeadThreads, "smh_train_plan.h plans this kernel's workgroup");
     hipLaunchKernelGGL(single_head_train_kernel, dim3(1), dim3(kTh), 0, st, a, pre, y, dpre, grad, losses);
     return smh::launch_status("single_head_train_kernel");
 }

@@ -3,14 +3,16 @@ launch_heads_train, B3_MTL and intermediate fusion; smh_train_cascade.hip: launc
 
 It computes no numbers: it only says which instantiation of a heads kernel a batch of N patches takes, so that
 tests/test_heads_plans.py can show that every case of tests/test_heads_plans_gpu.py reaches the plan it is named for.  Each
-function cites the C++ it copies; a change of a threshold there must be mirrored here, and the hand-computed boundary pins of
-tests/test_heads_plans.py then say which cases have moved off the path they were chosen for.
+function cites the C++ it copies (today: plan_heads in smh_train_plan.h, which those launchers execute).  It is the heads part of
+tests/train_plans.py, which tests/test_train_plan_gpu.py holds to the library's own answer: a threshold that moves there without
+moving here fails that test, and the hand-computed boundary pins of tests/test_heads_plans.py then say which cases have moved off
+the path they were chosen for.
 """
 from __future__ import annotations
 
 K_HIDDEN = 16                     # smh_model.h: kHidden, the Dense(16) of every head
-MTL_STAGE_BYTES = 122 * 1024      # smh_train.hip launch_heads_train: `lds <= 122 * 1024`
-CASCADE_STAGE_BYTES = 120 * 1024  # smh_train_cascade.hip launch_cascade_heads_train: `<= 120 * 1024`
+MTL_STAGE_BYTES = 122 * 1024      # smh_train_plan.h: kHeadsStageBytes
+CASCADE_STAGE_BYTES = 120 * 1024  # smh_train_plan.h: kCascadeStageBytes
 KINDS = ("B3_MTL", "fusion", "cascaded")
 
 

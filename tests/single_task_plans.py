@@ -1,5 +1,6 @@
 """Python restatement of the launch plan of the single-task model's head kernel (sm_hpss_mtl_amd/csrc/smh_train_single.hip:
-launch_single_head_train) -- TEST INFRASTRUCTURE, like tests/heads_plans.py.  It computes no numbers.
+launch_single_head_train) -- TEST INFRASTRUCTURE, like tests/heads_plans.py, and like it a part of tests/train_plans.py, which
+tests/test_train_plan_gpu.py holds to the library.  It computes no numbers.
 
 The kernel has ONE instantiation: one workgroup of kTh = 512 threads, a sample per lane, no staged tile.  What a batch size changes
 is the number of passes over the per-wave accumulator rows -- the first pass assigns them, every later one adds to them -- so the

@@ -51,6 +51,14 @@ def test_gradients_and_losses_vs_oracle(ncls, N, W, schedule, monkeypatch):
     if schedule == "bf16":  # the training forward on split bf16 operands (smh_trainer_set_dtype): same tolerances as the f32 step
         m.train_dtype = "bf16"
         assert m.train_dtype == "bf16"
+    # The network's gradient is discontinuous where a relu input is zero or two channels tie for the channel maximum: a forward
+    # that differs from the oracle's by a relative eps takes the other branch on a fraction ~ eps of the gates, and the gradient
+    # moves by ~ sqrt(eps) of its norm.  eps ~ 1e-7 (f32 forward): 2e-3; eps ~ 1e-5 (split-bf16 forward): 2e-2.
+    _step_vs_oracle(m, ncls, w, x, y, drop_tcn, drop_heads, lw, rtol=2e-2 if schedule == "bf16" else 2e-3)
+
+
+def _step_vs_oracle(m, ncls, w, x, y, drop_tcn, drop_heads, lw, rtol):
+    """One step with apply=False: losses, accuracy and every gradient tensor against oracle.b3_mtl_train.forward_backward."""
     heads = [n for n, _, _ in b3_mtl.head_spec(ncls)]
     got = m.train_on_batch(x, y, drop_tcn=torch.from_numpy(drop_tcn).cuda(), drop_heads=torch.from_numpy(drop_heads).cuda(),
                            apply=False)
@@ -72,11 +80,33 @@ def test_gradients_and_losses_vs_oracle(ncls, N, W, schedule, monkeypatch):
         # a bias in front of BatchNorm has an analytically zero gradient: what either side holds there is float rounding of a
         # sum of O(0.1) terms that cancel
         atol = 2e-5 if name.endswith("/dense/bias") else 1e-6
-        # The network's gradient is discontinuous where a relu input is zero or two channels tie for the channel maximum: a forward
-        # that differs from the oracle's by a relative eps takes the other branch on a fraction ~ eps of the gates, and the gradient
-        # moves by ~ sqrt(eps) of its norm.  eps ~ 1e-7 (f32 forward): the 2e-3 below; eps ~ 1e-5 (split-bf16 forward): 2e-2.
-        rtol = 2e-2 if schedule == "bf16" else 2e-3
         assert np.abs(gg - gref).max() <= rtol * scale + atol, (name, np.abs(gg - gref).max(), scale)
+
+
+# The draw of the scalar-backward cases: a float32 evaluation of the reference graph stays within a tenth of the bounds below for all
+# three, which tests/test_train_plans.py asserts (how the seed was chosen: profiles/r16_train_plan.txt).
+SCALAR_SEED = 3
+SCALAR_LW = {"S": 0.7, "R": 1.3}
+
+
+@pytest.mark.parametrize("ncls,N,W,switch,use_wt", [(3, 3, 68, "SMH_TRAIN_VALU", 1),    # with the transposed kernel copies in LDS
+                                                    (3, 2, 249, "SMH_TRAIN_VALU", 0),   # too long for them
+                                                    (3, 2, 260, None, 0)])              # 257..264: the route every model takes
+def test_scalar_backward_vs_oracle(ncls, N, W, switch, use_wt, monkeypatch):
+    """tcn_backward_kernel, the scalar trunk backward: what SMH_TRAIN_VALU selects and what serves patches of 257..264 frames, too
+    long for the MFMA kernel.  The step's own plan says the case is on that route; then the comparison and the bounds of
+    test_gradients_and_losses_vs_oracle."""
+    from sm_hpss_mtl_amd.model import B3MTL
+    from tests import train_plans as P
+    monkeypatch.delenv("SMH_TRAIN_VALU", raising=False)
+    if switch:
+        monkeypatch.setenv(switch, "1")
+    w, x, y, drop_tcn, drop_heads = _problem(ncls, N, W=W, seed=SCALAR_SEED)
+    m = B3MTL(n_feat=240, patch_size=W, n_classes=ncls, loss_weights=SCALAR_LW)
+    m.set_weights_dict(w)
+    plan = dict(zip(P.FIELDS, P.ask_library(m.lib, m._h, N, 0)))
+    assert (P.ROUTES[plan["route"]], plan["use_wt"], P.DWH[plan["dwh"]]) == ("scalar", use_wt, "none")
+    _step_vs_oracle(m, ncls, w, x, y, drop_tcn, drop_heads, SCALAR_LW, rtol=2e-3)
 
 
 def test_sgd_step_matches_oracle():
