@@ -173,6 +173,10 @@ SIGNATURES = {
     "smh_late_fusion_dense_workspace_bytes": (_sz, [_vp, _i, _i]),
     "smh_late_fusion_forward_dense_f32": (_i, [_vp, _fp, _i, _i, C.c_double, _vp, _sz, _fp, _vp, _fp, _vp]),
 }
+# test-only exports that include/smh.h does not declare
+INTERNAL_SIGNATURES = {
+    "smh_internal_stft_plan": (_i, [_vp, _fp, _i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
+}
 
 _lib = None
 
@@ -187,7 +191,7 @@ def load():
             "libsmh.so not found at %s -- build it with `python -m sm_hpss_mtl_amd.build` "
             "(there is no CPU fallback for the HIP path)" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **INTERNAL_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

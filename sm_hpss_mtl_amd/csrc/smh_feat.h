@@ -103,14 +103,6 @@ int launch_std_patch(const smh_ctx *c, float *fv, const int *maxkeys, int B, int
 // ---- device helpers of the finishing kernels (smh_ragged.hip, smh_plain.hip) ------------------------------------------------------
 constexpr float kAmin = 1e-10f;  // librosa.power_to_db amin
 
-// item n of a 1-D grid whose workgroup i runs on XCD i % 8: the list in 8 contiguous ranges, one per XCD (smh_stft.hip has the reasoning)
-__device__ __forceinline__ bool xcd_item(int n_items, unsigned &n) {
-    const unsigned total = (unsigned)n_items, per_xcd = (total + 7u) >> 3;
-    const unsigned j = blockIdx.x >> 3;
-    n = (blockIdx.x & 7u) * per_xcd + j;
-    return j < per_xcd && n < total;
-}
-
 // top-dB floor in the power domain (features_clip_kernel has the derivation):
 //   max(10 log10(max(amin, x^2)), dBmax - 80) = 10 log10(max(x^2, lim)),  lim = max(amin, max(amin, xmax^2) * 1e-8)
 // -- the amin clamp acts on the f32 square

@@ -1363,7 +1363,7 @@ int launch_features_image(const smh_ctx *c, const float *S, const float *harmb, 
         // (the two halves of a clip back to back in their XCD's dispatch order: consecutive workgroups land on the same CU and the
         // second finds the first one's S / harm / perc lines in that CU's vector cache -- n halves apart the kernel takes 134 us
         // instead of 111, profiles/r03_store_policies.txt)
-        const unsigned grid = 16u * (unsigned)((n + 7) / 8);
+        const unsigned grid = 2 * smh::xcd_grid(n);
         if (!rag && getenv("SMH_FEAT_OCC")) {  // tools only: what the runtime says about residency
             const void *k2 = (const void *)pick_half_kernel(true, false, false, kNoTool);
             int nb = -1;

@@ -136,7 +136,7 @@ extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio,
         // tables of B equal clips -- a file gets the same bits alone, in an equal-length batch and in a ragged one.  The STFT kernel is
         // the one smh_stft_mag_f32 would pick for this batch: the generic one when a clip starts off an 8-byte boundary (odd n_samples
         // and B > 1), whose S differs in the last bits from the specialised kernel's that a lone aligned clip gets.
-        const bool aligned8 = ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0;
+        const bool aligned8 = smh_stft::frames_aligned8(reinterpret_cast<uintptr_t>(d_audio), B, n_samples);
         rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, po, d_fv, d_work, work_bytes, aligned8, st);
         if (rc < 0) return rc;
         if (rc == 1) return nP;

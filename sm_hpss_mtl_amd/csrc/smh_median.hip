@@ -337,7 +337,7 @@ int launch_rag(const float *d_S, float *d_harm, float *d_perc, int K, int lh, in
         return smh::set_error(SMH_E_INVALID, "ragged medians: no block-split kernel for (l_harm,l_perc)=(%d,%d), K=%d", lh, lp, K);
     const size_t lds = (size_t)K * stride * sizeof(float);
     SMH_CHECK_HIP(hipFuncSetAttribute((const void *)se->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned grid = (unsigned)(8 * (((long long)n_items + 7) / 8));
+    const unsigned grid = smh::xcd_grid(n_items);
     hipLaunchKernelGGL(se->fn, dim3(grid), dim3((q.nwh + q.nwp) * 64), lds, st, d_S, d_harm, d_perc, K, 0, TT, stride, q.nsh, q.nsp,
                        q.nwh, 2, -__builtin_inff(), __builtin_inff(), d_clips, d_items, n_items);
     return smh::launch_status("hpss_median_split_kernel (ragged)");

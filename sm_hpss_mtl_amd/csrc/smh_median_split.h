@@ -334,9 +334,8 @@ hpss_median_split_kernel(const float *__restrict__ S, float *__restrict__ harm, 
     int b = blockIdx.y, tile_i = blockIdx.x;
     size_t spec_off, harm_off;
     if (rag) {
-        const unsigned total = (unsigned)n_items, per_xcd = (total + 7u) >> 3;
-        const unsigned j = blockIdx.x >> 3, n = (blockIdx.x & 7u) * per_xcd + j;
-        if (j >= per_xcd || n >= total) return;
+        unsigned n;
+        if (!smh::xcd_item(n_items, n)) return;
         const smh_rag::Item item = items[n];
         b = item.clip, tile_i = item.tile;
         T = rag[b].T;

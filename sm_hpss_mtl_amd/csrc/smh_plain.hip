@@ -42,7 +42,7 @@ using smh_feat::final_value;
 using smh_feat::floor_of_max;
 using smh_feat::MelTable;
 using smh_feat::PatchOut;
-using smh_feat::xcd_item;
+using smh::xcd_item;
 using smh_rag::align_up;
 using smh_rag::Clip;
 using smh_rag::HostClip;
@@ -259,7 +259,7 @@ int launch_pair(const smh_ctx *ctx, const float *S, float *fv, const PatchOut &p
     const int K = ctx->K, rows = ctx->feat_rows, log_db = ctx->cfg.log_db ? 1 : 0;
     if (n_clips <= 0 || g.n_items <= 0) return SMH_OK;
     const size_t lds = ctx->n_mels > 0 ? sizeof(float) * (size_t)K * kTile : 0;
-    const unsigned gp = (unsigned)(8 * (((long long)g.n_items + 7) / 8));
+    const unsigned gp = smh::xcd_grid(g.n_items);
     // (the attribute never below 1024: a spectrogram context launches with no dynamic LDS at all)
     int rc = smh::launch_lds(plain_project_kernel, "plain_project_kernel", dim3(gp), dim3(64 * kProjWaves), lds, std::max<size_t>(lds, 1024), st,
                              smh_feat::mel_table(ctx), S, K, rows, log_db, fv, keys, g);
@@ -361,8 +361,8 @@ size_t plain_clip_bytes(const smh_ctx *ctx, int T) {
 }
 constexpr size_t kPlainFixedBytes = 6 * 256;  // alignment slack between the regions of a sub-batch
 
-int plain_sub_batch(const smh_ctx *ctx, const float *d_audio, const HostClip *hc, int n, const PatchOut &po, float *d_fv, char *d_work,
-                    size_t work_bytes, hipStream_t st) {
+int plain_sub_batch(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const float *d_audio, const HostClip *hc, int n, const PatchOut &po,
+                    float *d_fv, char *d_work, size_t work_bytes, hipStream_t st) {
     std::vector<Clip> clips;
     const size_t spec = smh_rag::fill_clips(hc, n, ctx->K, po.patches != nullptr, clips);
     // the tables: [clips][stft items][projection items][max keys = 0]
@@ -370,24 +370,17 @@ int plain_sub_batch(const smh_ctx *ctx, const float *d_audio, const HostClip *hc
     Geo g;
     int n_stft;
     const size_t o_clips = t.add(clips.data(), clips.size() * sizeof(Clip));
-    const size_t o_stft = t.add_items(hc, n, smh_stft::rag_frames(ctx, true), -1, &n_stft);
+    const size_t o_stft = t.add_items(hc, n, smh_stft::rag_frames(smh_stft::geom_of(ctx), sw, true), -1, &n_stft);
     const size_t o_proj = t.add_items(hc, n, kTile, -1, &g.n_items);
     const size_t o_keys = t.add(nullptr, (size_t)n * sizeof(int));
     int rc = t.upload(ctx, "smh_plain_frontend_ragged_f32", d_work, work_bytes, spec * sizeof(float), st);
     if (rc) return rc;
     float *d_S = reinterpret_cast<float *>(t.behind());
     g.clips = t.at<const Clip>(o_clips), g.items = t.at<const Item>(o_proj);
-    rc = smh_stft::launch_rag(ctx, d_audio, d_S, g.clips, t.at<const Item>(o_stft), n_stft, true, st);
+    rc = smh_stft::launch_rag(ctx, sw, d_audio, d_S, g.clips, t.at<const Item>(o_stft), n_stft, true, st);
     if (rc) return rc;
     g.T = g.Ttiled = g.nP = g.ntiles = 0;
     return launch_pair(ctx, d_S, d_fv, po, t.at<int>(o_keys), g, n, st);
-}
-
-// the specialised n_fft = 400 STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when
-// it is processed alone, so it is processed alone here too
-bool plain_rag_ok(const smh_ctx *ctx, const float *d_audio, long long off) {
-    const bool need8 = smh_stft::rag_frames(ctx, true) == smh_stft::kRagFrames && !ctx->stft_f64;
-    return !need8 || ((reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)off * 4) % 8) == 0;
 }
 
 }  // namespace
@@ -437,14 +430,18 @@ extern "C" int smh_plain_frontend_ragged_layout_f32(const smh_ctx *ctx, const fl
     rc = smh_rag::plan_layout(ctx, "plain ragged", h_offsets, h_lengths, B, W, shift, patches, ctx->feat_rows, p);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    auto taken = [&](int b) { return plain_rag_ok(ctx, d_audio, h_offsets[b]); };
+    // the specialised n_fft = 400 STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when
+    // it is processed alone, so it is processed alone here too
+    const smh_stft::StftSwitches sw = smh_stft::read_stft_switches();  // once per call: routing, table sizes and the launch agree
+    const bool need8 = smh_stft::rag_needs_aligned8(smh_stft::geom_of(ctx), sw);
+    auto taken = [&](int b) { return !need8 || smh_stft::clip_aligned8(reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)h_offsets[b] * 4); };
     std::vector<HostClip> hc;
     hc.reserve(B);
     for (int b = 0; b < B; ++b)
         if (taken(b)) hc.push_back(smh_rag::host_clip(p, h_offsets, b, po.W, 0));
     rc = smh_rag::run_sub_batches(
         hc.size(), kPlainFixedBytes, work_bytes, st, [&](size_t b) { return plain_clip_bytes(ctx, hc[b].T); }, [&](size_t b0, size_t nb) {
-            return plain_sub_batch(ctx, d_audio, hc.data() + b0, (int)nb, po, d_fv, (char *)d_work, work_bytes, st);
+            return plain_sub_batch(ctx, sw, d_audio, hc.data() + b0, (int)nb, po, d_fv, (char *)d_work, work_bytes, st);
         });
     if (rc) return rc;
     // the clips off an 8-byte boundary, through smh_plain_frontend_f32 (the workspace is free again in stream order)

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "smh_common.h"
+#include "smh_stft_plan.h"
 
 namespace smh_feat {
 struct PatchOut;  // smh_feat.h: where a call's patches go
@@ -110,20 +111,14 @@ int launch_with_table(const smh_ctx *ctx, const char *who, const void *src, size
 
 }  // namespace smh_rag
 
-namespace smh_stft {
-// frames per STFT item: 20 for the specialised n_fft = 400 kernel (every clip on an 8-byte boundary), 16 for the generic one
-int rag_frames(const smh_ctx *ctx, bool aligned8);
-// |STFT| of every (clip, frame tile) item into the workspace
-int launch_rag(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items,
-               int n_items, bool aligned8, hipStream_t st);
-constexpr int kRagFrames = 20;  // (the equal-length path splits 98 frames into 5 x 20 as well)
-// the f64 STFT of smh_stft_f64.hip: LDS bytes and frames per pass (0: n_fft too large) of a context, its item size, its launches
-size_t f64_lds_bytes(int M, int tt);
-int f64_frames(int M);
-int rag_frames_f64();
-int launch_rag_f64(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items,
-                   int n_items, hipStream_t st);
-int launch_f64(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, float *d_S, hipStream_t st);
+namespace smh_stft {  // the launches of a plan of smh_stft_plan.h
+inline Geom geom_of(const smh_ctx *c) { return Geom{c->cfg.n_fft, c->cfg.win_length, c->cfg.hop, c->M, c->K, c->stft_f64, c->stft64_frames}; }
+// |STFT| of every (clip, frame tile) item into the workspace; items of rag_frames(geom, sw, aligned8) frames: sw as the tables were sized
+int launch_rag(const smh_ctx *ctx, const StftSwitches &sw, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips,
+               const smh_rag::Item *d_items, int n_items, bool aligned8, hipStream_t st);
+// the f64 STFT of smh_stft_f64.hip under plan p: n_items items of a ragged call (d_clips != nullptr), else B = n_items clips of n_samples
+int launch_f64(const smh_ctx *ctx, const StftPlan &p, const char *what, const float *d_audio, int n_items, int n_samples, int T, float *d_S,
+               const smh_rag::Clip *d_clips, const smh_rag::Item *d_items, hipStream_t st);
 }  // namespace smh_stft
 
 namespace smh_median {

@@ -61,7 +61,7 @@ using smh_feat::FeatPlan;
 using smh_feat::final_value;
 using smh_feat::floor_of_max;
 using smh_feat::PatchOut;
-using smh_feat::xcd_item;
+using smh::xcd_item;
 using smh_rag::align_up;
 using smh_rag::Clip;
 using smh_rag::HostClip;
@@ -382,6 +382,7 @@ decltype(&rag_final_kernel<false>) pick_final_kernel(bool image) { return image 
 // (HostClip::cls here: 0: LDS image, even T; 1: LDS image, odd T; 2: streaming kernels)
 struct RagGeom {
     int K, rows, stft_frames, med_frames;
+    smh_stft::StftSwitches stft_sw;  // read once per call: the table sizes (stft_frames) and the launch agree
 };
 
 // device bytes one clip adds to a sub-batch (tables, statistics, S, perc, harm)
@@ -455,7 +456,7 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
     float *d_harm = reinterpret_cast<float *>(w);
     const Clip *d_clips = t.at<const Clip>(o_clips);
     int *d_keys = t.at<int>(o_keys);
-    rc = smh_stft::launch_rag(ctx, d_audio, d_S, d_clips, t.at<const Item>(o_stft), n_stft, stft_aligned8, st);
+    rc = smh_stft::launch_rag(ctx, g.stft_sw, d_audio, d_S, d_clips, t.at<const Item>(o_stft), n_stft, stft_aligned8, st);
     if (rc) return rc;
     rc = smh_median::launch_rag(d_S, d_harm, d_perc, g.K, ctx->cfg.l_harm, ctx->cfg.l_perc, d_clips, t.at<const Item>(o_med), n_med, st);
     if (rc) return rc;
@@ -468,7 +469,7 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
     }
     if (!list[2].empty()) {
         const FeatPlan fp = smh_feat::feat_plan(ctx, 1);
-        const unsigned gw = (unsigned)(8 * ((2 * (long long)n_walk + 7) / 8));
+        const unsigned gw = smh::xcd_grid(2 * (long long)n_walk);
         hipLaunchKernelGGL(pick_walk_kernel(fp.pend), dim3(gw), dim3(64 * fp.nseg), 0, st, fp, d_S, d_harm, d_perc, g.K, g.rows, d_fv, d_keys,
                            d_clips, t.at<const Item>(o_walk), n_walk);
         rc = smh::launch_status("rag_walk_kernel");
@@ -481,7 +482,7 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
             if (rc) return rc;
         }
         const size_t lds = final_tile_bytes(g.rows);
-        const unsigned gf = (unsigned)(8 * (((long long)n_final + 7) / 8));
+        const unsigned gf = smh::xcd_grid(n_final);
         rc = smh::launch_lds(pick_final_kernel(po.layout == smh_feat::kLayoutImage && d_patches), "rag_final_kernel", dim3(gf), dim3(512), lds,
                              lds, st, d_fv, (const int *)d_keys, ctx->cfg.log_db, g.rows, po.W, po.shift, d_patches, (const float4 *)d_stats,
                              d_clips, t.at<const Item>(o_final), n_final);
@@ -492,11 +493,11 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
 
 // all clips of `hc` through the ragged kernels, in as few sub-batches as the workspace allows
 int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip> &hc, const PatchOut &po, float *d_fv, void *d_work,
-            size_t work_bytes, bool stft_aligned8, hipStream_t st) {
+            size_t work_bytes, const smh_stft::StftSwitches &sw, bool stft_aligned8, hipStream_t st) {
     if (hc.empty()) return SMH_OK;
     RagGeom g;
-    g.K = ctx->K, g.rows = ctx->feat_rows;
-    g.stft_frames = smh_stft::rag_frames(ctx, stft_aligned8);
+    g.K = ctx->K, g.rows = ctx->feat_rows, g.stft_sw = sw;
+    g.stft_frames = smh_stft::rag_frames(smh_stft::geom_of(ctx), g.stft_sw, stft_aligned8);
     g.med_frames = smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, nullptr);
     SMH_REQUIRE(g.med_frames > 0, "ragged front end: no median kernel for this context");
     return smh_rag::run_sub_batches(
@@ -654,7 +655,7 @@ int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, in
         hc[b].audio_off = (long long)b * n_samples, hc[b].fv_off = (long long)b * rows2 * T, hc[b].patch_off = (long long)b * po.nP;
         hc[b].T = T, hc[b].Ttiled = smh_tiled_frames(T, po.W), hc[b].nP = po.nP, hc[b].cls = 2;
     }
-    int rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, stft_aligned8, st);
+    int rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, smh_stft::read_stft_switches(), stft_aligned8, st);
     return rc ? rc : 1;
 }
 
@@ -677,15 +678,16 @@ extern "C" int smh_internal_frontend_route(const smh_ctx *ctx, int T) {
 // ---- the C ABI -------------------------------------------------------------------------------------------------------------
 namespace {
 // which clips the ragged kernels take (cls 0 / 1 / 2) and which go through smh_frontend_f32 alone (-1)
-void classify(const smh_ctx *ctx, const float *d_audio, const long long *off, const Layout &p, int B, std::vector<int> &cls) {
+void classify(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const float *d_audio, const long long *off, const Layout &p, int B,
+              std::vector<int> &cls) {
     cls.assign(B, -1);
     if (!rag_context_ok(ctx)) return;
     // the specialised STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when it is
     // processed alone, so it is processed alone here too (same bits either way)
-    const bool need8 = smh_stft::rag_frames(ctx, true) == smh_stft::kRagFrames;
+    const bool need8 = smh_stft::rag_needs_aligned8(smh_stft::geom_of(ctx), sw);
     for (int b = 0; b < B; ++b) {
         if (!rag_clip_ok(ctx, p.T[b])) continue;
-        if (need8 && ((reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)off[b] * 4) % 8) != 0) continue;
+        if (need8 && !smh_stft::clip_aligned8(reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)off[b] * 4)) continue;
         // (even T: one workgroup per clip half; odd T -- or SMH_FEAT_NOPAIR -- one per clip: the route smh_frontend_f32 takes)
         const int r = smh_rag::feature_route(ctx, p.T[b]);
         if (r <= 2) cls[b] = r;
@@ -706,7 +708,7 @@ extern "C" int smh_frontend_ragged_sizes(const smh_ctx *ctx, const long long *h_
         // every clip the ragged kernels take at once, and never less than the largest single clip needs (alone in a sub-batch, or
         // through smh_frontend_f32): smh_rag::work_size
         std::vector<int> cls;
-        classify(ctx, nullptr, h_offsets, p, B, cls);  // (alignment is the call's business: sized as if every clip qualified)
+        classify(ctx, smh_stft::read_stft_switches(), nullptr, h_offsets, p, B, cls);  // (alignment is the call's business: sized as if every clip qualified)
         RagGeom g;
         g.K = ctx->K, g.rows = ctx->feat_rows, g.stft_frames = 16;
         g.med_frames = std::max(16, smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, nullptr));
@@ -740,13 +742,14 @@ extern "C" int smh_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d
     rc = smh_rag::plan_layout(ctx, "ragged", h_offsets, h_lengths, B, W, shift, patches, 2 * ctx->feat_rows, p);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
+    const smh_stft::StftSwitches sw = smh_stft::read_stft_switches();  // once per call: routing, table sizes and the launch agree
     std::vector<int> cls;
-    classify(ctx, d_audio, h_offsets, p, B, cls);
+    classify(ctx, sw, d_audio, h_offsets, p, B, cls);
     std::vector<HostClip> hc;
     hc.reserve(B);
     for (int b = 0; b < B; ++b)
         if (cls[b] >= 0) hc.push_back(smh_rag::host_clip(p, h_offsets, b, po.W, cls[b]));
-    rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, true, st);
+    rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, sw, true, st);
     if (rc) return rc;
     // the clips no ragged kernel covers, one by one on the same stream (the workspace is free again in stream order)
     return smh_rag::run_alone(p, B, W, shift, 2 * ctx->feat_rows, d_fv, d_patches, [&](int b) { return cls[b] >= 0; },

@@ -11,16 +11,12 @@
 // work-item -> (frame, butterfly) maps use a reciprocal multiply instead of an integer division.
 // HBM traffic per clip: 64,000 B audio in (re-reads of the 2.5x frame overlap are served by L2),
 // 78,792 B magnitudes out.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-
 #include "smh_common.h"
 #include "smh_rag.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace smh_stft;  // the plan's constants (kThreads, kMP400: stft400_kernel's float2 frame stride) and functions
 
 struct StftArgs {
     int n_samples, n_fft, hop, M, K, T, tt;  // tt = frames per workgroup
@@ -30,7 +26,7 @@ struct StftArgs {
     float inv_ns[smh::kMaxFftStages];  // 1 / Ns of the stage
     int tmul[smh::kMaxFftStages];      // M / (Ns * radix)
     float inv_tt;
-    int B, xcd_tiles;  // xcd_tiles > 0: 1-D grid, neighbouring tiles on one XCD (see stft400_kernel); the value is the tiles per clip
+    int B, xcd_tiles;  // xcd_tiles > 0: 1-D grid, neighbouring tiles on one XCD (smh_xcd.h); the value is the tiles per clip
 };
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
@@ -174,19 +170,16 @@ stft_mag_kernel(StftArgs a, const float *__restrict__ audio, const float *__rest
     float2 *buf1 = buf0 + a.tt * MP;
     int b = blockIdx.y, tile = blockIdx.x;
     size_t clip_off, spec_off;
-    if (rag) {  // ragged call (smh_rag.h): a.B items of clips of different lengths, in 8 contiguous ranges like the grid below
-        const unsigned total = (unsigned)a.B, per_xcd = (total + 7u) >> 3;
-        const unsigned j = blockIdx.x >> 3, n = (blockIdx.x & 7u) * per_xcd + j;
-        if (j >= per_xcd || n >= total) return;
+    unsigned n;
+    if (rag) {  // ragged call (smh_rag.h): a.B items of clips of different lengths, one list range per XCD (smh_xcd.h)
+        if (!smh::xcd_item(a.B, n)) return;
         const smh_rag::Item item = items[n];
         b = item.clip, tile = item.tile;
         a.T = rag[b].T;
         clip_off = (size_t)rag[b].audio_off, spec_off = (size_t)rag[b].spec_off;
     } else {
-        if (a.xcd_tiles > 0) {  // the (clip, tile) items in 8 contiguous ranges, one per XCD: stft400_kernel has the reasoning
-            const unsigned total = (unsigned)a.B * (unsigned)a.xcd_tiles, per_xcd = (total + 7u) >> 3;
-            const unsigned j = blockIdx.x >> 3, n = (blockIdx.x & 7u) * per_xcd + j;
-            if (j >= per_xcd || n >= total) return;
+        if (a.xcd_tiles > 0) {  // the (clip, tile) items in clip-major order, one range per XCD
+            if (!smh::xcd_item((unsigned)a.B * (unsigned)a.xcd_tiles, n)) return;
             b = (int)(n / (unsigned)a.xcd_tiles), tile = (int)(n - (unsigned)b * (unsigned)a.xcd_tiles);
         }
         clip_off = (size_t)b * a.n_samples, spec_off = (size_t)b * a.K * a.T;
@@ -247,8 +240,6 @@ stft_mag_kernel(StftArgs a, const float *__restrict__ audio, const float *__rest
 // element, see the kernel.
 // ~225 wave-instructions per frame instead of ~510 in the generic kernel.  Frame stride 201 float2 (odd) keeps the
 // frame-strided phase-3 reads and the 25-strided phase-2 reads conflict-free.
-constexpr int kF400 = 32;    // upper bound of frames per workgroup: phase 2 has 8 items per frame
-constexpr int kMP400 = 201;  // float2 stride of one frame in LDS
 
 // Complex arithmetic on (re, im) register PAIRS for stft400_kernel.  hipcc packs float2 math into v_pk_* instructions but
 // builds every swapped / negated operand ((-i) b, conj b, the cross terms of a complex product) with v_mov / v_pk_mov into a new
@@ -387,30 +378,22 @@ stft400_kernel(const float *__restrict__ audio, const float *__restrict__ window
     v2 *Z = win2 + 8 * ROW;   // F frames of kMP400
     // (ROW == 40) table column of item `it` (= 25 f + n2): n2, + 25 behind a frame change inside the item's 16-lane group
     auto column = [&](int it, int f, int n2) { return ROW == 25 ? n2 : n2 + 25 * (f - (it & ~15) / 25); };
-    // Workgroup -> (clip, frame tile).  ntiles > 0: a 1-D grid decoded so that NEIGHBOURING TILES RUN ON ONE XCD, dispatched next to
-    // each other.  A row of S is T frames (98: 392 bytes) and a tile writes an 80-byte piece of it, so the lines of a row are completed
-    // by up to three tiles -- in one L2 they merge before they leave for HBM; with consecutive tiles on consecutive XCDs (the plain
-    // grid: workgroup i goes to XCD i % 8) every piece left as a partial line (WRITE_SIZE 105 MB for 80.7 MB of S), and the 240 samples
-    // neighbouring tiles share were fetched twice.  The (clip, tile) items in clip-major order are cut into 8 contiguous ranges, one
-    // per XCD: the same rule serves a batch of a thousand clips (an XCD owns 128 whole clips) and a single long file (an XCD owns an
-    // eighth of its tiles).  ntiles == 0: the plain (tile, clip) grid.
+    // Workgroup -> (clip, frame tile).  ntiles > 0: a 1-D grid decoded so that NEIGHBOURING TILES RUN ON ONE XCD (smh_xcd.h has the
+    // reasoning): the B * ntiles (clip, tile) items in clip-major order, one contiguous range per XCD.  ntiles == 0: the plain grid.
     // rag != nullptr (smh_rag.h): B work items of clips of DIFFERENT lengths, item n = (clip, tile) from the list, clip shapes and
     // offsets from the descriptor table; the items are in clip-major order and cut into the same 8 ranges.
     int b = blockIdx.y, tile = blockIdx.x;
     size_t clip_off, spec_off;
+    unsigned n;
     if (rag) {
-        const unsigned total = (unsigned)B, per_xcd = (total + 7u) >> 3;
-        const unsigned j = blockIdx.x >> 3, n = (blockIdx.x & 7u) * per_xcd + j;
-        if (j >= per_xcd || n >= total) return;
+        if (!smh::xcd_item(B, n)) return;
         const smh_rag::Item item = items[n];
         b = item.clip, tile = item.tile;
         T = rag[b].T;
         clip_off = (size_t)rag[b].audio_off, spec_off = (size_t)rag[b].spec_off;
     } else {
         if (ntiles > 0) {
-            const unsigned total = (unsigned)B * (unsigned)ntiles, per_xcd = (total + 7u) >> 3;  // (the launch keeps B * ntiles below 2^31)
-            const unsigned j = blockIdx.x >> 3, n = (blockIdx.x & 7u) * per_xcd + j;
-            if (j >= per_xcd || n >= total) return;
+            if (!smh::xcd_item((unsigned)B * (unsigned)ntiles, n)) return;  // (the plan keeps B * ntiles below 2^31)
             b = (int)(n / (unsigned)ntiles), tile = (int)(n - (unsigned)b * (unsigned)ntiles);
         }
         clip_off = (size_t)b * n_samples, spec_off = (size_t)b * K * T;
@@ -608,141 +591,66 @@ stft400_kernel(const float *__restrict__ audio, const float *__restrict__ window
     }
 }
 
-}  // namespace
-
-namespace {
-// the specialised 8 x 25 kernel serves n_fft = 400 with an even hop (frames start on 8-byte boundaries when the clip does)
-bool stft400_ok(const smh_ctx *ctx) {
-    return ctx->cfg.n_fft == 400 && ctx->M == 200 && ctx->cfg.win_length <= 400 && (ctx->cfg.hop % 2) == 0 && !getenv("SMH_STFT_GENERIC");
+// the plan of smh_stft_mag_f32 for B clips of T >= 1 frames
+StftPlan equal_plan(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T) {
+    return plan_equal(geom_of(ctx), read_stft_switches(), frames_aligned8(reinterpret_cast<uintptr_t>(d_audio), B, n_samples), B, T);
 }
-// SMH_STFT_PAIRS=0: stft400_kernel's round-robin phase 1 and one-frame phase 3 on every tile (A/B runs, tests); same bits either way
-int stft400_pairs() {
-    const char *ev = getenv("SMH_STFT_PAIRS");
-    return ev && atoi(ev) == 0 ? 0 : 1;
-}
-void generic_args(const smh_ctx *ctx, StftArgs &a) {
-    a.n_fft = ctx->cfg.n_fft, a.hop = ctx->cfg.hop, a.M = ctx->M, a.K = ctx->K;
-    a.n_stages = ctx->n_stages;
-    for (int i = 0; i < smh::kMaxFftStages; ++i) {
-        a.radix[i] = i < ctx->n_stages ? ctx->radix[i] : 1;
-        a.inv_nb[i] = (float)a.radix[i] / (float)a.M;
+// plan p onto the stream: n_items items of a ragged call (d_clips != nullptr), else B = n_items clips of n_samples samples, T frames
+int launch(const smh_ctx *ctx, const StftPlan &p, const float *d_audio, int n_items, int n_samples, int T, float *d_S,
+           const smh_rag::Clip *d_clips, const smh_rag::Item *d_items, hipStream_t st) {
+    SMH_REQUIRE(!p.refusal[0], "%s", p.refusal);
+    const dim3 grid(p.grid_x, p.grid_y), block(p.threads);
+    if (p.kernel == kF64)
+        return launch_f64(ctx, p, d_clips ? "stft_f64_kernel (ragged)" : "stft_f64_kernel", d_audio, n_items, n_samples, T, d_S, d_clips, d_items, st);
+    if (p.kernel == kGeneric) {
+        StftArgs a;
+        a.n_fft = ctx->cfg.n_fft, a.hop = ctx->cfg.hop, a.M = ctx->M, a.K = ctx->K;
+        fill_stages(ctx->radix, ctx->n_stages, a);
+        a.n_samples = n_samples, a.T = T, a.tt = p.frames, a.inv_tt = 1.0f / (float)a.tt, a.B = n_items, a.xcd_tiles = p.xcd_tiles;
+        return smh::launch_lds(stft_mag_kernel, d_clips ? "stft_mag_kernel (ragged)" : "stft_mag_kernel", grid, block, p.lds, p.lds, st, a, d_audio,
+                               ctx->d_window, ctx->d_twM, ctx->d_tw2M, d_S, d_clips, d_items);
     }
-    for (int i = 0, ns = 1; i < smh::kMaxFftStages; ++i) {
-        a.inv_ns[i] = 1.0f / (float)ns;
-        a.tmul[i] = a.M / (ns * a.radix[i]) > 0 ? a.M / (ns * a.radix[i]) : 0;
-        ns *= a.radix[i];
-        if (ns > a.M) ns = a.M;
+    int row = 25, probe = 0;
+    if (!d_clips) {  // the probes of an equal-length call: outputs invalid
+        if (const char *ev = smh::probe_env("SMH_STFT_ROW")) row = atoi(ev) == 40 ? 40 : 25;
+        probe = smh::probe_env("SMH_STFT_PROBE_NOSTORE") ? 1 : 0;  // timing experiment, S is not written
     }
-}
-constexpr int kRagFramesGeneric = 16;
-// The kernel an equal-length call runs: 2 the f64 one, 1 the specialised 8 x 25 one, 0 the generic one.
-// n_fft = 400 with 8-byte aligned frames takes the specialised kernel (SMH_STFT_GENERIC=1 forces the generic one); an odd clip
-// length only matters for where the NEXT clip starts, so a single clip keeps it.
-int stft_route(const smh_ctx *ctx, const float *d_audio, int B, int n_samples) {
-    if (ctx->stft_f64) return 2;
-    return stft400_ok(ctx) && ((n_samples % 2) == 0 || B == 1) && (reinterpret_cast<uintptr_t>(d_audio) % 8) == 0 ? 1 : 0;
+    const size_t lds = lds400_bytes(row, p.frames);
+    return smh::launch_lds(row == 25 ? stft400_kernel<25> : stft400_kernel<40>, d_clips ? "stft400_kernel (ragged)" : "stft400_kernel", grid, block,
+                           lds, lds, st, d_audio, ctx->d_window, ctx->d_twM, ctx->d_tw2M, d_S, n_samples, ctx->cfg.hop, T, p.frames, probe, n_items,
+                           p.xcd_tiles, p.pairs, d_clips, d_items);
 }
 }  // namespace
-
-// tests: the route smh_stft_mag_f32 takes for this call (stft_route above), -1 for a null context
-extern "C" int smh_internal_stft_route(const smh_ctx *ctx, const float *d_audio, int B, int n_samples) {
-    return ctx ? stft_route(ctx, d_audio, B, n_samples) : -1;
-}
-
-namespace smh_stft {
-int rag_frames(const smh_ctx *ctx, bool aligned8) {
-    if (ctx->stft_f64) return rag_frames_f64();
-    return stft400_ok(ctx) && aligned8 ? kRagFrames : kRagFramesGeneric;
-}
 
 // One launch for clips of different lengths (smh_rag.h).  A frame's transform does not depend on the frames it shares a workgroup
 // with, so every clip gets the bits smh_stft_mag_f32 gives it alone.
-int launch_rag(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items,
-               int n_items, bool aligned8, hipStream_t st) {
+int smh_stft::launch_rag(const smh_ctx *ctx, const StftSwitches &sw, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips,
+                         const smh_rag::Item *d_items, int n_items, bool aligned8, hipStream_t st) {
     if (n_items <= 0) return SMH_OK;
-    if (ctx->stft_f64) return launch_rag_f64(ctx, d_audio, d_S, d_clips, d_items, n_items, st);
-    const unsigned grid = (unsigned)(8 * (((long long)n_items + 7) / 8));
-    if (stft400_ok(ctx) && aligned8) {
-        const int F = kRagFrames;
-        const size_t lds = sizeof(float2) * (8 * 25 + 202 + 8 * 25 + (size_t)F * kMP400);
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)stft400_kernel<25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(stft400_kernel<25>, dim3(grid), dim3(256), lds, st, d_audio, ctx->d_window, ctx->d_twM, ctx->d_tw2M, d_S, 0,
-                           ctx->cfg.hop, 0, F, 0, n_items, 0, stft400_pairs(), d_clips, d_items);
-        return smh::launch_status("stft400_kernel (ragged)");
-    }
-    StftArgs a;
-    generic_args(ctx, a);
-    a.n_samples = 0, a.T = 0, a.tt = kRagFramesGeneric, a.inv_tt = 1.0f / (float)a.tt;
-    const int MP = a.M + (a.M >> 4) + 2;
-    const size_t lds = sizeof(float2) * ((size_t)a.M + (a.M + 1) + 2 * (size_t)a.tt * MP);
-    SMH_REQUIRE(lds <= 150 * 1024, "ragged STFT: n_fft=%d too large for the LDS FFT", a.n_fft);
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)stft_mag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    a.B = n_items, a.xcd_tiles = 0;
-    hipLaunchKernelGGL(stft_mag_kernel, dim3(grid), dim3(kThreads), lds, st, a, d_audio, ctx->d_window, ctx->d_twM, ctx->d_tw2M, d_S,
-                       d_clips, d_items);
-    return smh::launch_status("stft_mag_kernel (ragged)");
+    return launch(ctx, plan_rag(geom_of(ctx), sw, aligned8, n_items), d_audio, n_items, 0, 0, d_S, d_clips, d_items, st);
 }
-}  // namespace smh_stft
 
-extern "C" int smh_stft_mag_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, float *d_S,
-                                void *stream) {
+// tests: the kernel smh_stft_mag_f32 runs for this call (smh_stft_plan.h: Kernel; it does not depend on T), -1 for a null context
+extern "C" int smh_internal_stft_route(const smh_ctx *ctx, const float *d_audio, int B, int n_samples) {
+    return ctx ? equal_plan(ctx, d_audio, B, n_samples, 1).kernel : -1;
+}
+// tests: the plan (stft_plan_ints) of this smh_stft_mag_f32 call, or (ragged != 0) of launch_rag(aligned8, n_items), or its refusal
+extern "C" int smh_internal_stft_plan(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int ragged, int aligned8, int n_items,
+                                      int *out) {
+    SMH_REQUIRE(ctx && out, "smh_internal_stft_plan: null argument");
+    const int T = smh_num_frames(n_samples, ctx->cfg.n_fft, ctx->cfg.hop);
+    SMH_REQUIRE(ragged || (B >= 1 && T >= 1), "smh_internal_stft_plan: bad shape");
+    const StftPlan p = ragged ? plan_rag(geom_of(ctx), read_stft_switches(), aligned8 != 0, n_items) : equal_plan(ctx, d_audio, B, n_samples, T);
+    SMH_REQUIRE(!p.refusal[0], "%s", p.refusal);
+    stft_plan_ints(p, out);
+    return SMH_OK;
+}
+
+extern "C" int smh_stft_mag_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, float *d_S, void *stream) {
     SMH_REQUIRE(ctx && (d_audio || B == 0) && (d_S || B == 0), "smh_stft_mag_f32: null argument");
     SMH_REQUIRE(B >= 0 && B <= 65535, "smh_stft_mag_f32: B=%d out of range", B);
     const int T = smh_num_frames(n_samples, ctx->cfg.n_fft, ctx->cfg.hop);
     SMH_REQUIRE(T >= 1, "smh_stft_mag_f32: clip of %d samples is shorter than n_fft=%d", n_samples, ctx->cfg.n_fft);
     if (B == 0) return SMH_OK;
-    const int route = stft_route(ctx, d_audio, B, n_samples);
-    if (route == 2) return smh_stft::launch_f64(ctx, d_audio, B, n_samples, T, d_S, (hipStream_t)stream);
-    if (route == 1) {
-        // frames per workgroup: <= 20 (37 KB of LDS, 128 VGPRs: FOUR 256-thread workgroups per CU), splitting T evenly (98 -> 5 x 20,
-        // the last with 18).  25 frames (45 KB: three per CU) measured 69-71 us, 20 frames 64.6; 16 and fewer leave half of phase
-        // 2's threads idle (8 items per frame) and are slower again.  tools/gpu/r2_stft_tune.sh sweeps it.
-        int maxf = 20, nthreads = 256;
-        if (const char *ev = getenv("SMH_STFT_FRAMES")) sscanf(ev, "%d,%d", &maxf, &nthreads);  // tuning override
-        if (nthreads != 512) nthreads = 256;
-        if (maxf < 1) maxf = 1;
-        if (maxf > nthreads / 8) maxf = nthreads / 8;
-        const int ntiles = (T + maxf - 1) / maxf;
-        int F = (T + ntiles - 1) / ntiles;
-        const int pairs = stft400_pairs();
-        if (pairs && T % 2 == 0 && F % 2 != 0 && F < maxf) ++F;  // even tiles for an even T: every tile can take phase 3 in frame pairs
-        int row = 25;
-        if (const char *ev = smh::probe_env("SMH_STFT_ROW")) row = atoi(ev) == 40 ? 40 : 25;
-        const size_t lds = sizeof(float2) * (8 * row + 202 + 8 * row + (size_t)F * kMP400);
-        auto kernel = row == 40 ? stft400_kernel<40> : stft400_kernel<25>;
-        SMH_CHECK_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int nt = (T + F - 1) / F;
-        bool by_xcd = true;  // SMH_STFT_XCD=0: the plain (tile, clip) grid (A/B, tests)
-        if (const char *ev = getenv("SMH_STFT_XCD")) by_xcd = atoi(ev) != 0;
-        if ((long long)B * nt >= (1ll << 31) - 8) by_xcd = false;
-        dim3 grid(nt, B), block(nthreads);
-        if (by_xcd) grid = dim3((unsigned)(8 * (((long long)B * nt + 7) / 8)), 1);
-        const int probe = smh::probe_env("SMH_STFT_PROBE_NOSTORE") ? 1 : 0;  // timing experiment, S is not written
-        hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, d_audio, ctx->d_window, ctx->d_twM,
-                           ctx->d_tw2M, d_S, n_samples, ctx->cfg.hop, T, F, probe, B, by_xcd ? nt : 0, pairs, nullptr, nullptr);
-        return smh::launch_status("stft400_kernel");
-    }
-    StftArgs a;
-    generic_args(ctx, a);
-    a.n_samples = n_samples, a.T = T;
-    // frames per workgroup: <= 16, chosen to split T evenly (T=98 -> 7 tiles of 14)
-    const int max_tt = 16;
-    const int ntiles = (T + max_tt - 1) / max_tt;
-    a.tt = (T + ntiles - 1) / ntiles;
-    a.inv_tt = 1.0f / (float)a.tt;
-    const int MP = a.M + (a.M >> 4) + 2;
-    const size_t lds = sizeof(float2) * ((size_t)a.M + (a.M + 1) + 2 * (size_t)a.tt * MP);
-    SMH_REQUIRE(lds <= 150 * 1024, "smh_stft_mag_f32: n_fft=%d too large for the LDS FFT", a.n_fft);
-    SMH_REQUIRE((size_t)a.tt * a.K < (1u << 20), "smh_stft_mag_f32: tile too large");
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)stft_mag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-    const int ntg = (T + a.tt - 1) / a.tt;
-    bool xcd_grid = (long long)B * ntg < (1ll << 31) - 8;
-    if (const char *ev = getenv("SMH_STFT_XCD")) xcd_grid = xcd_grid && atoi(ev) != 0;
-    a.B = B, a.xcd_tiles = xcd_grid ? ntg : 0;
-    dim3 grid(ntg, B), block(kThreads);
-    if (xcd_grid) grid = dim3((unsigned)(8 * (((long long)B * ntg + 7) / 8)), 1);
-    hipLaunchKernelGGL(stft_mag_kernel, grid, block, lds, (hipStream_t)stream, a, d_audio, ctx->d_window, ctx->d_twM,
-                       ctx->d_tw2M, d_S, nullptr, nullptr);
-    return smh::launch_status("stft_mag_kernel");
+    return launch(ctx, equal_plan(ctx, d_audio, B, n_samples, T), d_audio, B, n_samples, T, d_S, nullptr, nullptr, (hipStream_t)stream);
 }

@@ -16,17 +16,12 @@
 // the workgroup transforms them tt at a time (tt: the frames whose two f64 ping-pong buffers fit the LDS budget, chosen when the
 // context is created).  A frame's bits do not depend on its tile, so a clip gets the same S in every kind of call.  Audio is read
 // as single floats: no alignment requirement on the clip start or its length.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-
 #include "smh_common.h"
 #include "smh_rag.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kItemFrames = 16;  // frames per ragged item: the item counts the ragged planner sizes its tables for (smh_ragged.hip)
+using smh_stft::kThreads;
 
 struct Stft64Args {
     int n_samples, hop, M, K, T;
@@ -181,19 +176,16 @@ stft_f64_kernel(Stft64Args a, const float *__restrict__ audio, const double *__r
     c64 *buf1 = buf0 + a.tt * MP;
     int b = blockIdx.y, tile = blockIdx.x;
     size_t clip_off, spec_off;
-    if (rag) {  // ragged call / streaming route (smh_rag.h): a.B items, in 8 contiguous ranges, one per XCD
-        const unsigned total = (unsigned)a.B, per_xcd = (total + 7u) >> 3;
-        const unsigned j = blockIdx.x >> 3, n = (blockIdx.x & 7u) * per_xcd + j;
-        if (j >= per_xcd || n >= total) return;
+    unsigned n;
+    if (rag) {  // ragged call / streaming route (smh_rag.h): a.B items, one list range per XCD (smh_xcd.h)
+        if (!smh::xcd_item(a.B, n)) return;
         const smh_rag::Item item = items[n];
         b = item.clip, tile = item.tile;
         a.T = rag[b].T;
         clip_off = (size_t)rag[b].audio_off, spec_off = (size_t)rag[b].spec_off;
     } else {
-        if (a.xcd_tiles > 0) {  // the (clip, tile) items in 8 contiguous ranges, one per XCD (smh_stft.hip: stft400_kernel)
-            const unsigned total = (unsigned)a.B * (unsigned)a.xcd_tiles, per_xcd = (total + 7u) >> 3;
-            const unsigned j = blockIdx.x >> 3, n = (blockIdx.x & 7u) * per_xcd + j;
-            if (j >= per_xcd || n >= total) return;
+        if (a.xcd_tiles > 0) {  // the (clip, tile) items in clip-major order, one range per XCD
+            if (!smh::xcd_item((unsigned)a.B * (unsigned)a.xcd_tiles, n)) return;
             b = (int)(n / (unsigned)a.xcd_tiles), tile = (int)(n - (unsigned)b * (unsigned)a.xcd_tiles);
         }
         clip_off = (size_t)b * a.n_samples, spec_off = (size_t)b * a.K * a.T;
@@ -244,71 +236,14 @@ stft_f64_kernel(Stft64Args a, const float *__restrict__ audio, const double *__r
     }
 }
 
-void fill_args(const smh_ctx *ctx, Stft64Args &a) {
-    a.hop = ctx->cfg.hop, a.M = ctx->M, a.K = ctx->K;
-    a.n_stages = ctx->n_stages;
-    a.tt = ctx->stft64_frames;
-    for (int i = 0; i < smh::kMaxFftStages; ++i) {
-        a.radix[i] = i < ctx->n_stages ? ctx->radix[i] : 1;
-        a.inv_nb[i] = (float)a.radix[i] / (float)a.M;
-    }
-    for (int i = 0, ns = 1; i < smh::kMaxFftStages; ++i) {
-        a.inv_ns[i] = 1.0f / (float)ns;
-        a.tmul[i] = a.M / (ns * a.radix[i]) > 0 ? a.M / (ns * a.radix[i]) : 0;
-        ns *= a.radix[i];
-        if (ns > a.M) ns = a.M;
-    }
-}
-
 }  // namespace
 
-namespace smh_stft {
-
-size_t f64_lds_bytes(int M, int tt) {
-    const size_t MP = (size_t)M + (M >> 4) + 2;
-    return sizeof(double2) * ((size_t)M + (M + 1) + M + 2 * (size_t)tt * MP);
-}
-
-// frames per LDS pass of an f64 context: up to 8 (two 256-thread workgroups per CU at n_fft = 400: 62 KB each), fewer for a
-// large n_fft; 0 when not even one frame fits
-int f64_frames(int M) {
-    for (int tt = 8; tt >= 1; --tt)
-        if (f64_lds_bytes(M, tt) <= 64 * 1024 || (tt == 1 && f64_lds_bytes(M, 1) <= 150 * 1024)) return tt;
-    return 0;
-}
-
-int rag_frames_f64() { return kItemFrames; }
-
-int launch_rag_f64(const smh_ctx *ctx, const float *d_audio, float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items,
-                   int n_items, hipStream_t st) {
-    if (n_items <= 0) return SMH_OK;
+int smh_stft::launch_f64(const smh_ctx *ctx, const StftPlan &p, const char *what, const float *d_audio, int n_items, int n_samples, int T,
+                         float *d_S, const smh_rag::Clip *d_clips, const smh_rag::Item *d_items, hipStream_t st) {
     Stft64Args a;
-    fill_args(ctx, a);
-    a.n_samples = 0, a.T = 0, a.F = kItemFrames, a.B = n_items, a.xcd_tiles = 0;
-    const size_t lds = f64_lds_bytes(a.M, a.tt);
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)stft_f64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned grid = (unsigned)(8 * (((long long)n_items + 7) / 8));
-    hipLaunchKernelGGL(stft_f64_kernel, dim3(grid), dim3(kThreads), lds, st, a, d_audio, ctx->d_window64, ctx->d_twM64, ctx->d_tw2M64,
-                       d_S, d_clips, d_items);
-    return smh::launch_status("stft_f64_kernel (ragged)");
+    a.hop = ctx->cfg.hop, a.M = ctx->M, a.K = ctx->K;
+    fill_stages(ctx->radix, ctx->n_stages, a);
+    a.n_samples = n_samples, a.T = T, a.F = p.frames, a.tt = p.pass_frames, a.B = n_items, a.xcd_tiles = p.xcd_tiles;
+    return smh::launch_lds(stft_f64_kernel, what, dim3(p.grid_x, p.grid_y), dim3(p.threads), p.lds, p.lds, st, a, d_audio, ctx->d_window64,
+                           ctx->d_twM64, ctx->d_tw2M64, d_S, d_clips, d_items);
 }
-
-// equal-length batch: items of up to 16 frames splitting T evenly (98 -> 7 x 14)
-int launch_f64(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, float *d_S, hipStream_t st) {
-    Stft64Args a;
-    fill_args(ctx, a);
-    a.n_samples = n_samples, a.T = T;
-    const int ntg = (T + kItemFrames - 1) / kItemFrames;
-    a.F = (T + ntg - 1) / ntg;
-    const size_t lds = f64_lds_bytes(a.M, a.tt);
-    SMH_CHECK_HIP(hipFuncSetAttribute((const void *)stft_f64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const bool xcd_grid = (long long)B * ntg < (1ll << 31) - 8;
-    a.B = B, a.xcd_tiles = xcd_grid ? ntg : 0;
-    dim3 grid(ntg, B);
-    if (xcd_grid) grid = dim3((unsigned)(8 * (((long long)B * ntg + 7) / 8)), 1);
-    hipLaunchKernelGGL(stft_f64_kernel, grid, dim3(kThreads), lds, st, a, d_audio, ctx->d_window64, ctx->d_twM64, ctx->d_tw2M64, d_S,
-                       nullptr, nullptr);
-    return smh::launch_status("stft_f64_kernel");
-}
-
-}  // namespace smh_stft

@@ -53,12 +53,13 @@ import torch
 
 from oracle import frontend as ofe
 from tests import plain_ref as pr
+from tests import stft_plans as sp
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5      # include/smh.h: |S| within 1e-5 of max|S| of the reference's, per clip
 SENTINEL = -7.0
-LDS_LIMIT = 150 * 1024  # smh_stft.hip: the generic kernel's launch refuses more dynamic LDS
+LDS_LIMIT = sp.LDS_LIMIT  # the generic kernel's launch refuses more dynamic LDS
 _FES, _BASE = {}, {}
 
 

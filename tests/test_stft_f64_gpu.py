@@ -148,6 +148,24 @@ def test_stft_mag_other_radices_hops_and_windows(n_fft, win_length, hop):
         _compare_S(S[i], ofe.stft_mag(y, n_fft=n_fft, win_length=win_length, hop=hop), (n_fft, win_length, hop, i))
 
 
+def test_plain_grid_gives_the_bits_of_the_per_xcd_grid(monkeypatch):
+    """SMH_STFT_XCD=0 (the (tile, clip) grid) against the default 1-D grid: B = 3, T = 41 (three tiles of 14, 14 and 13 frames)."""
+    monkeypatch.delenv("SMH_STFT_XCD", raising=False)
+    fe = _f64(n_mels=0)
+    n = 400 + 40 * 160
+    clips = np.stack([_synth(n, 51), _synth(n, 52, silent=(0, 400 + 2 * 160)), _music(n, 53)])
+    x = _dev(clips)
+    from tests import stft_plans as P
+    grid = lambda: P.ask_library(fe.lib, fe._h, x.data_ptr(), 3, n)[P.FIELDS.index("grid_x"):P.FIELDS.index("pairs")]
+    S = fe.stft_mag(x)
+    assert grid() == (16, 1, 3)
+    monkeypatch.setenv("SMH_STFT_XCD", "0")
+    S_plain = fe.stft_mag(x)
+    assert grid() == (3, 3, 0)
+    assert S.shape == (3, 201, 41) and torch.equal(S, S_plain)
+    _compare_S(_host(S_plain)[0], ofe.stft_mag(clips[0], n_fft=400, win_length=400, hop=160), "plain grid")
+
+
 def _window_ok(Sok, h, axis):
     """bins whose median window (half width h along `axis`, reflect boundary) holds bit-equal S only"""
     bad = ~Sok
