@@ -176,6 +176,7 @@ SIGNATURES = {
 # test-only exports that include/smh.h does not declare
 INTERNAL_SIGNATURES = {
     "smh_internal_stft_plan": (_i, [_vp, _fp, _i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "smh_internal_median_plan": (_i, [_i] * 9 + [C.POINTER(C.c_int)]),
 }
 
 _lib = None

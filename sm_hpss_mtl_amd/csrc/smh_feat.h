@@ -172,9 +172,3 @@ __device__ __forceinline__ float standardize(float x, double mean, double scale)
 }
 
 }  // namespace smh_feat
-
-namespace smh_median {
-// both HPSS medians in one launch; returns 1 if harm was written time-major (B,T,K), 0 if (B,K,T), <0 on error
-int launch_hpss(const float *S, int B, int K, int T, int lh, int lp, float *harm, float *perc, int want_tmajor,
-                hipStream_t st);
-}  // namespace smh_median

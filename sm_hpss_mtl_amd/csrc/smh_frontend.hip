@@ -130,14 +130,15 @@ extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio,
     const int nP = po.nP;
     if (B == 0) return nP;
     hipStream_t st = (hipStream_t)stream;
-    const int route = smh_rag::feature_route(ctx, T);
+    const smh_median::MedianSwitches msw = smh_median::read_median_switches();  // once per call: the layout promised and the launch agree
+    const int route = smh_rag::feature_route(ctx, msw, T);
     if (!d_S && !d_harm && !d_perc && route == 2) {
         // Clips beyond the LDS image (longer than ~1.6 s at 240 rows), no taps: the streaming kernels of the ragged front end, fed the
         // tables of B equal clips -- a file gets the same bits alone, in an equal-length batch and in a ragged one.  The STFT kernel is
         // the one smh_stft_mag_f32 would pick for this batch: the generic one when a clip starts off an 8-byte boundary (odd n_samples
         // and B > 1), whose S differs in the last bits from the specialised kernel's that a lone aligned clip gets.
         const bool aligned8 = smh_stft::frames_aligned8(reinterpret_cast<uintptr_t>(d_audio), B, n_samples);
-        rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, po, d_fv, d_work, work_bytes, aligned8, st);
+        rc = smh_rag::run_equal(ctx, d_audio, B, n_samples, T, po, d_fv, d_work, work_bytes, msw, aligned8, st);
         if (rc < 0) return rc;
         if (rc == 1) return nP;
     }
@@ -146,7 +147,7 @@ extern "C" int smh_frontend_layout_f32(const smh_ctx *ctx, const float *d_audio,
     // the harmonic median is written in the layout its consumer reads best unless the caller taps it:
     // 16-frame blocks for the single-kernel feature path, time-major otherwise
     const int want = d_harm ? 0 : (route <= 1 ? 2 : 1);
-    const int tm = smh_median::launch_hpss(S, B, ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc, harm, perc, want, st);
+    const int tm = smh_median::launch_hpss(msw, S, B, ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc, harm, perc, want, st);
     if (tm < 0) return tm;
     if (want == 2 && tm != 2)
         return smh::set_error(SMH_E_INVALID, "smh_frontend_f32: the medians of T=%d wrote harm layout %d, the feature route needs 2", T, tm);

@@ -21,6 +21,7 @@
 // time-major (B,T,K) layout, where the 64 bins of a wave are contiguous.
 #pragma once
 #include "smh_common.h"
+#include "smh_median_plan.h"
 
 namespace smh_median {
 
@@ -264,15 +265,7 @@ hpss_median_kernel(const float *__restrict__ S, float *__restrict__ harm, float 
 }
 
 using KernelFn = void (*)(const float *, float *, float *, int, int, int, int, int, int, int, int, float, float);
-
-struct Entry {
-    int lh, lp;
-    KernelFn fn;
-};
-
-#define SMH_MEDIAN_E2(a, b) {a, b, smh_median::hpss_median_kernel<a, b>},
-#define SMH_MEDIAN_SINGLE(w) SMH_MEDIAN_E2(w, 0) SMH_MEDIAN_E2(0, w)
-
+// the instantiation of a window pair / of a single filter (lh or lp = 0) in the lists of smh_median_plan.h; nullptr: none
 KernelFn find_pair_kernel(int lh, int lp);    // smh_median.hip
 KernelFn find_single_kernel(int lh, int lp);  // smh_median_singles.hip
 

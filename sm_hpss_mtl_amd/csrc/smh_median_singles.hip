@@ -1,20 +1,13 @@
-// Single-filter instantiations (any odd window 3..63) of the HPSS median kernel.
+// Single-filter instantiations (any odd window 3..63) of the HPSS median kernel, from the list of smh_median_plan.h.
 #include "smh_median_kernel.h"
 
 namespace smh_median {
 
-const Entry kSingles[] = {
-    SMH_MEDIAN_SINGLE(3) SMH_MEDIAN_SINGLE(5) SMH_MEDIAN_SINGLE(7) SMH_MEDIAN_SINGLE(9) SMH_MEDIAN_SINGLE(11)
-    SMH_MEDIAN_SINGLE(13) SMH_MEDIAN_SINGLE(15) SMH_MEDIAN_SINGLE(17) SMH_MEDIAN_SINGLE(19) SMH_MEDIAN_SINGLE(21)
-    SMH_MEDIAN_SINGLE(23) SMH_MEDIAN_SINGLE(25) SMH_MEDIAN_SINGLE(27) SMH_MEDIAN_SINGLE(29) SMH_MEDIAN_SINGLE(31)
-    SMH_MEDIAN_SINGLE(33) SMH_MEDIAN_SINGLE(35) SMH_MEDIAN_SINGLE(37) SMH_MEDIAN_SINGLE(39) SMH_MEDIAN_SINGLE(41)
-    SMH_MEDIAN_SINGLE(43) SMH_MEDIAN_SINGLE(45) SMH_MEDIAN_SINGLE(47) SMH_MEDIAN_SINGLE(49) SMH_MEDIAN_SINGLE(51)
-    SMH_MEDIAN_SINGLE(53) SMH_MEDIAN_SINGLE(55) SMH_MEDIAN_SINGLE(57) SMH_MEDIAN_SINGLE(59) SMH_MEDIAN_SINGLE(61)
-    SMH_MEDIAN_SINGLE(63)};
-
 KernelFn find_single_kernel(int lh, int lp) {
-    for (const Entry &e : kSingles)
-        if (e.lh == lh && e.lp == lp) return e.fn;
+#define SMH_MEDIAN_SINGLE(w)                                    \
+    if (lh == w && lp == 0) return hpss_median_kernel<w, 0>; \
+    if (lh == 0 && lp == w) return hpss_median_kernel<0, w>;
+    SMH_MEDIAN_SINGLES(SMH_MEDIAN_SINGLE)
     return nullptr;
 }
 

@@ -300,16 +300,13 @@ __device__ __forceinline__ int stage_clip_dma(const char *src, int bytes, char *
     }
     return mis;
 }
-// LDS bytes the copy may write for a clip of `bytes` bytes whose start is only known to lie on a multiple of `align` bytes
-__host__ __device__ constexpr size_t dma_stage_bytes(size_t bytes, size_t align) { return (bytes + (16 - align) + 15) & ~(size_t)15; }
 
-// Register budget: the history is H*(H+1)-1 registers (80 for W = 17, 120 for W = 21), so the workgroup size is
-// chosen for 4 waves per SIMD (128 VGPRs) up to W = 17 and 3 waves per SIMD (168 VGPRs) above; two workgroups share
-// a CU (LDS: 2 x 80 KB), one staging its tile while the other computes.
+// Workgroup size by register budget (smh_median_plan.h: split_threads); two workgroups share a CU (LDS: 2 x 80 KB), one staging its
+// tile while the other computes.
 template <int LH, int LP>
 struct SplitCfg {
     static constexpr int kMaxW = LH > LP ? LH : LP;
-    static constexpr int kThreads = kMaxW <= 17 ? 512 : 384;
+    static constexpr int kThreads = split_threads(LH, LP);
     static constexpr int kWavesPerSimd = kMaxW <= 17 ? 4 : 3;
     // float2 loads in flight per lane in the flat tile load: batch x threads x 2 >= 201 x 98 (the reference clip)
     static constexpr int kFlatBatch = kMaxW <= 17 ? 20 : 27;
@@ -474,8 +471,7 @@ hpss_median_split_kernel(const float *__restrict__ S, float *__restrict__ harm, 
 // The DMA writes LDS linearly, so the tile is the flat K x T image (row stride T): conflict-free for the harmonic
 // lanes (lane <-> bin) whenever gcd(T, 64) <= 2 -- T = 98 -- because ds_read_b32 is serviced in 32-lane halves.
 // A clip need not start on a 16-byte boundary (K*T*4 = 78 792 B): the copy starts at the aligned address below it
-// and the tile pointer is moved up by the same `mis` bytes.
-__host__ __device__ constexpr int persist_tile_bytes(int K, int T) { return ((K * T * 4 + 16) + 1023) & ~1023; }
+// and the tile pointer is moved up by the same `mis` bytes (persist_tile_bytes, smh_median_plan.h).
 
 // THREADS = 512 / 768 / 1024: 2 / 3 / 4 waves per SIMD and 256 / 168 / 128 VGPRs per lane.
 template <int LH, int LP, int THREADS>
@@ -542,20 +538,10 @@ hpss_median_persist_kernel(const float *__restrict__ S, float *__restrict__ harm
 }
 
 using PersistFn = void (*)(const float *, float *, float *, int, int, int, int, int, int, int);
-struct PersistEntry {
-    int lh, lp, threads;
-    PersistFn fn;
-};
-const PersistEntry *find_persist_kernel(int lh, int lp, int threads);  // smh_median_split.hip
-
-constexpr int kSplitMaxWindow = 21;  // 120 history registers; larger windows keep the delete/insert kernel
-
 using SplitFn = void (*)(const float *, float *, float *, int, int, int, int, int, int, int, int, float, float,
                          const smh_rag::Clip *, const smh_rag::Item *, int);
-struct SplitEntry {
-    int lh, lp, threads;
-    SplitFn fn, fn_dma;  // fn_dma: the whole clip staged by LDS-DMA (stride == T)
-};
-const SplitEntry *find_split_kernel(int lh, int lp);  // smh_median_split.hip
+// the instantiations of the lists of smh_median_plan.h (smh_median_split.hip); nullptr: none.  dma: the whole clip staged by LDS-DMA
+PersistFn find_persist_kernel(int lh, int lp, int threads);
+SplitFn find_split_kernel(int lh, int lp, bool dma);
 
 }  // namespace smh_median

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "smh_common.h"
+#include "smh_median_plan.h"
 #include "smh_stft_plan.h"
 
 namespace smh_feat {
@@ -42,12 +43,12 @@ struct Item {
 // (and reported by smh_internal_frontend_route):
 //   0  the LDS image, even T: features_half_kernel      1  the LDS image, odd T (or SMH_FEAT_NOPAIR): features_clip_kernel
 //   2  the streaming kernels of smh_ragged.hip           3  neither: launch_hp_feat + launch_std_patch on the whole clip
-int feature_route(const smh_ctx *ctx, int T);
+int feature_route(const smh_ctx *ctx, const smh_median::MedianSwitches &msw, int T);
 // smh_frontend_f32's route 2 for B equal clips: the streaming kernels of smh_ragged.hip on the tables of B equal clips (returns 1 if
 // it ran, 0 if this context or shape has no ragged kernels, < 0 on error), and what that adds to the workspace
 size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T);
 int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, const smh_feat::PatchOut &po, float *d_fv, void *d_work,
-              size_t work_bytes, bool stft_aligned8, hipStream_t st);
+              size_t work_bytes, const smh_median::MedianSwitches &msw, bool stft_aligned8, hipStream_t st);
 
 // ---- the host-side planner of a ragged entry (smh_frontend_ragged_*, smh_plain_frontend_ragged_*) -------------------------------
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -121,12 +122,12 @@ int launch_f64(const smh_ctx *ctx, const StftPlan &p, const char *what, const fl
                const smh_rag::Clip *d_clips, const smh_rag::Item *d_items, hipStream_t st);
 }  // namespace smh_stft
 
-namespace smh_median {
-// frames per median item and the LDS row stride that goes with it (two workgroups per CU); 0 when (lh, lp) has no block-split kernel
-int rag_tile_frames(int K, int lh, int lp, int *stride);
-// whether launch_hpss(want_tmajor = 2) of a (K, T) spectrogram writes the 16-frame blocked harm layout
-bool blocked_harm_ok(int K, int T, int lh, int lp);
-// both HPSS medians of every (clip, frame tile) item; harm in the 16-frame blocked layout
-int launch_rag(const float *d_S, float *d_harm, float *d_perc, int K, int lh, int lp, const smh_rag::Clip *d_clips,
+namespace smh_median {  // the launches of a plan of smh_median_plan.h; sw: as the caller routed and sized its tables
+// both HPSS medians of every (clip, frame tile) item of rag_tile_frames(K, lh, lp, sw) frames; harm in the 16-frame blocked layout
+int launch_rag(const MedianSwitches &sw, const float *d_S, float *d_harm, float *d_perc, int K, int lh, int lp, const smh_rag::Clip *d_clips,
                const smh_rag::Item *d_items, int n_items, hipStream_t st);
+// both HPSS medians of B equal clips in one launch where the pair is fused; returns the harm layout written -- want_layout where the
+// kernel has it (2: blocked_harm_ok(K, T, lh, lp, sw)), else 1 or 0 --, < 0 on error
+int launch_hpss(const MedianSwitches &sw, const float *S, int B, int K, int T, int lh, int lp, float *harm, float *perc, int want_layout,
+                hipStream_t st);
 }  // namespace smh_median

@@ -382,7 +382,8 @@ decltype(&rag_final_kernel<false>) pick_final_kernel(bool image) { return image 
 // (HostClip::cls here: 0: LDS image, even T; 1: LDS image, odd T; 2: streaming kernels)
 struct RagGeom {
     int K, rows, stft_frames, med_frames;
-    smh_stft::StftSwitches stft_sw;  // read once per call: the table sizes (stft_frames) and the launch agree
+    smh_stft::StftSwitches stft_sw;      // read once per call: the table sizes (stft_frames, med_frames) and the launches agree
+    smh_median::MedianSwitches med_sw;
 };
 
 // device bytes one clip adds to a sub-batch (tables, statistics, S, perc, harm)
@@ -400,17 +401,17 @@ size_t clip_bytes(const RagGeom &g, const HostClip &c) {
 size_t final_tile_bytes(int rows) { return sizeof(float) * (size_t)2 * rows * (kFinalFrames + 1); }  // rag_final_kernel's [R2][65] tile
 constexpr size_t kFixedBytes = 8 * 256;  // alignment slack between the regions of a sub-batch
 
-bool rag_context_ok(const smh_ctx *ctx) {
+bool rag_context_ok(const smh_ctx *ctx, const smh_median::MedianSwitches &msw) {
     if (!ctx->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS") || getenv("SMH_FEAT_TWO_KERNELS") || getenv("SMH_RAGGED_PERFILE")) return false;
     if (ctx->feat_nseg[1] < 1 || ctx->feat_nseg[1] > 8) return false;
     if (final_tile_bytes(ctx->feat_rows) > 150 * 1024) return false;  // (this tile's own limit, not one of smh_feat.h's image budgets)
-    return smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, nullptr) > 0;
+    return smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, msw) > 0;
 }
-// the block-split walkers fold once per side: window / 2 + 4 < axis length (smh_median.hip: fast_ok)
+// the block-split walkers fold once per side (windows of one have no walker)
 bool rag_clip_ok(const smh_ctx *ctx, int T) {
     // (the streaming kernels address a clip's rows with 32-bit offsets: K * T and 2 * rows * T below 2^29 elements -- a day of audio)
     if ((long long)(ctx->K + 16) * T >= (1ll << 29) || (long long)2 * ctx->feat_rows * T >= (1ll << 29)) return false;
-    return ctx->cfg.l_harm / 2 + 4 < T && ctx->cfg.l_perc / 2 + 4 < ctx->K && T >= 2;
+    return smh_median::fast_ok(T, ctx->cfg.l_harm) && smh_median::fast_ok(ctx->K, ctx->cfg.l_perc);
 }
 
 // one sub-batch: tables -> one upload -> one launch per stage
@@ -458,7 +459,7 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
     int *d_keys = t.at<int>(o_keys);
     rc = smh_stft::launch_rag(ctx, g.stft_sw, d_audio, d_S, d_clips, t.at<const Item>(o_stft), n_stft, stft_aligned8, st);
     if (rc) return rc;
-    rc = smh_median::launch_rag(d_S, d_harm, d_perc, g.K, ctx->cfg.l_harm, ctx->cfg.l_perc, d_clips, t.at<const Item>(o_med), n_med, st);
+    rc = smh_median::launch_rag(g.med_sw, d_S, d_harm, d_perc, g.K, ctx->cfg.l_harm, ctx->cfg.l_perc, d_clips, t.at<const Item>(o_med), n_med, st);
     if (rc) return rc;
     // (The LDS-image clips' small grids were tried on a side stream beside the streaming kernels: the fork / join events cost the host
     // 0.4 ms per call and the call got slower, 0.74 -> 1.10 ms per 256 files; everything stays on the caller's stream.)
@@ -493,12 +494,12 @@ int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, co
 
 // all clips of `hc` through the ragged kernels, in as few sub-batches as the workspace allows
 int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip> &hc, const PatchOut &po, float *d_fv, void *d_work,
-            size_t work_bytes, const smh_stft::StftSwitches &sw, bool stft_aligned8, hipStream_t st) {
+            size_t work_bytes, const smh_stft::StftSwitches &sw, const smh_median::MedianSwitches &msw, bool stft_aligned8, hipStream_t st) {
     if (hc.empty()) return SMH_OK;
     RagGeom g;
-    g.K = ctx->K, g.rows = ctx->feat_rows, g.stft_sw = sw;
+    g.K = ctx->K, g.rows = ctx->feat_rows, g.stft_sw = sw, g.med_sw = msw;
     g.stft_frames = smh_stft::rag_frames(smh_stft::geom_of(ctx), g.stft_sw, stft_aligned8);
-    g.med_frames = smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, nullptr);
+    g.med_frames = smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, g.med_sw);
     SMH_REQUIRE(g.med_frames > 0, "ragged front end: no median kernel for this context");
     return smh_rag::run_sub_batches(
         hc.size(), kFixedBytes, work_bytes, st, [&](size_t b) { return clip_bytes(g, hc[b]); }, [&](size_t b0, size_t nb) {
@@ -647,24 +648,24 @@ size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T) {
 }
 
 int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, const PatchOut &po, float *d_fv, void *d_work,
-              size_t work_bytes, bool stft_aligned8, hipStream_t st) {
-    if (!rag_context_ok(ctx) || !rag_clip_ok(ctx, T) || (reinterpret_cast<uintptr_t>(d_work) % 16) != 0) return 0;
+              size_t work_bytes, const smh_median::MedianSwitches &msw, bool stft_aligned8, hipStream_t st) {
+    if (!rag_context_ok(ctx, msw) || !rag_clip_ok(ctx, T) || (reinterpret_cast<uintptr_t>(d_work) % 16) != 0) return 0;
     const int rows2 = 2 * ctx->feat_rows;
     std::vector<HostClip> hc(B);
     for (int b = 0; b < B; ++b) {
         hc[b].audio_off = (long long)b * n_samples, hc[b].fv_off = (long long)b * rows2 * T, hc[b].patch_off = (long long)b * po.nP;
         hc[b].T = T, hc[b].Ttiled = smh_tiled_frames(T, po.W), hc[b].nP = po.nP, hc[b].cls = 2;
     }
-    int rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, smh_stft::read_stft_switches(), stft_aligned8, st);
+    int rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, smh_stft::read_stft_switches(), msw, stft_aligned8, st);
     return rc ? rc : 1;
 }
 
-int feature_route(const smh_ctx *ctx, int T) {
+int feature_route(const smh_ctx *ctx, const smh_median::MedianSwitches &msw, int T) {
     if (smh_features_blocked_ok(ctx, T, 0)) {
-        if (!smh_median::blocked_harm_ok(ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc)) return 3;
+        if (!smh_median::blocked_harm_ok(ctx->K, T, ctx->cfg.l_harm, ctx->cfg.l_perc, msw)) return 3;
         return ((T & 1) || getenv("SMH_FEAT_NOPAIR")) ? 1 : 0;
     }
-    return rag_context_ok(ctx) && rag_clip_ok(ctx, T) ? 2 : 3;
+    return rag_context_ok(ctx, msw) && rag_clip_ok(ctx, T) ? 2 : 3;
 }
 
 }  // namespace smh_rag
@@ -672,16 +673,16 @@ int feature_route(const smh_ctx *ctx, int T) {
 // tests: the feature route (smh_rag::feature_route) of a clip of T frames in this context; -1 for a bad argument
 extern "C" int smh_internal_frontend_route(const smh_ctx *ctx, int T) {
     if (!ctx || T < 1) return -1;
-    return smh_rag::feature_route(ctx, T);
+    return smh_rag::feature_route(ctx, smh_median::read_median_switches(), T);
 }
 
 // ---- the C ABI -------------------------------------------------------------------------------------------------------------
 namespace {
 // which clips the ragged kernels take (cls 0 / 1 / 2) and which go through smh_frontend_f32 alone (-1)
-void classify(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const float *d_audio, const long long *off, const Layout &p, int B,
+void classify(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const smh_median::MedianSwitches &msw, const float *d_audio, const long long *off, const Layout &p, int B,
               std::vector<int> &cls) {
     cls.assign(B, -1);
-    if (!rag_context_ok(ctx)) return;
+    if (!rag_context_ok(ctx, msw)) return;
     // the specialised STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when it is
     // processed alone, so it is processed alone here too (same bits either way)
     const bool need8 = smh_stft::rag_needs_aligned8(smh_stft::geom_of(ctx), sw);
@@ -689,7 +690,7 @@ void classify(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const float 
         if (!rag_clip_ok(ctx, p.T[b])) continue;
         if (need8 && !smh_stft::clip_aligned8(reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)off[b] * 4)) continue;
         // (even T: one workgroup per clip half; odd T -- or SMH_FEAT_NOPAIR -- one per clip: the route smh_frontend_f32 takes)
-        const int r = smh_rag::feature_route(ctx, p.T[b]);
+        const int r = smh_rag::feature_route(ctx, msw, p.T[b]);
         if (r <= 2) cls[b] = r;
     }
 }
@@ -708,10 +709,11 @@ extern "C" int smh_frontend_ragged_sizes(const smh_ctx *ctx, const long long *h_
         // every clip the ragged kernels take at once, and never less than the largest single clip needs (alone in a sub-batch, or
         // through smh_frontend_f32): smh_rag::work_size
         std::vector<int> cls;
-        classify(ctx, smh_stft::read_stft_switches(), nullptr, h_offsets, p, B, cls);  // (alignment is the call's business: sized as if every clip qualified)
+        const smh_median::MedianSwitches msw = smh_median::read_median_switches();
+        classify(ctx, smh_stft::read_stft_switches(), msw, nullptr, h_offsets, p, B, cls);  // (alignment is the call's business: sized as if every clip qualified)
         RagGeom g;
         g.K = ctx->K, g.rows = ctx->feat_rows, g.stft_frames = 16;
-        g.med_frames = std::max(16, smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, nullptr));
+        g.med_frames = std::max(16, smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, msw));
         size_t total = kFixedBytes, single = 0;
         for (int b = 0; b < B; ++b) {
             single = std::max(single, smh_frontend_workspace_bytes(ctx, 1, h_lengths[b]));
@@ -743,13 +745,14 @@ extern "C" int smh_frontend_ragged_layout_f32(const smh_ctx *ctx, const float *d
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const smh_stft::StftSwitches sw = smh_stft::read_stft_switches();  // once per call: routing, table sizes and the launch agree
+    const smh_median::MedianSwitches msw = smh_median::read_median_switches();
     std::vector<int> cls;
-    classify(ctx, sw, d_audio, h_offsets, p, B, cls);
+    classify(ctx, sw, msw, d_audio, h_offsets, p, B, cls);
     std::vector<HostClip> hc;
     hc.reserve(B);
     for (int b = 0; b < B; ++b)
         if (cls[b] >= 0) hc.push_back(smh_rag::host_clip(p, h_offsets, b, po.W, cls[b]));
-    rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, sw, true, st);
+    rc = run_rag(ctx, d_audio, hc, po, d_fv, d_work, work_bytes, sw, msw, true, st);
     if (rc) return rc;
     // the clips no ragged kernel covers, one by one on the same stream (the workspace is free again in stream order)
     return smh_rag::run_alone(p, B, W, shift, 2 * ctx->feat_rows, d_fv, d_patches, [&](int b) { return cls[b] >= 0; },

@@ -144,16 +144,16 @@ def clip_index(B):
 FAMILY_CODE = {None: -1, "copy": 0, "small": 1, "split": 2, "persist": 3, "delete_insert": 4, "two_singles": 5}
 
 
-def library_route(lib, entry, K, T, lh, lp, B, lay):
-    """smh_internal_median_route (test-only export, not in include/smh.h) as the dict of median_plans.route; raises
-    median_plans.Refused with the text of smh_last_error() where the entry point would return SMH_E_INVALID."""
+def library_route(lib, entry, K, T, lh, lp, B, lay, n_cu=0, align=16):
+    """smh_internal_median_plan (test-only export, not in include/smh.h) as the dict of median_plans.route; raises
+    median_plans.Refused with the text of smh_last_error() where the entry point would return SMH_E_INVALID.  n_cu = 0: the library
+    asks the device; align: the input clip's alignment class.  The switches are the process's environment."""
     from sm_hpss_mtl_amd import _lib
-    f = lib.smh_internal_median_route
-    f.restype, f.argtypes = C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int)]
-    out = (C.c_int * 6)()
-    rc = f(P.ENTRIES.index(entry), K, T, lh, lp, B, lay, out)
+    out = (C.c_int * len(P.FIELDS))()
+    rc = lib.smh_internal_median_plan(P.ALL_ENTRIES.index(entry), K, T, lh, lp, B, lay, n_cu, align, out)
     if rc == _lib.SMH_E_INVALID:
         raise P.Refused(_lib.last_error())
     assert rc == 0, _lib.last_error()
-    fam = {v: k for k, v in FAMILY_CODE.items()}[out[0]]
-    return dict(family=fam, layout=out[1], ntiles=out[2], TT=out[3], nsh=out[4], nsp=out[5])
+    r = dict(zip(P.FIELDS, out))
+    r["family"] = {v: k for k, v in FAMILY_CODE.items()}[r["family"]]
+    return r

@@ -1,7 +1,7 @@
 """The median filters' harm layouts 1 = (B, T, K) and 2 = (B, ceil(T / 16), K, 16) on every kernel route, bit for bit.
 
-Every case of tests/median_cases.py (a) holds the library's own routing decision (the test-only smh_internal_median_route, which
-calls the functions the launcher decides with) against the restatement tests/median_plans.route for this device's CU count, (b) calls
+Every case of tests/median_cases.py (a) holds the library's own routing decision (the test-only smh_internal_median_plan, which
+calls the functions the launcher plans with) against the restatement tests/median_plans.route for this device's CU count, (b) calls
 the entry point, (c) asserts that the layout it returns is the predicted one, and (d) decodes the buffer by the RETURNED layout and
 compares every value of every frame t < T with oracle.frontend.median_time / median_freq (pinned to scipy in
 tests/test_oracle_pins.py) with np.array_equal -- no tolerance, nothing sampled.  `perc` is compared wherever the entry writes it.
@@ -14,8 +14,8 @@ Inputs (tests/median_cases.clips): |Gaussian| noise, a clip of multiples of 1/4 
 values near 1e30.  No NaN, no infinities, no -0.0: the kernels use +-inf as sentinels and fminf / fmaxf / v_med3_f32, which order
 neither NaN nor the two zeros the way a sort does, and the reference's own order of +-0 is arbitrary; |S| is none of these.
 
-SMH_MEDIAN_NOSPLIT is read once into a static of the library, so no test here switches it; SMH_MEDIAN_PERSIST is read on every
-call and is set by the cases that name it.  With either (or a tuning switch) set from outside the cases have nothing to say."""
+SMH_MEDIAN_PERSIST is read on every call and is set by the cases that name it.  With it, SMH_MEDIAN_NOSPLIT or a tuning switch set
+from outside the cases have nothing to say."""
 import ctypes as C
 import functools
 import os

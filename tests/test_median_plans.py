@@ -205,47 +205,166 @@ def test_the_table_covers_the_store_edges():
     assert {c["K"] for c, r in tall} == {698, 960, 1024}
 
 
-# ---- the library's own decision, where it needs no device ---------------------------------------------------------------------------
-def _needs_device(K, T, lh, lp, persist):
-    """launch_route asks the device for its CU count only on the way to the persistent kernel."""
-    want = (lh > 17 or lp > 17) if persist is None else bool(int(persist))
-    return want and (lh, lp, P.PERSIST_THREADS) in P.PERSIST and P.pair_fused(K, T, lh, lp)
+# ---- the plan's launch fields, pinned by hand ---------------------------------------------------------------------------------------
+def test_hand_computed_ragged_tile():
+    """rag_tile_frames: K = 201 leaves 20 224 // 201 = 100 -> 99 columns; less the halo of 2 x 10 frames (l_harm = 21) 79, down to a
+    multiple of 4: 76 frames, 96 columns, stride 97, 201 x 97 x 4 bytes of LDS.  (21, 11) is a 384-thread build: 6 waves, 4 of them
+    the 201 harmonic lanes, so one segment each.  The grid is the item count rounded up to a multiple of 8 (one range per XCD)."""
+    r = P.route("rag", 201, 0, 21, 11, 1001, 2, N_CU)
+    assert (r["family"], r["layout"], r["ntiles"], r["TT"], r["stride"], r["lds"]) == ("split", 2, 0, 76, 97, 201 * 97 * 4)
+    assert (r["nsh"], r["nsp"], r["nwh"], r["nwp"], r["threads"], r["grid_x"], r["grid_y"], r["dma"]) == (1, 1, 4, 2, 384, 1008, 1, 0)
+    assert P.rag_tile(201, 17, 17) == (80, 97) and P.rag_tile(201, 31, 31) is None and P.rag_tile(201, 21, 0) is None
+    # the tile must hold 2 hh + 8 = 28 frames: 48 columns, so 49 odd ones, 20 224 // K >= 49 -> K <= 412 (20 224 / 49 = 412.7;
+    # K = 413 -> 48 -> 47 columns -> 27 -> 24 frames)
+    assert P.rag_tile(412, 21, 11) == (28, 49) and P.rag_tile(413, 21, 11) is None
+    assert _refusal("rag", 413, 0, 21, 11, 5, 2, N_CU) == "ragged medians: no block-split kernel for (l_harm,l_perc)=(21,11), K=413"
+    assert P.route("rag", 201, 0, 21, 11, 0, 2, N_CU)["family"] is None
 
 
-def _switches_set():
-    return [n for n in ("SMH_MEDIAN_NOSPLIT", "SMH_MEDIAN_PERSIST", "SMH_MEDIAN_SEG", "SMH_MEDIAN_PTHREADS") if os.environ.get(n)]
+def test_hand_computed_dma_staging_boundary():
+    """dma_staged.  time_ex, K = 2, T = 34, l_harm = 11: one tile, odd stride 35, 2 x 35 x 4 = 280 bytes of LDS; the clip is
+    2 x 34 x 4 = 272 bytes, a multiple of 16.  On a 16-byte boundary the copy is the clip, 272 <= 280: DMA, the kernel is given the
+    flat image's stride 34.  Known only to 8 bytes it may start 8 bytes behind a boundary: 272 + 8 = 280, rounded out to 288 > 280:
+    registers, stride 35.  T = 33 (odd: the tile has no spare column, 2 x 33 x 4 = 264 -> 272 > 264) and T = 36 (gcd(36, 64) = 4)
+    never; K = 201, T = 98 (78 792 bytes, + 12 -> 78 816 <= 201 x 99 x 4 = 79 596) at all three alignments; a pointer off a 4-byte
+    boundary, a clip of several tiles and SMH_MEDIAN_DMA_STAGE=0 never."""
+    r = lambda T, align, K=2, env=None: P.route("time_ex", K, T, 11, 0, 3, 1, N_CU, env=env, align=align)  # noqa: E731
+    a = r(34, 16)
+    assert (a["family"], a["ntiles"], a["lds"], a["dma"], a["stride"], a["threads"], a["grid_x"], a["grid_y"]) == ("split", 1, 280, 1, 34, 512, 1, 3)
+    b = r(34, 8)
+    assert (b["dma"], b["stride"], b["lds"]) == (0, 35, 280) and r(34, 4)["dma"] == 0 and r(34, 0)["dma"] == 0
+    assert P.dma_stage_bytes(272, 16) == 272 and P.dma_stage_bytes(272, 8) == 288 and P.dma_stage_bytes(78792, 4) == 78816
+    assert [r(33, al)["dma"] for al in (16, 8, 4)] == [0, 0, 0] and [r(36, al)["dma"] for al in (16, 8, 4)] == [0, 0, 0]
+    assert [r(98, al, K=201)["dma"] for al in (16, 8, 4, 0)] == [1, 1, 1, 0]
+    assert r(34, 16, env={"SMH_MEDIAN_DMA_STAGE": "0"})["dma"] == 0 and r(34, 16, env={"SMH_MEDIAN_DMA_STAGE": "1"})["dma"] == 1
+    two = P.route("hpss_ex", 201, 102, 21, 11, 3, 2, N_CU, align=16)  # gcd(102, 64) = 2, but two tiles
+    assert (two["family"], two["ntiles"], two["dma"], two["stride"]) == ("split", 2, 0, 99)
+    # the other families never stage by DMA; the persistent kernel's rows are T, its LDS two tiles, its grid the CUs
+    pers = P.route("hpss_ex", 201, 98, 21, 11, 512, 2, N_CU)
+    assert (pers["family"], pers["dma"], pers["stride"], pers["lds"], pers["grid_x"], pers["grid_y"], pers["threads"]) \
+        == ("persist", 0, 98, 2 * 78848, N_CU, 1, 512) and (pers["nwh"], pers["nwp"]) == (4, 4)
+    di = P.route("hpss_ex", 40, 34, 31, 31, 3, 2, N_CU)
+    assert (di["family"], di["dma"], di["stride"], di["threads"], di["grid_x"], di["grid_y"]) == ("delete_insert", 0, 35, 1024, 1, 3)
 
 
-def test_library_route_equals_the_restatement_on_a_sweep_of_shapes():
-    """The export reports the launcher's own decision; everything but the persistent kernel's batch threshold is decided without a
-    device, so the restatement is held against the C++ here over tile, segment, table and fallback boundaries."""
-    if _switches_set():
-        pytest.skip("implementation forced by " + ", ".join(_switches_set()))
+# ---- the library's own plan: no device is asked when the CU count is given ----------------------------------------------------------
+def _env():
+    """The switches the library reads in this process, for the restatement."""
+    return {n: os.environ[n] for n in P.SWITCHES if n in os.environ}
+
+
+def _same(lib, entry, K, T, lh, lp, B, lay, n_cu, align):
+    """The library's plan (or refusal) of one call equals the restatement's, field by field."""
+    a = (entry, K, T, lh, lp, B, lay)
+    try:
+        want = P.route(*a, n_cu, env=_env(), align=align)
+    except P.Refused as e:
+        with pytest.raises(P.Refused) as got:
+            M.library_route(lib, *a, n_cu=n_cu, align=align)
+        assert str(got.value) == str(e), a
+    else:
+        assert M.library_route(lib, *a, n_cu=n_cu, align=align) == want, (a, n_cu, align)
+
+
+@pytest.fixture(scope="module")
+def lib():
     from sm_hpss_mtl_amd import _lib
-    lib = _lib.load()
+    return _lib.load()
+
+
+def test_library_route_equals_the_restatement_on_a_sweep_of_shapes(lib):
+    """The export reports the plan the launchers execute, and the CU count is its argument: the restatement is held against the C++
+    without a device over tile, segment, table, fallback and staging boundaries, on a device of 256 and one of 104 CUs, at all three
+    alignment classes, under whatever switches are set."""
     n = 0
-    for entry in P.ENTRIES:
+    for entry in P.ALL_ENTRIES[:5]:
         for K in (1, 9, 10, 24, 44, 66, 201, 257, 697, 698, 960, 961, 1024, 1025, 1938, 1939):
             for T in (1, 14, 15, 33, 43, 44, 67, 88, 98, 100, 101, 180, 333, 2000):
-                for lh in (1, 3, 11, 13, 17, 21, 23, 31, 63, 4, 65):
-                    for lp in ((0,) if entry.startswith("time") else (1, 7, 11, 17, 21, 51)):
+                for lh in ((0,) if entry == "freq" else (1, 3, 11, 13, 17, 21, 23, 31, 63, 4, 65)):
+                    for lp in ((0,) if entry.startswith("time") else (1, 7, 11, 17, 21, 51, 6) if entry == "freq" else (1, 7, 11, 17, 21, 51)):
                         for lay in ((0, 1, 2, 3) if entry.endswith("_ex") else (0,)):
-                            if _needs_device(K, T, lh, lp, None):
-                                continue
-                            a = (entry, K, T, lh, lp, 3, lay)
-                            try:
-                                want = P.route(*a, N_CU)
-                            except P.Refused as e:
-                                with pytest.raises(P.Refused) as got:
-                                    M.library_route(lib, *a)
-                                assert str(got.value) == str(e), a
-                            else:
-                                assert M.library_route(lib, *a) == want, a
+                            n_cu, align = ((256, 16), (104, 8), (256, 4), (104, 16), (256, 8), (104, 4))[n % 6]
+                            _same(lib, entry, K, T, lh, lp, 3, lay, n_cu, align)
                             n += 1
     assert n > 20000
-    assert M.library_route(lib, "hpss_ex", 24, 33, 21, 11, 0, 2) == P.route("hpss_ex", 24, 33, 21, 11, 0, 2, N_CU)
+    assert M.library_route(lib, "hpss_ex", 24, 33, 21, 11, 0, 2, n_cu=N_CU) == P.route("hpss_ex", 24, 33, 21, 11, 0, 2, N_CU)
     with pytest.raises(P.Refused, match="exceeds the grid limit"):
-        M.library_route(lib, "time_ex", 24, 33, 21, 0, 65536, 1)
+        M.library_route(lib, "time_ex", 24, 33, 21, 0, 65536, 1, n_cu=N_CU)
+    for K in (1, 24, 201, 257, 412, 413, 697, 2100):
+        for lh, lp in ((21, 11), (17, 17), (11, 11), (11, 21), (21, 21), (31, 31), (21, 0), (13, 7)):
+            for n_items in (0, 1, 8, 9, 1001):
+                _same(lib, "rag", K, 0, lh, lp, n_items, 2, N_CU, 16)
+
+
+def test_library_plan_holds_the_persistent_threshold_on_both_sides_without_a_device(lib):
+    """B >= 2 n_cu with n_cu an argument: 256 and 104 CUs, one clip short, exact and three over, every layout and alignment class, on
+    the shapes the sweep above used to skip (a persistent build exists and the pair is fused)."""
+    n = {"persist": 0, "split": 0, "delete_insert": 0}
+    for n_cu in (256, 104):
+        for entry in ("hpss_ex", "hpss"):
+            for K, T in ((25, 33), (24, 34), (24, 36), (201, 98), (201, 97), (201, 100), (410, 98)):
+                for lh, lp in ((21, 11), (21, 21), (11, 21), (17, 17), (11, 11), (31, 31)):
+                    for B in (2 * n_cu - 1, 2 * n_cu, 2 * n_cu + 3):
+                        for lay in ((0, 1, 2) if entry == "hpss_ex" else (0,)):
+                            for align in (16, 8, 4):
+                                _same(lib, entry, K, T, lh, lp, B, lay, n_cu, align)
+                    if not _env():
+                        fam = [P.route(entry, K, T, lh, lp, B, 0, n_cu)["family"] for B in (2 * n_cu - 1, 2 * n_cu)]
+                        assert fam[0] != "persist"
+                        n[fam[1]] += 1
+                        if fam[1] == "persist":
+                            assert M.library_route(lib, entry, K, T, lh, lp, 2 * n_cu - 1, 0, n_cu=n_cu)["family"] == "split"
+                            assert M.library_route(lib, entry, K, T, lh, lp, 2 * n_cu, 0, n_cu=n_cu)["family"] == "persist"
+    assert _env() or min(n.values()) >= 8, n
+
+
+def test_library_reads_every_switch_on_every_call(lib, monkeypatch):
+    """Each SMH_MEDIAN_* variable set in-process between two calls of the query moves the plan, and unset moves it back; the
+    restatement under the same `env` agrees each time.  SMH_MEDIAN_NOSPLIT is no longer frozen at first use."""
+    for name in P.SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    a17, a21 = ("hpss_ex", 201, 98, 17, 17, 512, 2), ("hpss_ex", 201, 98, 21, 11, 512, 2)
+
+    def both(a, align=16):
+        got = M.library_route(lib, *a, n_cu=N_CU, align=align)
+        assert got == P.route(*a, N_CU, env=_env(), align=align), (a, _env())
+        return got
+
+    base17, base21 = both(a17), both(a21)
+    assert (base17["family"], base17["layout"], base17["dma"], base17["nsh"], base17["nsp"]) == ("split", 2, 1, 1, 2)
+    assert (base21["family"], base21["threads"]) == ("persist", 512)
+    monkeypatch.setenv("SMH_MEDIAN_NOSPLIT", "1")
+    r = both(a17)
+    assert (r["family"], r["layout"], r["threads"], r["dma"]) == ("delete_insert", 1, 1024, 0) and both(a21)["family"] == "delete_insert"
+    with pytest.raises(P.Refused, match="ragged medians"):
+        M.library_route(lib, "rag", 201, 0, 21, 11, 9, 2, n_cu=N_CU)
+    monkeypatch.delenv("SMH_MEDIAN_NOSPLIT")
+    assert both(a17) == base17 and both(a21) == base21 and both(("rag", 201, 0, 21, 11, 9, 2))["TT"] == 76
+    monkeypatch.setenv("SMH_MEDIAN_PERSIST", "1")
+    assert both(a17)["family"] == "persist"
+    monkeypatch.setenv("SMH_MEDIAN_PERSIST", "0")
+    assert both(a17) == base17 and both(a21)["family"] == "split"
+    monkeypatch.delenv("SMH_MEDIAN_PERSIST")
+    monkeypatch.setenv("SMH_MEDIAN_PTHREADS", "768")
+    r = both(a21)
+    assert (r["family"], r["threads"], r["lds"]) == ("persist", 768, base21["lds"]) and r["nwh"] + r["nwp"] > 8
+    monkeypatch.setenv("SMH_MEDIAN_PTHREADS", "640")  # no such build
+    assert both(a21)["family"] == "split"
+    monkeypatch.delenv("SMH_MEDIAN_PTHREADS")
+    monkeypatch.setenv("SMH_MEDIAN_SEG", "1,1")
+    r = both(a17)
+    assert (r["family"], r["nsh"], r["nsp"], r["nwh"], r["nwp"]) == ("split", 1, 1, 4, 2)
+    monkeypatch.setenv("SMH_MEDIAN_SEG", "2,9")  # 7 + 14 waves do not fit 8: the plan's own counts stay
+    assert both(a17) == base17
+    monkeypatch.setenv("SMH_MEDIAN_SEG", "1")   # not "nsh,nsp": ignored
+    assert both(a17) == base17
+    monkeypatch.delenv("SMH_MEDIAN_SEG")
+    monkeypatch.setenv("SMH_MEDIAN_DMA_STAGE", "0")
+    r = both(a17)
+    assert (r["dma"], r["stride"]) == (0, 99) and {k: v for k, v in r.items() if k not in ("dma", "stride")} \
+        == {k: v for k, v in base17.items() if k not in ("dma", "stride")}
+    monkeypatch.delenv("SMH_MEDIAN_DMA_STAGE")
+    assert both(a17) == base17 and both(a21) == base21
 
 
 # ---- the decoders ------------------------------------------------------------------------------------------------------------------
