@@ -121,6 +121,31 @@ int smh_median_time_ex_f32(const smh_ctx *ctx, const float *d_S, int B, int K, i
 int smh_softmask_f32(const smh_ctx *ctx, const float *d_S, const float *d_harm, const float *d_perc, size_t n,
                      float *d_H, float *d_P, void *stream);
 
+/* ---- a3': HPSS audio separation -- librosa.effects.hpss with this library's framing; what makes the reference's hpss_audio/
+ * listening demos (<name>, <name>_Harmonic, <name>_Percussive).  With w the context's window (periodic Hann of win_length,
+ * zero-padded centrally to n_fft), center=False and T = smh_num_frames(n_samples, n_fft, hop):
+ *   D[:, t] = rfft(w * y[t*hop : t*hop + n_fft]);   D_h = D * softmask(harm, perc),  D_p = D * softmask(perc, harm)
+ *   (power 2, split_zeros, margin 1: |D_h|, |D_p| are smh_softmask_f32's H and P; the mixture's phase is kept);
+ *   y_c = librosa.istft(D_c, center=False, length=n_samples):  num[n] = sum_t w[n - t*hop] * irfft(D_c[:, t])[n - t*hop],
+ *   wss[n] = sum_t w^2[n - t*hop],  y_c[n] = num[n] / wss[n] where wss[n] > FLT_MIN, else num[n]; 0 from n_fft + hop*(T-1) on.
+ * smh_hpss_resynth_f32: the one kernel, on caller-supplied medians.  d_audio (B, n_samples), d_harm, d_perc (B, K, T) ->
+ *   d_y_harm, d_y_perc (B, n_samples).  The transforms are f32 in either STFT precision; the complex spectrogram stays on chip.
+ *   No atomics: a sample is the sum of its frames in ascending order, so a clip's samples are bit for bit the same alone, at any
+ *   place of any batch and in every run.
+ * smh_hpss_audio_f32: smh_stft_mag_f32 -> smh_hpss_median_f32 (the context's l_harm, l_perc) -> smh_hpss_resynth_f32, with S,
+ *   harm and perc in d_work (smh_hpss_audio_workspace_bytes, 16-byte aligned).  The context's STFT precision governs |S|, and with
+ *   it the medians, only.  (The f32 STFT picks its kernel by the clips' alignment: in a batch of an ODD n_samples its |S| differs
+ *   in the last bits from the same clip's alone, as smh_stft_mag_f32's does; even lengths and the f64 STFT are batch-independent.)
+ * Refused with SMH_E_INVALID (text in smh_last_error) before any launch: null pointers; B < 0; B > 65535 (the grid limit);
+ * n_samples < n_fft (no frame to invert); outputs that overlap an input, the workspace or each other; hop > n_fft; n_fft > 17 * hop
+ * (more than 17 frames per sample); a tile that does not fit the kernel's LDS (150 KB: csrc/smh_resynth_plan.h; both of the
+ * reference's configurations, (400, 400, 160) and (512, 400, 160), take 55 and 65 KB).  A workspace that is too small: SMH_E_WORKSPACE.  B == 0 returns SMH_OK and touches nothing.  Every offset is 64-bit. */
+int smh_hpss_resynth_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, const float *d_harm, const float *d_perc,
+                         float *d_y_harm, float *d_y_perc, void *stream);
+size_t smh_hpss_audio_workspace_bytes(const smh_ctx *ctx, int B, int n_samples);
+int smh_hpss_audio_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, float *d_y_harm, float *d_y_perc,
+                       void *d_work, size_t work_bytes, void *stream);
+
 /* ---- a4: librosa.feature.melspectrogram(S=X, n_mels=) = mel_basis(22050, n_fft) @ X ---------
  * d_X (B, K, T) -> d_Y (B, n_mels, T)  (preprocessing.py:409-410,419,421)                       */
 int smh_mel_f32(const smh_ctx *ctx, const float *d_X, int B, int T, float *d_Y, void *stream);

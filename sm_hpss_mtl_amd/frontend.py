@@ -246,6 +246,80 @@ class Frontend:
                                              _stream()), "smh_softmask_f32")
         return H, P
 
+    # ---- HPSS audio separation (librosa.effects.hpss with this framing; include/smh.h a3') ----
+    def _audio_2d(self, audio, who):
+        """(audio as (B, N), whether it came 1-D)"""
+        audio = _f32c(audio, "audio")
+        if audio.dim() not in (1, 2):
+            raise ValueError("%s: audio must be (B, N) or (N,), got shape %s" % (who, tuple(audio.shape)))
+        one = audio.dim() == 1
+        audio = audio[None] if one else audio
+        if audio.shape[1] < self.cfg.n_fft:
+            raise ValueError("%s: clip of %d samples is shorter than n_fft=%d" % (who, audio.shape[1], self.cfg.n_fft))
+        return audio, one
+
+    def resynth(self, audio, harm, perc, out=None):
+        """`smh_hpss_resynth_f32`, the resynthesis kernel alone: audio (B, N) or (N,), harm / perc (B, K, T) or (K, T) (the medians of
+        |STFT|, or any non-negative pair) -> dict(harmonic, percussive), float32 device tensors of audio's shape:
+        istft(stft(audio) * softmask(harm, perc)) and istft(stft(audio) * softmask(perc, harm)).  `out` may carry preallocated
+        'harmonic' / 'percussive' tensors."""
+        self._need_hpss("resynth")
+        audio, one = self._audio_2d(audio, "resynth")
+        harm, perc = _f32c(harm, "harm"), _f32c(perc, "perc")
+        B, N = audio.shape
+        shape = (B, self.K, self.num_frames(N))
+        if one and harm.dim() == 2 and perc.dim() == 2:
+            harm, perc = harm[None], perc[None]
+        if tuple(harm.shape) != shape or tuple(perc.shape) != shape:
+            raise ValueError("resynth: harm %s and perc %s must be %s" % (tuple(harm.shape), tuple(perc.shape), shape))
+        yshape = (N,) if one else (B, N)
+        yh = _out(out, "harmonic", yshape, torch.float32, audio.device)
+        yp = _out(out, "percussive", yshape, torch.float32, audio.device)
+        _lib.check(self.lib.smh_hpss_resynth_f32(self._h, _ptr(audio), B, N, _ptr(harm), _ptr(perc), _ptr(yh), _ptr(yp), _stream()),
+                   "smh_hpss_resynth_f32")
+        return {"harmonic": yh, "percussive": yp}
+
+    def separate(self, audio, out=None):
+        """`smh_hpss_audio_f32`: audio (B, N) -> dict(harmonic (B, N), percussive (B, N)), float32 device tensors --
+        librosa.effects.hpss(y, kernel_size=(l_harm, l_perc)) with this configuration's framing; bit for bit
+        resynth(audio, *hpss_median(stft_mag(audio))).  A 1-D input gives 1-D outputs.  A list of 1-D signals of different lengths
+        is grouped by length, one call per distinct length (signal by signal for an odd length under the f32 STFT, see below), and
+        returns lists in the caller's order, each entry bit for bit what the signal gives alone (`out` is for tensors only)."""
+        self._need_hpss("separate")
+        if isinstance(audio, (list, tuple)):
+            if out is not None:
+                raise ValueError("separate: `out` is not supported for a list of signals")
+            sigs = [_f32c(s, "audio[%d]" % i) for i, s in enumerate(audio)]
+            for i, s in enumerate(sigs):
+                if s.dim() != 1:
+                    raise ValueError("separate: audio[%d] must be 1-D, got shape %s" % (i, tuple(s.shape)))
+            groups = collections.OrderedDict()
+            for i, s in enumerate(sigs):
+                groups.setdefault(int(s.shape[0]), []).append(i)
+            res = {"harmonic": [None] * len(sigs), "percussive": [None] * len(sigs)}
+            for n, idx in groups.items():
+                # Every signal gets bit for bit what it gets alone.  The resynthesis kernel and the f64 STFT give that in any batch;
+                # the f32 STFT picks its kernel by where the clips start (smh_stft_plan.h: frames_aligned8), and in a batch of an odd
+                # length all clips but the first start off 8-byte boundaries: such a group goes signal by signal.
+                alone = self.cfg.stft_precision == "f32" and n % 2 == 1 and len(idx) > 1
+                for part in ([[i] for i in idx] if alone else [idx]):
+                    got = self.separate(torch.stack([sigs[i] for i in part]))
+                    for row, i in enumerate(part):
+                        res["harmonic"][i], res["percussive"][i] = got["harmonic"][row], got["percussive"][row]
+            return res
+        audio, one = self._audio_2d(audio, "separate")
+        B, N = audio.shape
+        dev = audio.device
+        yshape = (N,) if one else (B, N)
+        yh = _out(out, "harmonic", yshape, torch.float32, dev)
+        yp = _out(out, "percussive", yshape, torch.float32, dev)
+        need = self.lib.smh_hpss_audio_workspace_bytes(self._h, B, N)
+        if self._work is None or self._work.numel() < need or self._work.device != dev:
+            self._work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        _lib.check(self.lib.smh_hpss_audio_f32(self._h, _ptr(audio), B, N, _ptr(yh), _ptr(yp), _ptr(self._work), self._work.numel(),
+                                               _stream()), "smh_hpss_audio_f32")
+        return {"harmonic": yh, "percussive": yp}
+
     def mel(self, X):
         X = _f32c(X, "X")
         B, K, T = X.shape
