@@ -9,42 +9,24 @@
 #include "smh_common.h"
 #include "smh_feat.h"
 #include "smh_rag.h"
+#include "smh_softmask.h"
 
 namespace {
 
 constexpr float kAmin = 1e-10f;   // librosa.power_to_db amin
 constexpr float kTopDb = 80.0f;   // librosa.power_to_db top_db
 
-// librosa.util.softmask(X, X_ref, power=2, split_zeros=True) for both orientations at once
-// (called from librosa.decompose.hpss with margin 1; lib/preprocessing.py:408,418,430,440).
-// Same float32 operation order as numpy: Z=max; bad=Z<tiny -> Z=1; (X/Z)^2; m/(m+r); bad -> 0.5.
+// H = S * softmask(harm, perc), P = S * softmask(perc, harm) (lib/preprocessing.py:408,418,430,440): numpy's bits
 __device__ __forceinline__ void hpss_masks(float s, float h, float p, float &H, float &P) {
-    float Z = fmaxf(h, p);
-    const bool bad = Z < FLT_MIN;
-    Z = bad ? 1.0f : Z;
-    const float a = h / Z, b = p / Z;
-    const float m = __fmul_rn(a, a), r = __fmul_rn(b, b);  // no FMA contraction: numpy rounds the squares
-    const float den = __fadd_rn(m, r);
-    float mh = m / den, mp = r / den;
-    mh = bad ? 0.5f : mh;
-    mp = bad ? 0.5f : mp;
+    float mh, mp;
+    smh::softmask_pair(h, p, mh, mp);
     H = __fmul_rn(s, mh);
     P = __fmul_rn(s, mp);
 }
-
-// Same masks for the FUSED path: hardware reciprocals (1 ulp) instead of IEEE divisions.  H and P are not
-// outputs there; the dB features they feed are compared at 1e-3 dB (SURVEY 8d').
+// the same for the FUSED path, on hardware reciprocals
 __device__ __forceinline__ void hpss_masks_fast(float s, float h, float p, float &H, float &P) {
-    float Z = fmaxf(h, p);
-    const bool bad = Z < FLT_MIN;
-    Z = bad ? 1.0f : Z;
-    const float iz = __builtin_amdgcn_rcpf(Z);
-    const float a = h * iz, b = p * iz;
-    const float m = a * a, r = b * b;
-    const float id = __builtin_amdgcn_rcpf(m + r);
-    float mh = m * id, mp = r * id;
-    mh = bad ? 0.5f : mh;
-    mp = bad ? 0.5f : mp;
+    float mh, mp;
+    smh::softmask_pair_fast(h, p, mh, mp);
     H = s * mh;
     P = s * mp;
 }

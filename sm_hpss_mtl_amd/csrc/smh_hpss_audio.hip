@@ -5,9 +5,9 @@
 // One kernel, hpss_resynth_kernel.  A workgroup owns a run of output samples (smh_resynth_plan.h: tile, halo, LDS budget) and, in
 // passes of kPassFrames frames,
 //   1  recomputes the frames' forward transform from the audio: the windowed real frame packed into M = n_fft / 2 complex points, the
-//      mixed-radix Stockham FFT of smh_stft.hip in LDS (its butterflies are copied here, that file stays as it is);
-//   2  per bin pair (k, M - k): untangles the two real-FFT bins X[k], X[M - k], multiplies each by its two masks (the IEEE operation
-//      order of smh_softmask_f32) and tangles the masked Hermitian spectra back into the packed form of an inverse real FFT,
+//      mixed-radix Stockham FFT of smh_fft.h in LDS, the text the f32 STFT runs (smh_stft.hip: stft_mag_kernel);
+//   2  per bin pair (k, M - k): untangles the two real-FFT bins X[k], X[M - k], multiplies each by its two masks (smh_softmask.h:
+//      softmask_pair, the bits of smh_softmask_f32) and tangles the masked Hermitian spectra back into the packed form of an inverse real FFT,
 //      Z'[k] = E[k] + i O[k], E[k] = (X[k] + conj X[M - k]) / 2, O[k] = (X[k] - conj X[M - k]) / 2 * conj w^k;
 //   3  inverts both spectra with the same forward Stockham stages on conj Z' (ifft z = conj fft conj z / M): 2 * kPassFrames
 //      independent transforms; even samples are the real parts, odd samples minus the imaginary parts;
@@ -21,171 +21,26 @@
 #include <cstdint>
 
 #include "smh_common.h"
+#include "smh_fft.h"
 #include "smh_resynth_plan.h"
-#include "smh_stft_plan.h"
+#include "smh_softmask.h"
 
 namespace {
 
 using namespace smh_resynth;
+using namespace smh_fft;
 
 struct ResynthArgs {
     int n_samples, n_fft, hop, M, K, T;
     int tile, halo, pass, acc;  // acc: samples of one accumulator
-    int n_stages;
-    int radix[smh::kMaxFftStages];
-    float inv_nb[smh::kMaxFftStages];  // 1 / (M / radix)
-    float inv_ns[smh::kMaxFftStages];  // 1 / Ns of the stage
-    int tmul[smh::kMaxFftStages];      // M / (Ns * radix)
+    Stages st;
 };
 
-// ---- complex helpers and butterflies: copies of smh_stft.hip's (that file's machine code stays as it is) ------------------------
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // * (-i)
-__device__ __forceinline__ int pad(int i) { return i + (i >> 4); }
-// exact floor(it / n) for 0 <= it < 2^20 given inv = 1/n
-__device__ __forceinline__ int fdiv(int it, float inv) { return (int)(((float)it + 0.5f) * inv); }
-
-template <int R>
-__device__ __forceinline__ void dft_generic(float2 *v) {
-    float2 o[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-        float2 acc = v[0];
-#pragma unroll
-        for (int r = 1; r < R; ++r) {
-            const int e = (r * q) % R;
-            const double ang = -6.283185307179586476925 * (double)e / (double)R;
-            const float2 w = make_float2((float)__builtin_cos(ang), (float)__builtin_sin(ang));  // constant-folded
-            acc = cadd(acc, cmul(v[r], w));
-        }
-        o[q] = acc;
-    }
-#pragma unroll
-    for (int q = 0; q < R; ++q) v[q] = o[q];
-}
-
-__device__ __forceinline__ void dft4(float2 &a, float2 &b, float2 &c, float2 &d) {
-    const float2 s0 = cadd(a, c), d0 = csub(a, c);
-    const float2 s1 = cadd(b, d), d1 = mul_mi(csub(b, d));
-    a = cadd(s0, s1);
-    b = cadd(d0, d1);
-    c = csub(s0, s1);
-    d = csub(d0, d1);
-}
-
-template <int R>
-__device__ __forceinline__ void dft(float2 *v) {
-    if constexpr (R == 2) {
-        const float2 a = v[0], b = v[1];
-        v[0] = cadd(a, b);
-        v[1] = csub(a, b);
-    } else if constexpr (R == 4) {
-        dft4(v[0], v[1], v[2], v[3]);
-    } else if constexpr (R == 8) {
-        // 8 = 2 x 4: even/odd 4-point DFTs, odd outputs twisted by w8^k
-        float2 e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
-        float2 o0 = v[1], o1 = v[3], o2 = v[5], o3 = v[7];
-        dft4(e0, e1, e2, e3);
-        dft4(o0, o1, o2, o3);
-        const float h = 0.70710678118654752440f;
-        o1 = make_float2(h * (o1.x + o1.y), h * (o1.y - o1.x));    // * (1 - i)/sqrt2
-        o2 = mul_mi(o2);                                           // * (-i)
-        o3 = make_float2(h * (o3.y - o3.x), -h * (o3.x + o3.y));   // * (-1 - i)/sqrt2
-        v[0] = cadd(e0, o0), v[4] = csub(e0, o0);
-        v[1] = cadd(e1, o1), v[5] = csub(e1, o1);
-        v[2] = cadd(e2, o2), v[6] = csub(e2, o2);
-        v[3] = cadd(e3, o3), v[7] = csub(e3, o3);
-    } else if constexpr (R == 5) {
-        // Winograd-style 5-point DFT: 34 real operations
-        const float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f;
-        const float s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;
-        const float2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]);
-        const float2 t3 = csub(v[1], v[4]), t4 = csub(v[2], v[3]);
-        const float2 a1 = make_float2(v[0].x + c1 * t1.x + c2 * t2.x, v[0].y + c1 * t1.y + c2 * t2.y);
-        const float2 a2 = make_float2(v[0].x + c2 * t1.x + c1 * t2.x, v[0].y + c2 * t1.y + c1 * t2.y);
-        const float2 b1 = make_float2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y);
-        const float2 b2 = make_float2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
-        v[0] = make_float2(v[0].x + t1.x + t2.x, v[0].y + t1.y + t2.y);
-        v[1] = make_float2(a1.x + b1.y, a1.y - b1.x);  // a1 - i b1
-        v[4] = make_float2(a1.x - b1.y, a1.y + b1.x);  // a1 + i b1
-        v[2] = make_float2(a2.x + b2.y, a2.y - b2.x);
-        v[3] = make_float2(a2.x - b2.y, a2.y + b2.x);
-    } else {
-        dft_generic<R>(v);
-    }
-}
-
-// One Stockham stage for butterfly j of one frame (Govindaraju et al. formulation).  FIRST: the inputs are the windowed real frame
-// read straight from global memory, z[m] = (x[2m], x[2m+1]); the window comes from LDS here.
-template <int R, bool FIRST>
-__device__ __forceinline__ void stage(int step, int j, int Ns, float inv_ns, int tmul, const float2 *__restrict__ src,
-                                      float2 *__restrict__ dst, const float2 *__restrict__ tw,
-                                      const float *__restrict__ audio, const float *__restrict__ win) {
-    float2 v[R];
-    if constexpr (FIRST) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int m = j + r * step;
-            v[r] = make_float2(audio[2 * m] * win[2 * m], audio[2 * m + 1] * win[2 * m + 1]);
-        }
-    } else {
-        const int k = j - fdiv(j, inv_ns) * Ns;
-        const int tstep = k * tmul;  // exp(-2 pi i k r / (Ns R)) = twM[k r M/(Ns R)]
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            float2 x = src[pad(j + r * step)];
-            if (r > 0) x = cmul(x, tw[r * tstep]);
-            v[r] = x;
-        }
-    }
-    dft<R>(v);
-    const int k = FIRST ? 0 : j - fdiv(j, inv_ns) * Ns;
-    const int j0 = (j - k) * R + k;  // (j / Ns) * Ns * R + k
-#pragma unroll
-    for (int r = 0; r < R; ++r) dst[pad(j0 + r * Ns)] = v[r];
-}
-
-template <bool FIRST>
-__device__ __forceinline__ void run_stage(int nb, int R, int j, int Ns, float inv_ns, int tmul, const float2 *src,
-                                          float2 *dst, const float2 *tw, const float *audio, const float *win) {
-    switch (R) {
-        case 2: stage<2, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 3: stage<3, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 4: stage<4, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 5: stage<5, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 7: stage<7, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 8: stage<8, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        default: break;
-    }
-}
-
-// ---- the real-FFT bin pair ------------------------------------------------------------------------------------------------------
-// X[k] of the real frame from the packed transform: zk = Z[k], zm = Z[M - k], w = exp(-2 pi i k / n_fft);
-// X = (e - i w d) / 2 with e = zk + conj zm, d = zk - conj zm  (smh_stft.hip's untangle)
-__device__ __forceinline__ float2 untangle(float2 zk, float2 zm, float2 w) {
-    const float2 e = make_float2(zk.x + zm.x, zk.y - zm.y), d = make_float2(zk.x - zm.x, zk.y + zm.y);
-    const float2 wd = cmul(w, d);
-    return make_float2(0.5f * (e.x + wd.y), 0.5f * (e.y - wd.x));
-}
-// the inverse: conj Z'[k] from xk = X[k], xm = X[M - k]; Z' = E + i O, E = (xk + conj xm) / 2, O = (xk - conj xm) / 2 * conj w
+// the inverse of smh_fft.h's untangle: conj Z'[k] from xk = X[k], xm = X[M - k]; Z' = E + i O, E = (xk + conj xm) / 2, O = (xk - conj xm) / 2 * conj w
 __device__ __forceinline__ float2 tangle_conj(float2 xk, float2 xm, float2 w) {
     const float2 e = make_float2(xk.x + xm.x, xk.y - xm.y), d = make_float2(xk.x - xm.x, xk.y + xm.y);
     const float2 o = make_float2(d.x * w.x + d.y * w.y, d.y * w.x - d.x * w.y);  // d conj w
     return make_float2(0.5f * (e.x - o.y), -0.5f * (e.y + o.x));
-}
-// librosa.util.softmask(X, X_ref, power=2, split_zeros=True) for both orientations, margin 1: the float32 operation order of
-// smh_feat.hip's hpss_masks (= numpy's): Z = max; bad = Z < tiny -> Z = 1; (X/Z)^2; m / (m + r); bad -> 0.5
-__device__ __forceinline__ void masks(float h, float p, float &mh, float &mp) {
-    float Z = fmaxf(h, p);
-    const bool bad = Z < FLT_MIN;
-    Z = bad ? 1.0f : Z;
-    const float a = h / Z, b = p / Z;
-    const float m = __fmul_rn(a, a), r = __fmul_rn(b, b);
-    const float den = __fadd_rn(m, r);
-    mh = bad ? 0.5f : m / den;
-    mp = bad ? 0.5f : r / den;
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -220,16 +75,16 @@ hpss_resynth_kernel(ResynthArgs a, const float *__restrict__ audio, const float 
         // 1: forward transform of the pass's frames
         float2 *src = R0, *dst = R1;
         int Ns = 1;
-        for (int s = 0; s < a.n_stages; ++s) {
-            const int R = a.radix[s];
+        for (int s = 0; s < a.st.n_stages; ++s) {
+            const int R = a.st.radix[s];
             const int nb = M / R;
             __syncthreads();
             for (int it = threadIdx.x; it < nf * nb; it += blockDim.x) {
-                const int f = fdiv(it, a.inv_nb[s]), j = it - f * nb;
+                const int f = fdiv(it, a.st.inv_nb[s]), j = it - f * nb;
                 if (s == 0)
-                    run_stage<true>(nb, R, j, Ns, 1.f, 0, nullptr, dst + f * MP, tw, clip + (size_t)(p0 + f) * a.hop, win);
+                    run_stage<true, float2>(nb, R, j, Ns, 1.f, 0, nullptr, dst + f * MP, tw, clip + (size_t)(p0 + f) * a.hop, win);
                 else
-                    run_stage<false>(nb, R, j, Ns, a.inv_ns[s], a.tmul[s], src + f * MP, dst + f * MP, tw, nullptr, nullptr);
+                    run_stage<false, float2>(nb, R, j, Ns, a.st.inv_ns[s], a.st.tmul[s], src + f * MP, dst + f * MP, tw, nullptr, nullptr);
             }
             float2 *tmp = src;
             src = dst;
@@ -247,8 +102,8 @@ hpss_resynth_kernel(ResynthArgs a, const float *__restrict__ audio, const float 
             const float2 x1 = untangle(zk, zm, w1), x2 = untangle(zm, zk, w2);
             const size_t o1 = spec + (size_t)k * a.T + (size_t)(p0 + f), o2 = spec + (size_t)k2 * a.T + (size_t)(p0 + f);
             float mh1, mp1, mh2, mp2;
-            masks(harm[o1], perc[o1], mh1, mp1);
-            masks(harm[o2], perc[o2], mh2, mp2);
+            smh::softmask_pair(harm[o1], perc[o1], mh1, mp1);
+            smh::softmask_pair(harm[o2], perc[o2], mh2, mp2);
             const float2 h1 = make_float2(x1.x * mh1, x1.y * mh1), h2 = make_float2(x2.x * mh2, x2.y * mh2);
             const float2 q1 = make_float2(x1.x * mp1, x1.y * mp1), q2 = make_float2(x2.x * mp2, x2.y * mp2);
             Zh[pad(k)] = tangle_conj(h1, h2, w1);
@@ -261,16 +116,16 @@ hpss_resynth_kernel(ResynthArgs a, const float *__restrict__ audio, const float 
         // 3: both inverses as 2 * nf forward transforms of conj Z'
         float2 *hs = src, *hd = dst, *ps = R2, *pd = R3;
         Ns = 1;
-        for (int s = 0; s < a.n_stages; ++s) {
-            const int R = a.radix[s];
+        for (int s = 0; s < a.st.n_stages; ++s) {
+            const int R = a.st.radix[s];
             const int nb = M / R;
             __syncthreads();
             for (int it = threadIdx.x; it < 2 * nf * nb; it += blockDim.x) {
-                const int q = fdiv(it, a.inv_nb[s]), j = it - q * nb;
+                const int q = fdiv(it, a.st.inv_nb[s]), j = it - q * nb;
                 const bool pc = q >= nf;
                 const int f = pc ? q - nf : q;
-                run_stage<false>(nb, R, j, Ns, a.inv_ns[s], a.tmul[s], (pc ? ps : hs) + f * MP, (pc ? pd : hd) + f * MP, tw, nullptr,
-                                 nullptr);
+                run_stage<false, float2>(nb, R, j, Ns, a.st.inv_ns[s], a.st.tmul[s], (pc ? ps : hs) + f * MP, (pc ? pd : hd) + f * MP, tw,
+                                         nullptr, nullptr);
             }
             float2 *tmp = hs;
             hs = hd, hd = tmp;
@@ -367,7 +222,7 @@ extern "C" int smh_hpss_resynth_f32(const smh_ctx *ctx, const float *d_audio, in
     ResynthArgs a{};
     a.n_samples = n_samples, a.n_fft = ctx->cfg.n_fft, a.hop = ctx->cfg.hop, a.M = ctx->M, a.K = ctx->K, a.T = T;
     a.tile = p.tile, a.halo = p.halo, a.pass = p.pass, a.acc = (int)p.acc;
-    smh_stft::fill_stages(ctx->radix, ctx->n_stages, a);
+    fill_stages(ctx->radix, ctx->n_stages, a.M, a.st);
     return smh::launch_lds(hpss_resynth_kernel, "hpss_resynth_kernel", dim3((unsigned)p.tiles, (unsigned)B), dim3(p.threads), p.lds,
                            smh_resynth::kLdsLimit, (hipStream_t)stream, a, d_audio, ctx->d_window, ctx->d_twM, ctx->d_tw2M, d_harm, d_perc,
                            d_y_harm, d_y_perc);

@@ -206,7 +206,8 @@ __device__ __forceinline__ void walk_pairs(const FeatPlan &fp, int seg, int half
             f32x2 X;
             constexpr float kDenMin = 7.8886091e-31f;  // 2^-100: below it (digital silence) the normalised form with its split_zeros rule
             if (__builtin_expect(__any(den.x < kDenMin || den.y < kDenMin), 0)) {
-                auto one = [&](float s, float h, float p) {  // librosa.util.softmask as smh_feat.hip's hpss_masks_fast evaluates it
+                auto one = [&](float s, float h, float p) {  // smh_softmask.h's softmask_pair_fast, this half's side only (called as that, the
+                                                             // whole walk compiles to other code, not this branch alone)
                     float Z = fmaxf(h, p);
                     const bool bad = Z < FLT_MIN;
                     Z = bad ? 1.0f : Z;

@@ -6,152 +6,24 @@
 // Stockham autosort FFT that lives entirely in LDS (ping-pong buffers, one butterfly per thread),
 // un-tangled into the n_fft/2+1 real-FFT bins and written as magnitudes, frame-fastest, so that the
 // (K, T) freq-major layout librosa returns is produced directly.  n_fft = 400 -> M = 200 = 8*5*5.
-// Butterflies: radix 8 (= 2x4 in registers), radix 4, radix 2, Winograd radix 5, generic 3 / 7.
-// LDS indices are padded (one float2 per 16) so that the strided Stockham writes spread over banks;
-// work-item -> (frame, butterfly) maps use a reciprocal multiply instead of an integer division.
+// The FFT itself (stage table, butterflies, stages, the untangle) is smh_fft.h's.
 // HBM traffic per clip: 64,000 B audio in (re-reads of the 2.5x frame overlap are served by L2),
 // 78,792 B magnitudes out.
 #include "smh_common.h"
+#include "smh_fft.h"
 #include "smh_rag.h"
 
 namespace {
 
 using namespace smh_stft;  // the plan's constants (kThreads, kMP400: stft400_kernel's float2 frame stride) and functions
+using namespace smh_fft;
 
 struct StftArgs {
     int n_samples, n_fft, hop, M, K, T, tt;  // tt = frames per workgroup
-    int n_stages;
-    int radix[smh::kMaxFftStages];
-    float inv_nb[smh::kMaxFftStages];  // 1 / (M / radix)
-    float inv_ns[smh::kMaxFftStages];  // 1 / Ns of the stage
-    int tmul[smh::kMaxFftStages];      // M / (Ns * radix)
+    Stages st;
     float inv_tt;
     int B, xcd_tiles;  // xcd_tiles > 0: 1-D grid, neighbouring tiles on one XCD (smh_xcd.h); the value is the tiles per clip
 };
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // * (-i)
-__device__ __forceinline__ int pad(int i) { return i + (i >> 4); }
-// exact floor(it / n) for 0 <= it < 2^20 given inv = 1/n
-__device__ __forceinline__ int fdiv(int it, float inv) { return (int)(((float)it + 0.5f) * inv); }
-
-template <int R>
-__device__ __forceinline__ void dft_generic(float2 *v) {
-    float2 o[R];
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-        float2 acc = v[0];
-#pragma unroll
-        for (int r = 1; r < R; ++r) {
-            const int e = (r * q) % R;
-            const double ang = -6.283185307179586476925 * (double)e / (double)R;
-            const float2 w = make_float2((float)__builtin_cos(ang), (float)__builtin_sin(ang));  // constant-folded
-            acc = cadd(acc, cmul(v[r], w));
-        }
-        o[q] = acc;
-    }
-#pragma unroll
-    for (int q = 0; q < R; ++q) v[q] = o[q];
-}
-
-__device__ __forceinline__ void dft4(float2 &a, float2 &b, float2 &c, float2 &d) {
-    const float2 s0 = cadd(a, c), d0 = csub(a, c);
-    const float2 s1 = cadd(b, d), d1 = mul_mi(csub(b, d));
-    a = cadd(s0, s1);
-    b = cadd(d0, d1);
-    c = csub(s0, s1);
-    d = csub(d0, d1);
-}
-
-template <int R>
-__device__ __forceinline__ void dft(float2 *v) {
-    if constexpr (R == 2) {
-        const float2 a = v[0], b = v[1];
-        v[0] = cadd(a, b);
-        v[1] = csub(a, b);
-    } else if constexpr (R == 4) {
-        dft4(v[0], v[1], v[2], v[3]);
-    } else if constexpr (R == 8) {
-        // 8 = 2 x 4: even/odd 4-point DFTs, odd outputs twisted by w8^k
-        float2 e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
-        float2 o0 = v[1], o1 = v[3], o2 = v[5], o3 = v[7];
-        dft4(e0, e1, e2, e3);
-        dft4(o0, o1, o2, o3);
-        const float h = 0.70710678118654752440f;
-        o1 = make_float2(h * (o1.x + o1.y), h * (o1.y - o1.x));    // * (1 - i)/sqrt2
-        o2 = mul_mi(o2);                                           // * (-i)
-        o3 = make_float2(h * (o3.y - o3.x), -h * (o3.x + o3.y));   // * (-1 - i)/sqrt2
-        v[0] = cadd(e0, o0), v[4] = csub(e0, o0);
-        v[1] = cadd(e1, o1), v[5] = csub(e1, o1);
-        v[2] = cadd(e2, o2), v[6] = csub(e2, o2);
-        v[3] = cadd(e3, o3), v[7] = csub(e3, o3);
-    } else if constexpr (R == 5) {
-        // Winograd-style 5-point DFT: 34 real operations
-        const float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f;
-        const float s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;
-        const float2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]);
-        const float2 t3 = csub(v[1], v[4]), t4 = csub(v[2], v[3]);
-        const float2 a1 = make_float2(v[0].x + c1 * t1.x + c2 * t2.x, v[0].y + c1 * t1.y + c2 * t2.y);
-        const float2 a2 = make_float2(v[0].x + c2 * t1.x + c1 * t2.x, v[0].y + c2 * t1.y + c1 * t2.y);
-        const float2 b1 = make_float2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y);
-        const float2 b2 = make_float2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
-        v[0] = make_float2(v[0].x + t1.x + t2.x, v[0].y + t1.y + t2.y);
-        v[1] = make_float2(a1.x + b1.y, a1.y - b1.x);  // a1 - i b1
-        v[4] = make_float2(a1.x - b1.y, a1.y + b1.x);  // a1 + i b1
-        v[2] = make_float2(a2.x + b2.y, a2.y - b2.x);
-        v[3] = make_float2(a2.x - b2.y, a2.y + b2.x);
-    } else {
-        dft_generic<R>(v);
-    }
-}
-
-// One Stockham stage for butterfly j of one frame (Govindaraju et al. formulation).
-template <int R, bool FIRST>
-__device__ __forceinline__ void stage(int step, int j, int Ns, float inv_ns, int tmul, const float2 *__restrict__ src,
-                                      float2 *__restrict__ dst, const float2 *__restrict__ tw,
-                                      const float *__restrict__ audio, const float *__restrict__ win) {
-    float2 v[R];
-    if constexpr (FIRST) {
-        // read the windowed real frame straight from global memory: z[m] = (x[2m], x[2m+1])
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int m = j + r * step;
-            v[r] = make_float2(audio[2 * m] * win[2 * m], audio[2 * m + 1] * win[2 * m + 1]);
-        }
-    } else {
-        const int k = j - fdiv(j, inv_ns) * Ns;
-        const int tstep = k * tmul;  // exp(-2 pi i k r / (Ns R)) = twM[k r M/(Ns R)]
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            float2 x = src[pad(j + r * step)];
-            if (r > 0) x = cmul(x, tw[r * tstep]);
-            v[r] = x;
-        }
-    }
-    dft<R>(v);
-    const int k = FIRST ? 0 : j - fdiv(j, inv_ns) * Ns;
-    const int j0 = (j - k) * R + k;  // (j / Ns) * Ns * R + k
-#pragma unroll
-    for (int r = 0; r < R; ++r) dst[pad(j0 + r * Ns)] = v[r];
-}
-
-template <bool FIRST>
-__device__ __forceinline__ void run_stage(int nb, int R, int j, int Ns, float inv_ns, int tmul, const float2 *src,
-                                          float2 *dst, const float2 *tw, const float *audio, const float *win) {
-    switch (R) {
-        case 2: stage<2, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 3: stage<3, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 4: stage<4, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 5: stage<5, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 7: stage<7, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        case 8: stage<8, FIRST>(nb, j, Ns, inv_ns, tmul, src, dst, tw, audio, win); break;
-        default: break;
-    }
-}
 
 // |re + i im| on the hardware square root (v_sqrt_f32, 1 ulp): the correctly rounded expansion of sqrtf costs ~12 more
 // instructions per bin and the STFT kernels are VALU-bound; the parity bound on |S| is 1e-5 of its maximum
@@ -192,16 +64,16 @@ stft_mag_kernel(StftArgs a, const float *__restrict__ audio, const float *__rest
 
     float2 *src = buf0, *dst = buf1;
     int Ns = 1;
-    for (int s = 0; s < a.n_stages; ++s) {
-        const int R = a.radix[s];
+    for (int s = 0; s < a.st.n_stages; ++s) {
+        const int R = a.st.radix[s];
         const int nb = M / R;
         __syncthreads();
         for (int it = threadIdx.x; it < nf * nb; it += blockDim.x) {
-            const int f = fdiv(it, a.inv_nb[s]), j = it - f * nb;
+            const int f = fdiv(it, a.st.inv_nb[s]), j = it - f * nb;
             if (s == 0)
-                run_stage<true>(nb, R, j, Ns, 1.f, 0, nullptr, dst + f * MP, tw, clip + (size_t)(t0 + f) * a.hop, window);
+                run_stage<true, float2>(nb, R, j, Ns, 1.f, 0, nullptr, dst + f * MP, tw, clip + (size_t)(t0 + f) * a.hop, window);
             else
-                run_stage<false>(nb, R, j, Ns, a.inv_ns[s], a.tmul[s], src + f * MP, dst + f * MP, tw, nullptr, nullptr);
+                run_stage<false, float2>(nb, R, j, Ns, a.st.inv_ns[s], a.st.tmul[s], src + f * MP, dst + f * MP, tw, nullptr, nullptr);
         }
         float2 *tmp = src;
         src = dst;
@@ -215,6 +87,7 @@ stft_mag_kernel(StftArgs a, const float *__restrict__ audio, const float *__rest
     for (int it = threadIdx.x; it < nf * a.K; it += blockDim.x) {
         const int k = fdiv(it, inv_nf), f = it - k * nf;
         const float2 *Z = src + f * MP;
+        // smh_fft.h's untangle(), written out: called as that function, one multiply of this loop comes out with its operands swapped
         const float2 zk = Z[pad(k == M ? 0 : k)];
         float2 zc = Z[pad(k == 0 ? 0 : M - k)];
         zc.y = -zc.y;
@@ -605,7 +478,7 @@ int launch(const smh_ctx *ctx, const StftPlan &p, const float *d_audio, int n_it
     if (p.kernel == kGeneric) {
         StftArgs a;
         a.n_fft = ctx->cfg.n_fft, a.hop = ctx->cfg.hop, a.M = ctx->M, a.K = ctx->K;
-        fill_stages(ctx->radix, ctx->n_stages, a);
+        fill_stages(ctx->radix, ctx->n_stages, a.M, a.st);
         a.n_samples = n_samples, a.T = T, a.tt = p.frames, a.inv_tt = 1.0f / (float)a.tt, a.B = n_items, a.xcd_tiles = p.xcd_tiles;
         return smh::launch_lds(stft_mag_kernel, d_clips ? "stft_mag_kernel (ragged)" : "stft_mag_kernel", grid, block, p.lds, p.lds, st, a, d_audio,
                                ctx->d_window, ctx->d_twM, ctx->d_tw2M, d_S, d_clips, d_items);

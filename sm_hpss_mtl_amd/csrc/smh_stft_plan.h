@@ -6,7 +6,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <iterator>
 
 #include "smh_xcd.h"
 
@@ -129,20 +128,6 @@ inline void stft_plan_ints(const StftPlan &p, int *out) {
     const int v[10] = {p.kernel,   p.frames,      p.pass_frames, p.tiles,     p.threads,
                        (int)p.lds, (int)p.grid_x, (int)p.grid_y, p.xcd_tiles, p.pairs};
     for (int i = 0; i < 10; ++i) out[i] = v[i];
-}
-
-// the FFT stage table of StftArgs / Stft64Args: per stage the radix, 1 / (M / radix), 1 / Ns and M / (Ns * radix)
-template <class Args>
-void fill_stages(const int *radix, int n_stages, Args &a) {
-    a.n_stages = n_stages;
-    for (int i = 0, ns = 1; i < (int)std::size(a.radix); ++i) {
-        a.radix[i] = i < n_stages ? radix[i] : 1;
-        a.inv_nb[i] = (float)a.radix[i] / (float)a.M;
-        a.inv_ns[i] = 1.0f / (float)ns;
-        a.tmul[i] = a.M / (ns * a.radix[i]) > 0 ? a.M / (ns * a.radix[i]) : 0;
-        ns *= a.radix[i];
-        if (ns > a.M) ns = a.M;
-    }
 }
 
 }  // namespace smh_stft
