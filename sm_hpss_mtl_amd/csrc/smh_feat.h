@@ -1,6 +1,7 @@
 // Internal interface between smh_feat.hip and smh_frontend.hip.
 #pragma once
 #include "smh_common.h"
+#include "smh_wave.h"
 
 namespace smh_rag {
 struct Clip;
@@ -140,10 +141,7 @@ __device__ __forceinline__ void patch_range(int u, int W, int shift, int nP, int
 
 // ---- the per-file StandardScaler of smh_standardize_rows_f32, shared with the patch statistics (smh_skew.hip): ONE definition, so
 // that a value standardised there is bit for bit the patch element written here ------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+using smh::wave_sum;  // smh_wave.h: the xor-tree order
 
 // sklearn StandardScaler statistics of one row held by one wave: float64 mean / population variance,
 // (near-)constant rows are left unscaled (sklearn _is_constant_feature / _handle_zeros_in_scale).

@@ -48,10 +48,7 @@ using smh_fvtable::fill_table;
 using smh_fvtable::FvClip;
 using smh_fvtable::kMaxClips;
 
-__device__ __forceinline__ double wave_sum(double a) {
-    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
-    return a;
-}
+using smh::wave_sum;  // smh_wave.h: the xor-tree order
 
 __global__ void __launch_bounds__(64 * kWaves)
 row_moments_kernel(const FvClip *__restrict__ clips, int rows, int nrb, double *__restrict__ moments, int *__restrict__ nonfinite) {

@@ -1,8 +1,21 @@
-// Wave-level sum shared by the heads-training kernels (smh_train.hip, smh_train_cascade.hip).
+// Wave-level sums: the DPP float sum of the heads-training kernels (smh_train.hip, smh_train_cascade.hip,
+// smh_train_single.hip) and the xor-tree f64 sum of the f64 statistics (smh_silence.hip, smh_feat.h, smh_scale.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+
+namespace smh {
+
+// Sum over the 64 lanes, result in every lane, as a butterfly: lane i adds lane i ^ 32, then ^ 16, ... ^ 1.  Results that
+// are compared bit for bit (the per-file StandardScaler, the normalisation means, the mixing energies) were fixed on this
+// order.  smh_tcn::wave_sum_f below adds in ANOTHER order (rows of 16 first) and must not replace it.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+}  // namespace smh
 
 namespace smh_tcn {
 

@@ -4,8 +4,8 @@ tests/golden/make_silence_runs_golden.py import it, and none of them imports ano
 
 It holds
   (a) CRAFTED: energies written frame by frame for `remove_silence` (which takes the energy as an input), each with the claim it
-      is there for -- the branch of silence_runs_kernel / silence_compact_kernel (smh_silence.hip) that no audio clip reaches on
-      purpose;
+      is there for -- the branch of find_runs / compacted_index (smh_silence.hip: the rules that silence_runs_kernel,
+      silence_compact_kernel and preprocess_fused_kernel call) that no audio clip reaches on purpose;
   (b) AUDIO: clips for `preprocess_signal` at the lengths where its route or its load path changes, and at other frame parameters;
   (c) MIXED_BATCH: one batch of clips with different outcomes;
   and the route arithmetic of smh_preprocess_signal_f32 restated from the source.
@@ -34,13 +34,13 @@ def n_frames(N, fs, Tw, Ts):
     return 1 + (N + 2 * (frame // 2) - frame) // hop
 
 
-# ---- route arithmetic of smh_preprocess_signal_f32 (restated from smh_silence.hip: fused_plan) ----------------------------------
+# ---- route arithmetic of smh_preprocess_signal_f32 (restated from smh_silence.hip: plan_frames / CondPlan) ------------------
 FUSED_MAX_N = 36000
 LDS_BUDGET = 155 * 1024
 
 
 def lds_bytes(N, frame, hop):
-    """Dynamic LDS of preprocess_fused_kernel: samples rounded up to a multiple of 4, energies (float), run table (maxrun x 3 int),
+    """Dynamic LDS of preprocess_fused_kernel (CondPlan::lds): samples rounded up to a multiple of 4, energies (float), run table (maxrun x 3 int),
     raw and filtered frame markers (bytes)."""
     nF = 1 + (N + 2 * (frame // 2) - frame) // hop
     maxrun = nF // 2 + 2

@@ -1,7 +1,9 @@
 """Host-only test of the case table tests/silence_cases.py: with oracle/silence.py alone, every crafted case does what its claim
 says, every audio case keeps its silence decision out of reach of float32 summation order, and the route arithmetic restated in
 the table gives the figures worked out from smh_silence.hip.  (The GPU tests of tests/test_silence_edges_gpu.py then compare the
-kernels with the same oracle on cases that are known to reach the branch they name.)"""
+kernels with the same oracle on cases that are known to reach the branch they name.)  The last two tests ask the library itself,
+which loads without a GPU: what callers allocate (the workspace sizes) and what the route query rejects."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -168,3 +170,49 @@ def test_route_arithmetic():
     routes = {(n, sc.route(n, a.fs, a.Tw, a.Ts)) for a, n in sc.AUDIO_PARAMS}
     assert {(36000, 1), (36001, 0), (33408, 1), (33409, 0), (44101, 0)} <= routes
     assert {n % 4 for n, r in routes if r == 1} == {0, 1, 2, 3}
+
+
+# ---- the library's host plan (smh_silence.hip: CondPlan, carve), no GPU ---------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    from sm_hpss_mtl_amd import _lib
+    lib = _lib.load()
+    lib.smh_internal_preprocess_route.restype = C.c_int  # test-only export, not in include/smh.h
+    lib.smh_internal_preprocess_route.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    return lib
+
+
+def test_workspace_sizes_are_the_recorded_ones(lib):
+    """Bytes that smh_silence_workspace_bytes(B, N, hop) and smh_normalize_workspace_bytes(B, N) returned before the plan struct
+    existed: callers allocate by them, so they are pinned as literals."""
+    recorded = {(1, 201, 160): (3584, 2560), (3, 16000, 160): (197888, 2560), (8, 36001, 16): (1371136, 3328),
+                (136, 160000, 160): (88723968, 54784)}
+    for (B, N, hop), (silence, normalize) in recorded.items():
+        assert lib.smh_silence_workspace_bytes(B, N, hop) == silence, (B, N, hop)
+        assert lib.smh_normalize_workspace_bytes(B, N) == normalize, (B, N)
+    # (1, 201, 160) by hand: ten regions of at most 256 bytes (sums, mean, two maxima, two counts, run table, two markers,
+    # energies) and 201 floats rounded up to 1024 bytes
+    assert 10 * 256 + 1024 == 3584
+    for B, N, hop in ((-1, 201, 160), (1, 0, 160), (1, 201, 0), (1, 201, -3)):  # rejected arguments: 0 bytes
+        assert lib.smh_silence_workspace_bytes(B, N, hop) == 0
+    assert lib.smh_normalize_workspace_bytes(-1, 201) == 0 and lib.smh_normalize_workspace_bytes(1, 0) == 0
+
+
+def test_route_query_rejects_what_the_entry_rejects(lib, monkeypatch):
+    monkeypatch.delenv("SMH_SILENCE_MULTIPASS", raising=False)
+    route = lib.smh_internal_preprocess_route
+    for N, fs, Tw, Ts in ((0, 16000, 25, 10), (16000, 0, 25, 10), (16000, 16000, 0, 10), (16000, 16000, 25, 0),  # bad parameters
+                          (16000, 20, 25, 10),   # frame 0.5 and shift 0.2 samples: both round to zero
+                          (16000, 30, 40, 25),   # frame 1 sample, shift 0.75: the shift rounds to zero
+                          (16000, 30, 25, 40),   # shift 1 sample, frame 0.75: the frame size rounds to zero
+                          (200, 16000, 25, 10),  # N <= frame / 2 = 200: no reflect padding
+                          (1, 1000, 2, 1)):      # the smallest such: frame 2, N = 1
+        frame, hop = sc.frame_params(fs, Tw, Ts)
+        assert min(N, fs, Tw, Ts) < 1 or frame < 1 or hop < 1 or N <= frame // 2  # the case is what its comment says
+        assert route(N, fs, Tw, Ts) == -1, (N, fs, Tw, Ts)
+    # the first accepted neighbours
+    assert route(201, 16000, 25, 10) == 1 and route(2, 1000, 2, 1) == 1 and route(1, 1000, 1, 1) == 1
+    assert route(36001, 16000, 25, 10) == 0
+    assert route(16000, 1000, 1, 1) == sc.route(16000, 1000, 1, 1) == 0  # frame and shift of one sample: the tables outgrow LDS
+    monkeypatch.setenv("SMH_SILENCE_MULTIPASS", "1")  # read on every call
+    assert route(201, 16000, 25, 10) == 0 and route(200, 16000, 25, 10) == -1
