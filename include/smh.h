@@ -146,6 +146,30 @@ size_t smh_hpss_audio_workspace_bytes(const smh_ctx *ctx, int B, int n_samples);
 int smh_hpss_audio_f32(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, float *d_y_harm, float *d_y_perc,
                        void *d_work, size_t work_bytes, void *stream);
 
+/* ---- a3' for clips of DIFFERENT lengths in one call (the layout of the ragged front ends below: HOST arrays h_offsets, h_lengths).
+ * Clip b is h_lengths[b] samples at float h_offsets[b] of d_audio; its two components go to the same offsets of d_y_harm and
+ * d_y_perc, and the floats between clips are not written.  ONE LAUNCH PER STAGE for all clips: the STFT of every clip in the context's
+ * precision, both medians, the resynthesis kernel in its ragged form, on a descriptor table and (clip, tile) work lists uploaded in
+ * one copy from a pinned slot of the context.  The medians write harm in 16-frame blocks and the resynthesis reads it there.
+ * CONTRACT: every clip's two components are bit for bit what smh_hpss_audio_f32 gives that clip alone (B = 1, at its address),
+ * whatever else is in the call, whatever the sub-batching, in every run.  No atomics.
+ * Clips the ragged kernels do not cover go through smh_hpss_audio_f32 one by one on the same stream, same result in the same place:
+ * every clip of a context without a block-split median kernel (a window above 21) or under SMH_RAGGED_PERFILE; a clip with T <=
+ * l_harm / 2 + 4 frames (or K <= l_perc / 2 + 4 bins); a clip that starts off an 8-byte boundary where the f32 STFT reads float2
+ * (n_fft = 400, even hop: keep every offset a multiple of 4 samples); a clip beyond 32-bit row offsets (2^29 elements).
+ * smh_hpss_audio_ragged_sizes: h_T (or NULL) gets every clip's frames, *work_bytes (or NULL) the workspace that takes every clip at
+ *   once -- tables, then S, perc and blocked harm of every clip --, at most 8 GiB and never less than the largest single clip needs
+ *   (smh_hpss_audio_workspace_bytes(ctx, 1, len) included).  A smaller workspace that still holds the largest single clip (what
+ *   _sizes answers for that clip alone) runs the call in sub-batches, same bits; below that: SMH_E_WORKSPACE.
+ * Refused with SMH_E_INVALID before anything is enqueued, the text naming the clip at fault: null pointers; B < 0; a clip shorter
+ * than n_fft; a negative offset; two clips that overlap; an output whose extent (first clip .. last clip) overlaps the audio's, the
+ * workspace or the other output; a workspace off a 16-byte boundary; a capturing stream (the tables come from a staging buffer);
+ * the configurations smh_hpss_resynth_f32 refuses.  B == 0 returns SMH_OK and touches nothing.  Every offset is 64-bit. */
+int smh_hpss_audio_ragged_sizes(const smh_ctx *ctx, const long long *h_offsets, const int *h_lengths, int B, int *h_T /* or NULL */,
+                                size_t *work_bytes /* or NULL */);
+int smh_hpss_audio_ragged_f32(const smh_ctx *ctx, const float *d_audio, const long long *h_offsets, const int *h_lengths, int B,
+                              float *d_y_harm, float *d_y_perc, void *d_work, size_t work_bytes, void *stream);
+
 /* ---- a4: librosa.feature.melspectrogram(S=X, n_mels=) = mel_basis(22050, n_fft) @ X ---------
  * d_X (B, K, T) -> d_Y (B, n_mels, T)  (preprocessing.py:409-410,419,421)                       */
 int smh_mel_f32(const smh_ctx *ctx, const float *d_X, int B, int T, float *d_Y, void *stream);

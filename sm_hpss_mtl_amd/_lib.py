@@ -55,6 +55,9 @@ SIGNATURES = {
     "smh_hpss_resynth_f32": (_i, [_vp, _fp, _i, _i, _fp, _fp, _fp, _fp, _vp]),
     "smh_hpss_audio_workspace_bytes": (_sz, [_vp, _i, _i]),
     "smh_hpss_audio_f32": (_i, [_vp, _fp, _i, _i, _fp, _fp, _vp, _sz, _vp]),
+    "smh_hpss_audio_ragged_sizes": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), _i, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_size_t)]),
+    "smh_hpss_audio_ragged_f32": (_i, [_vp, _fp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), _i, _fp, _fp, _vp, _sz, _vp]),
     "smh_mel_f32": (_i, [_vp, _fp, _i, _i, _fp, _vp]),
     "smh_power_to_db_sq_f32": (_i, [_vp, _fp, _i, _i, _fp, _vp]),
     "smh_standardize_rows_f32": (_i, [_vp, _fp, _i, _i, _fp, _vp]),
@@ -181,6 +184,7 @@ INTERNAL_SIGNATURES = {
     "smh_internal_stft_plan": (_i, [_vp, _fp, _i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     "smh_internal_median_plan": (_i, [_i] * 9 + [C.POINTER(C.c_int)]),
     "smh_internal_resynth_plan": (_i, [_vp, _i, C.POINTER(C.c_int)]),
+    "smh_internal_hpss_audio_ragged_route": (_i, [_vp, _fp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), _i, C.POINTER(C.c_int)]),
 }
 
 _lib = None

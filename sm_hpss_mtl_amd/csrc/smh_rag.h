@@ -30,7 +30,8 @@ struct Clip {
     int Ttiled;           // frames after tile-if-short (lib/preprocessing.py:139-142)
     int nP;               // patches (0: none asked for)
     int row0;             // first row of this clip in the per-row statistics table (long clips only)
-    int pad_[2];
+    int n_samples;        // samples of the clip: set and read by the ragged HPSS audio separation only (smh_hpss_audio.hip), else 0
+    int pad_;
 };
 static_assert(sizeof(Clip) == 64, "smh_rag::Clip is read with 16-byte scalar loads");
 
@@ -50,7 +51,16 @@ size_t equal_overhead_bytes(const smh_ctx *ctx, int B, int T);
 int run_equal(const smh_ctx *ctx, const float *d_audio, int B, int n_samples, int T, const smh_feat::PatchOut &po, float *d_fv, void *d_work,
               size_t work_bytes, const smh_median::MedianSwitches &msw, bool stft_aligned8, hipStream_t st);
 
-// ---- the host-side planner of a ragged entry (smh_frontend_ragged_*, smh_plain_frontend_ragged_*) -------------------------------
+// Which clips the ragged STFT and median launches take, decided once for every entry that chains them (smh_frontend_ragged_*,
+// smh_hpss_audio_ragged_f32); a clip they do not take goes alone through the entry's equal-length form, with the same bits.
+//   medians_ok   the context has a block-split median kernel (rag_tile_frames > 0) and SMH_RAGGED_PERFILE is not set
+//   clip_ok      both medians fold once per side (fast_ok) and the clip's rows fit 32-bit offsets
+//   start_ok     the clip starts where the STFT kernel of an aligned call can take it: on 8 bytes where the f32 STFT reads float2
+bool medians_ok(const smh_ctx *ctx, const smh_median::MedianSwitches &msw);
+bool clip_ok(const smh_ctx *ctx, int T);
+bool start_ok(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const float *d_audio, long long off);
+
+// ---- the host-side planner of a ragged entry (smh_frontend_ragged_*, smh_plain_frontend_ragged_*, smh_hpss_audio_ragged_*) ------
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // where every clip of a call lies in the caller's buffers: frames, patches, and the floats / patches in front of clip b (B + 1 sums);

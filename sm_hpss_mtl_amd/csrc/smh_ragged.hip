@@ -403,17 +403,12 @@ size_t final_tile_bytes(int rows) { return sizeof(float) * (size_t)2 * rows * (k
 constexpr size_t kFixedBytes = 8 * 256;  // alignment slack between the regions of a sub-batch
 
 bool rag_context_ok(const smh_ctx *ctx, const smh_median::MedianSwitches &msw) {
-    if (!ctx->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS") || getenv("SMH_FEAT_TWO_KERNELS") || getenv("SMH_RAGGED_PERFILE")) return false;
+    if (!ctx->feat_walk_ok || smh::lab_env("SMH_FEAT_TAPS") || getenv("SMH_FEAT_TWO_KERNELS")) return false;
     if (ctx->feat_nseg[1] < 1 || ctx->feat_nseg[1] > 8) return false;
     if (final_tile_bytes(ctx->feat_rows) > 150 * 1024) return false;  // (this tile's own limit, not one of smh_feat.h's image budgets)
-    return smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, msw) > 0;
+    return smh_rag::medians_ok(ctx, msw);
 }
-// the block-split walkers fold once per side (windows of one have no walker)
-bool rag_clip_ok(const smh_ctx *ctx, int T) {
-    // (the streaming kernels address a clip's rows with 32-bit offsets: K * T and 2 * rows * T below 2^29 elements -- a day of audio)
-    if ((long long)(ctx->K + 16) * T >= (1ll << 29) || (long long)2 * ctx->feat_rows * T >= (1ll << 29)) return false;
-    return smh_median::fast_ok(T, ctx->cfg.l_harm) && smh_median::fast_ok(ctx->K, ctx->cfg.l_perc);
-}
+bool rag_clip_ok(const smh_ctx *ctx, int T) { return smh_rag::clip_ok(ctx, T); }
 
 // one sub-batch: tables -> one upload -> one launch per stage
 int run_sub_batch(const smh_ctx *ctx, const RagGeom &g, const float *d_audio, const HostClip *hc, int n, const PatchOut &po, float *d_fv,
@@ -511,6 +506,21 @@ int run_rag(const smh_ctx *ctx, const float *d_audio, const std::vector<HostClip
 }  // namespace
 
 namespace smh_rag {
+
+// ---- which clips the ragged STFT and median launches take (smh_rag.h) -------------------------------------------------------------
+bool medians_ok(const smh_ctx *ctx, const smh_median::MedianSwitches &msw) {
+    return !getenv("SMH_RAGGED_PERFILE") && smh_median::rag_tile_frames(ctx->K, ctx->cfg.l_harm, ctx->cfg.l_perc, msw) > 0;
+}
+// the block-split walkers fold once per side (windows of one have no walker)
+bool clip_ok(const smh_ctx *ctx, int T) {
+    // (the streaming kernels address a clip's rows with 32-bit offsets: K * T and 2 * rows * T below 2^29 elements -- a day of audio)
+    if ((long long)(ctx->K + 16) * T >= (1ll << 29) || (long long)2 * ctx->feat_rows * T >= (1ll << 29)) return false;
+    return smh_median::fast_ok(T, ctx->cfg.l_harm) && smh_median::fast_ok(ctx->K, ctx->cfg.l_perc);
+}
+bool start_ok(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const float *d_audio, long long off) {
+    return !smh_stft::rag_needs_aligned8(smh_stft::geom_of(ctx), sw) ||
+           smh_stft::clip_aligned8(reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)off * 4);
+}
 
 // ---- the planner (smh_rag.h) ------------------------------------------------------------------------------------------------
 int plan_layout(const smh_ctx *ctx, const char *who, const long long *off, const int *len, int B, int W, int shift, bool patches,
@@ -686,10 +696,9 @@ void classify(const smh_ctx *ctx, const smh_stft::StftSwitches &sw, const smh_me
     if (!rag_context_ok(ctx, msw)) return;
     // the specialised STFT needs every frame on an 8-byte boundary: a clip that starts elsewhere takes the generic kernel when it is
     // processed alone, so it is processed alone here too (same bits either way)
-    const bool need8 = smh_stft::rag_needs_aligned8(smh_stft::geom_of(ctx), sw);
     for (int b = 0; b < B; ++b) {
         if (!rag_clip_ok(ctx, p.T[b])) continue;
-        if (need8 && !smh_stft::clip_aligned8(reinterpret_cast<uintptr_t>(d_audio) + (uintptr_t)off[b] * 4)) continue;
+        if (!smh_rag::start_ok(ctx, sw, d_audio, off[b])) continue;
         // (even T: one workgroup per clip half; odd T -- or SMH_FEAT_NOPAIR -- one per clip: the route smh_frontend_f32 takes)
         const int r = smh_rag::feature_route(ctx, msw, p.T[b]);
         if (r <= 2) cls[b] = r;

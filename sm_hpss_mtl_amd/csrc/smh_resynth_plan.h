@@ -1,7 +1,8 @@
 // Launch plan of the HPSS audio resynthesis (smh_hpss_audio.hip: masked complex STFT and overlap-add ISTFT): the tile of frames a
 // workgroup owns, its halo, the frames per LDS pass, the LDS bytes and the refusals -- decided here, once, as a plain value.
-// smh_hpss_resynth_f32, smh_hpss_audio_f32 and the test query smh_internal_resynth_plan all take it from plan().  Host arithmetic
-// only, no HIP: a stand-alone host program can include this header by itself.
+// smh_hpss_resynth_f32, smh_hpss_audio_f32 and the test query smh_internal_resynth_plan all take it from plan(); the ragged entry
+// smh_hpss_audio_ragged_f32 takes the same plan for its refusals and LDS and, for clips of different lengths in one launch, plan_rag()
+// and the per-clip sizes below it.  Host arithmetic only, no HIP: a stand-alone host program can include this header by itself.
 //
 // Tile.  A workgroup owns the kTileFrames * hop output samples that start at frame t0's first sample (the last tile of a clip owns
 // the rest of the clip too: the last frame's tail and the zeros behind it).  Frame t reaches the samples t * hop .. t * hop +
@@ -22,6 +23,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdio>
+
+#include "smh_xcd.h"
 
 namespace smh_resynth {
 
@@ -63,6 +66,40 @@ inline Plan plan(const Geom &g, int T) {
                  g.hop, kMaxHalo + 1);
     else if (p.lds > kLdsLimit)
         snprintf(p.refusal, sizeof p.refusal, "n_fft=%d, hop=%d need %zu bytes of LDS, the limit is %zu", g.n_fft, g.hop, p.lds, kLdsLimit);
+    return p;
+}
+
+// ---- clips of different lengths in one launch (hpss_resynth_rag_kernel) --------------------------------------------------------
+// The work list is flat: one (clip, tile) item per kTileFrames frames of every clip, clip-major, on the 1-D per-XCD grid (smh_xcd.h);
+// a workgroup takes T, the sample count and every offset from its clip's descriptor.  The medians of a ragged call write harm in
+// 16-frame blocks, (ceil(T / 16), K, 16): element (k, t) at ((t >> 4) * K + k) * 16 + (t & 15).  A resynthesis tile starts on a
+// multiple of kTileFrames = 16 frames, so its own frames are one block and its halo frames (at most kMaxHalo = 16) lie in the block
+// before.  S and perc are (K, T) rows of exactly T floats, each clip's rounded up to 4 floats so that the next starts on 16 bytes.
+constexpr int kHarmBlock = 16;  // frames per block of the blocked harm image (smh_median_plan.h: layout 2)
+static_assert(kTileFrames % kHarmBlock == 0 && kMaxHalo <= kHarmBlock, "a tile starts on a harm block, its halo lies in the block before");
+
+inline int rag_items(int T) { return (T + kTileFrames - 1) / kTileFrames; }  // items of a clip of T frames
+inline size_t rag_spec_floats(int K, int T) { return ((size_t)K * T + 3) / 4 * 4; }  // S, and perc, of a clip in the workspace
+inline size_t rag_harm_floats(int K, int T) { return (size_t)((T + kHarmBlock - 1) / kHarmBlock) * K * kHarmBlock; }  // blocked harm
+// workspace bytes a clip adds to a ragged call: S, perc, blocked harm, its descriptor (64 bytes) and its 8-byte (clip, tile) items
+// of the three stages -- the STFT's and the medians' tiles of stft_frames and med_frames frames, the resynthesis tiles
+inline size_t rag_clip_bytes(int K, int T, int stft_frames, int med_frames) {
+    const size_t items = (size_t)(T + stft_frames - 1) / stft_frames + (size_t)(T + med_frames - 1) / med_frames + (size_t)rag_items(T);
+    return 4 * (2 * rag_spec_floats(K, T) + rag_harm_floats(K, T)) + 64 + 8 * items;
+}
+
+struct RagPlan {
+    int tile, halo, pass, threads;
+    unsigned grid_x, grid_y;  // the per-XCD grid of n_items items
+    size_t lds, acc;
+    char refusal[96];  // plan()'s: it depends on the context alone, so it holds for the ragged call as a whole
+};
+inline RagPlan plan_rag(const Geom &g, long long n_items) {
+    const Plan q = plan(g, 1);
+    RagPlan p{};
+    p.tile = q.tile, p.halo = q.halo, p.pass = q.pass, p.threads = q.threads, p.lds = q.lds, p.acc = q.acc;
+    p.grid_x = smh::xcd_grid(n_items), p.grid_y = 1;
+    snprintf(p.refusal, sizeof p.refusal, "%s", q.refusal);
     return p;
 }
 

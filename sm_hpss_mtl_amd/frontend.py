@@ -320,6 +320,49 @@ class Frontend:
                                                _stream()), "smh_hpss_audio_f32")
         return {"harmonic": yh, "percussive": yp}
 
+    def separate_ragged(self, signals, out=None):
+        """`smh_hpss_audio_ragged_f32`: signals of DIFFERENT lengths in one call, one launch per stage for all of them.  signals: list
+        of 1-D float32 arrays / tensors -> dict(harmonic=[...], percussive=[...]) in the caller's order, each entry a 1-D view of one
+        flat buffer per component and bit for bit what `separate` gives that signal alone.  The signals are packed at offsets that
+        are multiples of 4 samples, as `run_ragged` packs them; `out` may carry the two flat float32 buffers 'harmonic' /
+        'percussive' (sum of the lengths, each rounded up to 4; the floats between signals are not written)."""
+        self._need_hpss("separate_ragged")
+        B = len(signals)
+        if B == 0:
+            return {"harmonic": [], "percussive": []}
+        for i, s in enumerate(signals):
+            if s.ndim != 1:
+                raise ValueError("separate_ragged: signals[%d] must be 1-D, got shape %s" % (i, tuple(s.shape)))
+            if s.shape[0] < self.cfg.n_fft:
+                raise ValueError("separate_ragged: signals[%d] of %d samples is shorter than n_fft=%d" % (i, s.shape[0], self.cfg.n_fft))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        lens = [int(s.shape[0]) for s in signals]
+        offs, o = [], 0
+        for n in lens:
+            offs.append(o)
+            o += (n + 3) // 4 * 4  # next signal starts on a 16-byte boundary
+        if all(isinstance(s, np.ndarray) for s in signals):
+            # host signals: laid out in ONE host buffer and uploaded by ONE copy
+            host = np.zeros(o, dtype=np.float32)
+            for s, n, of in zip(signals, lens, offs):
+                host[of:of + n] = s
+            audio = torch.from_numpy(host).to(device=dev)
+        else:
+            audio = torch.zeros(o, dtype=torch.float32, device=dev)
+            for s, n, of in zip(signals, lens, offs):
+                t = s if isinstance(s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32))
+                audio[of:of + n] = t.to(device=dev, dtype=torch.float32)
+        yh = _out(out, "harmonic", (o,), torch.float32, dev)
+        yp = _out(out, "percussive", (o,), torch.float32, dev)
+        h_off, h_len = (C.c_longlong * B)(*offs), (C.c_int * B)(*lens)
+        work = C.c_size_t()
+        _lib.check(self.lib.smh_hpss_audio_ragged_sizes(self._h, h_off, h_len, B, None, C.byref(work)), "smh_hpss_audio_ragged_sizes")
+        if self._work is None or self._work.numel() < work.value or self._work.device != dev:
+            self._work = torch.empty(max(work.value, 1), dtype=torch.uint8, device=dev)
+        _lib.check(self.lib.smh_hpss_audio_ragged_f32(self._h, _ptr(audio), h_off, h_len, B, _ptr(yh), _ptr(yp), _ptr(self._work),
+                                                      self._work.numel(), _stream()), "smh_hpss_audio_ragged_f32")
+        return {"harmonic": [yh[of:of + n] for of, n in zip(offs, lens)], "percussive": [yp[of:of + n] for of, n in zip(offs, lens)]}
+
     def mel(self, X):
         X = _f32c(X, "X")
         B, K, T = X.shape
